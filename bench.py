@@ -4,6 +4,8 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: re-executes itself under
                                                               torch.distributed.run with N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR                    (also writes the poses of the last timed step as DIR/poses.npy:
+                                                              same arguments, same inputs -- two builds compare output for output)
 
 A "step" is one pass of the hot path over one batch of synthetic input = sampling `--clips-per-gpu` 320-frame clips per GPU
 (4 windows x 1000 denoising steps each).  Default: 1 clip at batch 1 = BASELINE config[1].  `--clips-per-gpu 16` is the
@@ -69,7 +71,12 @@ def parse(argv=None):
                         "(auto: whenever --gpus > 1 runs the default 1-clip-per-GPU workload)")
     p.add_argument("--sub-records", default="auto", choices=["auto", "on", "off"],
                    help="config2 / config3 / config4 / stream sub-records in the JSON line (auto: the default 1-GPU config[1] run)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the poses of the last timed step (all clips, gathered to rank 0) as DIR/poses.npy "
+                        "(float32; beyond 64 MB a fixed seeded sample of whole clips)")
     a = p.parse_args(argv)
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     if a.batch and not a.clips_per_gpu:
         a.clips_per_gpu, a.mode = a.batch, "lockstep"
     a.clips_per_gpu = a.clips_per_gpu or 1
@@ -87,6 +94,22 @@ def parse(argv=None):
     else:
         a.lanes = a.clips_per_gpu if a.mode == "streams" else 1
     return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, poses):
+    """`--dump-outputs DIR`: what the timed path returned to its caller in the last timed step -- the poses [clips, frames, dims] --
+    as DIR/poses.npy.  A larger output keeps DUMP_BYTES worth of whole clips, drawn with a fixed seed and kept in clip order, so that
+    two builds run with the same arguments write the same clips."""
+    import numpy as np
+    poses = np.ascontiguousarray(np.asarray(poses, np.float32))
+    if poses.nbytes > DUMP_BYTES:
+        keep = np.random.default_rng(0).choice(poses.shape[0], DUMP_BYTES // poses[0].nbytes, replace=False)
+        poses = poses[np.sort(keep)]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "poses.npy"), poses)
 
 
 def self_launch(a):
@@ -420,8 +443,8 @@ def main():
             # ... and 16 clips in lock step in bf16w2 (round 6: the ROWS kernel set on two-register fragments), one window of 1000 steps
             subs["precision"]["bf16w2_16clips"] = sub_record("16 clips in lock step in bf16w2 (1 of the 4 windows of a 320-frame ZEGGS clip, 1000 DDPM steps)",
                                                              "zeggs", 16, 1, "ddpm", 1, n_windows=1, warm_skip=960, precision="bf16w2")
-    if rank == 0 and os.environ.get("DSG_BENCH_DUMP"):      # TEST INFRASTRUCTURE (tests/test_bench_launch.py): the gathered poses, by clip id
-        np.save(os.environ["DSG_BENCH_DUMP"], np.asarray(gathered, np.float32))
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, gathered)
     if rank == 0:
         n_clips = world * NC * a.steps
         value = n_clips * frames_per_clip / dt

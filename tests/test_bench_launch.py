@@ -31,12 +31,12 @@ def test_bench_gpus2_spawns_two_ranks(emu_lib, tmp_path):
     from diffusestylegesture_amd.model import DSGDenoiser
     from diffusestylegesture_amd.sample import generate_clip
     from diffusestylegesture_amd.synth import synth_state_dict, synth_window_inputs
-    dump = str(tmp_path / "gathered.npy")
-    out = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--precision", "fp32", "--clips-per-gpu", "2"], {"DSG_BENCH_DUMP": dump})
+    dump = str(tmp_path / "dump")
+    out = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--precision", "fp32", "--clips-per-gpu", "2", "--dump-outputs", dump], {})
     assert out["n_gpus"] == 2 and out["config"]["clips_per_gpu"] == 2 and out["config"]["mode"] == "streams"
     assert out["config"]["parallelism"] == "clips x2" and out["value"] > 0 and out["scaling"] == "weak"
     assert "EMULATED" in out["data"]
-    got = np.load(dump)
+    got = np.load(os.path.join(dump, "poses.npy"))
     cfg = C.TINY
     assert got.shape[0] == 4
     m = DSGDenoiser(cfg, precision="fp32", max_batch=1, library=emu_lib)
@@ -59,6 +59,45 @@ def test_bench_single_rank_modes(emu_lib):
     assert c["config3"]["clips"] == 16 and c["config3"]["value"] > 0 and c["config3"]["kernel_set"] == "tile"
 
 
+def test_bench_dump_outputs_is_the_last_timed_step(emu_lib, tmp_path):
+    """`--dump-outputs DIR` writes the poses of the LAST of the `--steps` timed passes: pass i of the run samples with seed 123456 + i
+    (warm-up passes first), so with --warmup 1 --steps 2 the dump is the clip sampled with seed 123458."""
+    import numpy as np
+    from diffusestylegesture_amd import config as C
+    from diffusestylegesture_amd.diffusion import create_gaussian_diffusion
+    from diffusestylegesture_amd.model import DSGDenoiser
+    from diffusestylegesture_amd.sample import generate_clip
+    from diffusestylegesture_amd.synth import synth_state_dict, synth_window_inputs
+    dump = str(tmp_path / "dump")
+    out = _run(["--steps", "2", "--warmup", "1", "--precision", "fp32", "--no-cpu-baseline", "--dump-outputs", dump], {})
+    assert out["steps"] == 2 and out["warmup"] == 1
+    assert os.listdir(dump) == ["poses.npy"]
+    got = np.load(os.path.join(dump, "poses.npy"))
+    cfg = C.TINY
+    m = DSGDenoiser(cfg, precision="fp32", max_batch=1, library=emu_lib)
+    m.load_state_dict(synth_state_dict(cfg, 20240))
+    d = create_gaussian_diffusion(library=emu_lib)
+    feats = [synth_window_inputs(cfg, 1, window=w, clips=[0])["audio"] for w in range(2)]
+    want = generate_clip(m, d, feats, [1] + [0] * (cfg.style_dim_in - 1), seed=123458, smoothing=True, stream_id=0, skip_timesteps=997)
+    assert got.dtype == np.float32 and np.array_equal(got, want)
+
+
+def test_bench_dump_outputs_caps_size(tmp_path):
+    """An output above 64 MB is dumped as a fixed seeded sample of whole clips, in clip order; a smaller one whole."""
+    import numpy as np
+    import bench
+    poses = np.repeat(np.arange(40, dtype=np.float32), 1000 * 500).reshape(40, 1000, 500)       # 2e6 bytes per clip, 8e7 in all
+    bench.dump_outputs(str(tmp_path / "a"), poses)
+    bench.dump_outputs(str(tmp_path / "b"), poses)
+    a = np.load(str(tmp_path / "a" / "poses.npy"))
+    assert a.shape == (bench.DUMP_BYTES // poses[0].nbytes, 1000, 500) and a.nbytes <= bench.DUMP_BYTES
+    ids = a[:, 0, 0]
+    assert (np.diff(ids) > 0).all() and all((a[i] == ids[i]).all() for i in range(len(ids)))
+    assert np.array_equal(a, np.load(str(tmp_path / "b" / "poses.npy")))
+    bench.dump_outputs(str(tmp_path / "c"), poses[:5])
+    assert np.array_equal(np.load(str(tmp_path / "c" / "poses.npy")), poses[:5])
+
+
 def test_bench_gpus8_spawns_eight_ranks_128_clips(emu_lib, tmp_path):
     """Round-4 verdict 8b: the launch shape of BASELINE config[3] itself -- `bench.py --gpus 8 --clips-per-gpu 16` creates EIGHT ranks
     (emulated library, gloo), every rank samples its 16 of the 128 tiny clips as 4 lanes x batch 4, rank 0 gathers; gathered[c] must be
@@ -71,12 +110,12 @@ def test_bench_gpus8_spawns_eight_ranks_128_clips(emu_lib, tmp_path):
     from diffusestylegesture_amd.parallel import shard_clips
     from diffusestylegesture_amd.sample import generate_clip
     from diffusestylegesture_amd.synth import synth_state_dict, synth_window_inputs
-    dump = str(tmp_path / "gathered8.npy")
-    out = _run(["--gpus", "8", "--steps", "1", "--warmup", "0", "--precision", "fp32", "--clips-per-gpu", "16"],
-               {"DSG_BENCH_DUMP": dump, "DSG_BENCH_SKIP": "999", "DSG_EMU_THREADS": "1", "OMP_NUM_THREADS": "1"})
+    dump = str(tmp_path / "dump")
+    out = _run(["--gpus", "8", "--steps", "1", "--warmup", "0", "--precision", "fp32", "--clips-per-gpu", "16", "--dump-outputs", dump],
+               {"DSG_BENCH_SKIP": "999", "DSG_EMU_THREADS": "1", "OMP_NUM_THREADS": "1"})
     assert out["n_gpus"] == 8 and out["config"]["clips_per_gpu"] == 16 and out["config"]["lanes"] == 4 and out["config"]["batch_per_lane"] == 4
     assert out["config"]["parallelism"] == "clips x8" and out["collective_backend"] == "gloo" and "5th compute queue" in out["config"]["workload"]
-    got = np.load(dump)
+    got = np.load(os.path.join(dump, "poses.npy"))
     cfg = C.TINY
     assert got.shape[0] == 128 and np.isfinite(got).all()
     assert len({got[c].tobytes() for c in range(128)}) == 128          # 128 different clips
