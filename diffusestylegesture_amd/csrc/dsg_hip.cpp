@@ -954,26 +954,31 @@ extern "C" int dsg_set_window_cond_cfg(dsg_handle* h, const float* style, const 
 //   nothing depends on the batch but the grid (and the register budget of the LayerNorm GEMMs from 512 rows, same arithmetic):
 //   a row's result is bit-identical whatever the batch it rides in.
 // ---------------------------------------------------------------------------------------------------------
+// A layer form names ONE fixed kernel sequence of an encoder layer (layer_<form> below).  select_kernels picks the form of every
+// layer; fused guidance swaps the last layer's (layer_form).  A form whose feed-forward ends in k_ffn / k_ffn_ln leaves LayerNorm2
+// of its rows fragment-major in X0a; the others leave pre2, which the next QKV projection / the pose head normalise on read.
+enum class Form {
+    MID,            // QKV, [k_attn], k_mid | k_attn_mid, linear2                       LATENCY
+    UNFUSED,        // QKV, k_attn, out_proj, LayerNorm1 + linear1, linear2              TILE / BLOCK without k_attn_op
+    ATTN_OP,        // QKV, k_attn_op[_w], linear1, linear2                             TILE / BLOCK with k_attn_op; the last layer under fused guidance
+    ATTN_OP_SPLIT,  // QKV, k_attn_op[_w], k_ffn_part, k_ffn_ln                         BLOCK: DSG+ widths, fp32 ZEGGS, DSG_CLIP_ATTN=0
+    CLIP_SPLIT,     // k_clip_attn, k_ffn_part<OP>, k_ffn_ln                            BLOCK, bf16 ZEGGS / tiny
+    ATTN_OP_FFN,    // QKV, k_attn_op, k_ffn                                            STREAM / ROWS under DSG_CLIP_ATTN=0
+    CLIP_FFN,       // k_clip_attn, k_ffn<OP>                                           STREAM, ROWS (bf16, bf16w2)
+    CLIP_W_FFN,     // k_clip_attn_w, k_ffn<OP>                                         ROWS at latent_dim 384 / 512
+};
+static bool leaves_x0a(Form f) { return f >= Form::ATTN_OP_SPLIT; }
 struct KernelSel {
     int set = DSG_KSET_TILE;
-    bool lat = false;           // LATENCY: fused first kernel (k_inloc) and k_mid / k_attn_mid
-    bool attn_in_mid = false;   // ... with the attention inside k_mid (batch 1)
-    bool blk = false;           // BLOCK: 32-row block GEMMs
-    bool attn_op = false;       // k_attn_op instead of k_attn + out_proj
-    bool stream = false;        // STREAM: BLOCK with the weight-stationary persistent GEMMs of dsg_stream.h (LayerNorm + QKV, linear1, linear2, pose head)
-    bool ffn = false;           // STREAM (round 4): linear1 + GELU + linear2 + residual + LayerNorm2 in one kernel (k_ffn); QKV of the next layer
-                                // and the pose head then read normalised rows: direct streaming GEMMs, no k_ln_frag
-    bool ffn16_wide = false;    // ROWS at the DSG+ widths (round 6): k_clip_attn_w (or the direct QKV GEMM + k_attn) + k_ffn<OP> on 16-row tiles
-    bool clip_w = false;        // ... with k_clip_attn_w instead of the QKV GEMM + k_attn
-    bool ffn_rt2w = false;      // ... with k_ffn<OP> on 32-row blocks: >= 3 lanes whose row tiles together exceed one round of the CUs
-    bool ffn16 = false;         // ROWS (round 6): k_ffn on 16-row tiles (one workgroup per row tile), behind k_clip_attn; everything else as BLOCK
-    bool ffn_rt4 = false;       // ... on 64-row blocks: 4 lanes x >= 4000 token rows (4 x 64 clips: 981 -> 903 us per step of the 4 lanes; 1 x 64: 376 -> 432,
-                                // 4 x 16: 334 -> 392, 4 x 32 even -- profiles/r04_y2_sweep_ffn_rt4_*.log).  Bit-identical to the 32-row form.
-    bool ffn_split = false;     // BLOCK (round 4, bf16 ZEGGS / tiny dims): k_ffn split over the hidden dimension (k_ffn_part + k_ffn_ln); direct QKV / pose head
-    bool clip_attn = false;     // BLOCK (round 5, with ffn_split): the attention half per (clip, head) -- k_clip_attn (QKV slices + attention + partial out_proj)
-                                // + k_ffn_ln (head slabs + residual + LayerNorm1) instead of the QKV GEMM + k_attn_op
-    bool xs_frag = false;       // BLOCK / STREAM (bf16, Jp 128 / 1152): the state shadow is fragment-major and the pose embedding streams it (k_ws2<EPI_PARTIAL>:
+    Form form = Form::UNFUSED;
+    bool attn_in_mid = false;   // MID: the attention inside k_mid (batch 1)
+    int ffn_rows = 0;           // *_FFN: token rows per k_ffn workgroup, 16 / 32 / 64 (bit-identical whatever the block: the same waves, the same k order)
+    bool xs_frag = false;       // BLOCK / STREAM / ROWS (bf16): the state shadow is fragment-major and the pose embedding streams it (k_ws2<EPI_PARTIAL>:
                                 // 8.9 -> 4.3 us at 1424 rows, 29.9 -> 11.0 at 5632; 3.8 -> 4.1 at 356)
+    int x0a_frag = 0;           // the layout k_loc leaves the embedding rows in (X0a): 0 row-major, 1 fragment-major, 2 ... as a hi + lo bf16 pair
+    int ks_in = 1;              // workgroup split-K of the pose embedding
+    bool blk() const { return set >= DSG_KSET_BLOCK; }       // 32-row block GEMMs (STREAM / ROWS: pose embedding and layer-0 QKV as in BLOCK)
+    bool stream() const { return set == DSG_KSET_STREAM; }   // weight-stationary streaming GEMMs (dsg_stream.h)
 };
 static bool have_attn_mid(const dsg_handle* h, int B) {
     return B == 1 && h->H == 4 && ((h->D == 256 && h->Tp == 96) || (h->D == 128 && h->Tp == 32));
@@ -1022,9 +1027,6 @@ static bool rows_w2_ok(const dsg_handle* h) {
 }
 // the streamed pose embedding at the DSG+ pose widths (round 6: k_ws2<EPI_PARTIAL, 17 / 18, 2>, K over two workgroups) -- in the ROWS set
 static bool xs_frag_wide(const dsg_handle* h, int set) {
-#ifdef DSG_X_NO_XS_WIDE      // (A/B: make dev DEVFLAGS=-DDSG_X_NO_XS_WIDE)
-    return false;
-#endif
     return (set == DSG_KSET_ROWS || set == DSG_KSET_BLOCK) && (h->Jp == 2176 || h->Jp == 2304) && (h->D == 384 || h->D == 512);
 }
 static int auto_kernel_set(const dsg_handle* h, int B, int lanes) {
@@ -1084,60 +1086,84 @@ static int resolve_auto_set(const dsg_handle* h, int B, int lanes) {
     if (h->latency_mode == 1 && latency_set_ok(h)) set = DSG_KSET_LATENCY;
     return set;
 }
-static int select_kernels(const dsg_handle* h, int B, KernelSel& k) {
-    int set = h->kset_req;
-    if (set == DSG_KSET_AUTO) set = resolve_auto_set(h, B, 1);
+// whether the handle can run `set` (not AUTO) at all: dsg_set_kernel_set refuses what every later step would
+static int check_set(const dsg_handle* h, int set) {
+    if (set < DSG_KSET_LATENCY || set > DSG_KSET_ROWS) return fail(DSG_E_INVALID, "unknown kernel set");
     if (set == DSG_KSET_LATENCY && h->D > 512) return fail(DSG_E_NOT_IMPLEMENTED, "kernel set LATENCY: latent_dim > 512");
     if ((set == DSG_KSET_STREAM || set == DSG_KSET_ROWS) && !stream_set_ok(h) && !(set == DSG_KSET_ROWS && (rows_w2_ok(h) || rows_wide_ok(h))))
         return fail(DSG_E_NOT_IMPLEMENTED, "kernel sets STREAM / ROWS: bf16 (ROWS: bf16w2 as well), latent_dim 128 / 256, 4 heads, ff 128 / 1024 only");
-    if (set < DSG_KSET_LATENCY || set > DSG_KSET_ROWS) return fail(DSG_E_INVALID, "unknown kernel set");
     if (h->prec == DSG_PREC_BF16W2 && ((set > DSG_KSET_TILE && !(set == DSG_KSET_ROWS && rows_w2_ok(h))) || (set == DSG_KSET_LATENCY && h->D > 256)))
         return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2: kernel sets LATENCY (latent_dim <= 256), TILE and ROWS (latent_dim 128 / 256) only");
+    return 0;
+}
+static int select_kernels(const dsg_handle* h, int B, KernelSel& k) {
+    int set = h->kset_req;
+    if (set == DSG_KSET_AUTO) set = resolve_auto_set(h, B, 1);
+    CHK(check_set(h, set));
+    const bool w2 = h->prec == DSG_PREC_BF16W2;
+    if (set == DSG_KSET_ROWS && h->cfgB > 0) {      // (the guided last layer runs ATTN_OP: no bf16w2 form, no k_attn_op_w in ROWS)
+        if (w2) return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2, kernel set ROWS: no fused guidance (TILE has it)");
+        if (rows_wide_ok(h)) return fail(DSG_E_NOT_IMPLEMENTED, "kernel set ROWS at the DSG+ widths: no fused guidance (BLOCK has it)");
+    }
     k = KernelSel();
     k.set = set;
-    k.lat = set == DSG_KSET_LATENCY;
-    k.attn_in_mid = k.lat && have_attn_mid(h, B);
-    k.stream = set == DSG_KSET_STREAM;
-    k.ffn = k.stream;           // (round 4: k_ffn instead of k_ws<GELU> + k_ws2<RESID> + k_ln_frag)
-    // ROWS (round 6): BLOCK's first and last kernels around STREAM's per-layer pair, with k_ffn on ONE 16-row tile per workgroup -- no ff-split,
-    // no partial slabs, no k_ffn_ln: 3 + 2L dispatches.  Every workgroup streams W_o + W1 + W2 (1.15 MB) for 16 rows, so it pays while the row
-    // tiles of all lanes fit the 256 CUs in one round
-    k.ffn16 = set == DSG_KSET_ROWS;
-    if (k.ffn16) k.ffn = true;
-    {
-        const int rows = B * h->ntok, e = h->env_ffn_rt4;      // (test hook / A/B: 64-row blocks from this many token rows at any lane count; 0: never)
-        k.ffn_rt4 = k.ffn && (e >= 0 ? (e > 0 && rows >= e) : (h->lanes_now >= 4 && rows >= 4000));
+    const int rows = B * h->ntok, e = h->env_ffn_rt4;
+    const bool clip = have_attn_op_narrow(h) && h->env_clip_attn != 0;      // (A/B: DSG_CLIP_ATTN=0 = QKV GEMM + k_attn_op, round 4)
+    // k_ffn on 64-row blocks: 4 lanes x >= 4000 token rows (4 x 64 clips: 981 -> 903 us per step of the 4 lanes; 1 x 64: 376 -> 432, 4 x 16: 334 -> 392,
+    // 4 x 32 even -- profiles/r04_y2_sweep_ffn_rt4_*.log).  DSG_FFN_RT4=<rows> (test hook / A/B): from that many token rows at any lane count; 0: never
+    const bool rt4 = h->D == 256 && (e >= 0 ? (e > 0 && rows >= e) : (h->lanes_now >= 4 && rows >= 4000));
+    switch (set) {
+        case DSG_KSET_LATENCY:
+            k.form = Form::MID;
+            k.attn_in_mid = have_attn_mid(h, B);
+            break;
+        case DSG_KSET_TILE:
+            // (k_attn_op_w -- W_o streamed: DSG+ widths, fp32 -- belongs to BLOCK only: a set's arithmetic never depends on the batch, and at batch 1
+            //  its 10 workgroups per layer lose to k_attn + out_proj -- BEAT: 200 vs 163 us/step; 16 clips: 3371 vs 2904 frames/s)
+            k.form = have_attn_op_narrow(h) ? Form::ATTN_OP : Form::UNFUSED;
+            break;
+        case DSG_KSET_BLOCK:      // (A/B: DSG_FFN_SPLIT=0 = linear1 + linear2 + LayerNorm-on-read, round 3)
+            if (ffn_split_ok(h) && h->env_ffn_split != 0) k.form = clip ? Form::CLIP_SPLIT : Form::ATTN_OP_SPLIT;
+            else k.form = have_attn_op(h) ? Form::ATTN_OP : Form::UNFUSED;
+            break;
+        case DSG_KSET_STREAM:     // (round 4: k_ffn instead of k_ws<GELU> + k_ws2<RESID> + k_ln_frag)
+            k.form = clip ? Form::CLIP_FFN : Form::ATTN_OP_FFN;
+            k.ffn_rows = rt4 ? 64 : 32;
+            break;
+        default:
+            // ROWS (round 6): BLOCK's first and last kernels around STREAM's per-layer pair, with k_ffn on ONE 16-row tile per workgroup -- no ff-split,
+            // no partial slabs, no k_ffn_ln: 3 + 2L dispatches.  Every workgroup streams W_o + W1 + W2 (1.15 MB) for 16 rows, so it pays while the row
+            // tiles of all lanes fit the 256 CUs in one round
+            if (rows_wide_ok(h)) {      // (>= 3 lanes whose row tiles together exceed one round of the CUs: 32-row blocks, see layer_clip_w_ffn)
+                k.form = Form::CLIP_W_FFN;
+                k.ffn_rows = h->lanes_now >= 3 && h->lanes_now * cdiv(rows, 16) > 256 ? 32 : 16;
+            } else if (w2 || clip) {
+                k.form = Form::CLIP_FFN;
+                k.ffn_rows = 16;
+            } else {
+                k.form = Form::ATTN_OP_FFN;
+                k.ffn_rows = rt4 ? 64 : 32;
+            }
     }
-    k.blk = set == DSG_KSET_BLOCK || set == DSG_KSET_ROWS || k.stream;      // (STREAM / ROWS: pose embedding and layer-0 QKV as in BLOCK)
-    // the wide form (W_o streamed: DSG+ widths, fp32) belongs to BLOCK / STREAM only -- a set's arithmetic never depends on the batch,
-    // and at batch 1 its 10 workgroups per layer lose to k_attn + out_proj (BEAT: 200 vs 163 us/step; 16 clips: 3371 vs 2904 frames/s)
-    if (k.ffn16 && h->prec == DSG_PREC_BF16W2 && h->cfgB > 0) return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2, kernel set ROWS: no fused guidance (TILE has it)");
-    k.attn_op = !k.lat && (have_attn_op_narrow(h) || (k.blk && have_attn_op_wide(h)) || (k.ffn16 && rows_w2_ok(h)));
-    k.ffn16_wide = k.ffn16 && rows_wide_ok(h);
-    if (k.ffn16_wide) {
-#if !defined(DSG_X_NO_CLIP_W)      // (A/B: make dev DEVFLAGS=-DDSG_X_NO_CLIP_W)
-        k.clip_w = h->H == 4 && h->Tp == 160;
-#endif
-#if defined(DSG_X_FFN_RT2W)      // (A/B: 0 never, 1 always)
-        k.ffn_rt2w = DSG_X_FFN_RT2W != 0;
-#else
-        k.ffn_rt2w = h->lanes_now >= 3 && h->lanes_now * cdiv(B * h->ntok, 16) > 256;
-#endif
-        if (h->cfgB > 0) return fail(DSG_E_NOT_IMPLEMENTED, "kernel set ROWS at the DSG+ widths: no fused guidance (BLOCK has it)");
-        k.attn_op = false;      // k_attn writes the attention rows, k_ffn<OP> does out_proj + LayerNorm1
-    }
-    k.xs_frag = k.blk && h->prec == DSG_PREC_BF16 && (h->Jp == 1152 || h->Jp == 128 || xs_frag_wide(h, set));
-    if (set == DSG_KSET_BLOCK && ffn_split_ok(h)) k.ffn_split = h->env_ffn_split != 0;      // (A/B: DSG_FFN_SPLIT=0 = linear1 + linear2 + LayerNorm-on-read, round 3)
-    k.clip_attn = (k.ffn_split || k.ffn) && have_attn_op_narrow(h) && h->env_clip_attn != 0;      // (A/B: DSG_CLIP_ATTN=0 = QKV GEMM + k_attn_op, round 4)
-    if (k.ffn16 && h->prec == DSG_PREC_BF16W2) k.clip_attn = true;
-
+    k.xs_frag = k.blk() && h->prec == DSG_PREC_BF16 && (h->Jp == 1152 || h->Jp == 128 || xs_frag_wide(h, set));
+    const bool clip_form = k.form == Form::CLIP_SPLIT || k.form == Form::CLIP_FFN || k.form == Form::CLIP_W_FFN;
+    k.x0a_frag = (k.stream() || clip_form) ? (w2 ? 2 : 1) : 0;
+    // split-K of the pose-embedding GEMM across workgroups: one split per 256 pose features for the 16 x 16 tile kernel; the block kernel splits K
+    // over its 4 waves already, so 2 workgroup splits keep a wave's share at <= 8 k-blocks (one batch of loads) without fragmenting the work 5 ways.
+    // (streamed embedding: K stays whole but at the DSG+ pose widths, see k_ws2; bf16w2: the 16 x 16 tiles)
+    k.ks_in = k.xs_frag ? (h->Jp > 1152 ? 2 : 1) : ((k.blk() && !w2) ? std::min(h->KSin, 2) : h->KSin);
     return 0;
+}
+// fused guidance: the last layer leaves pre2 to the two-pass pose head k_gemm_cfg, which normalises on read -- where the set's form
+// leaves X0a, that layer runs the round-3 feed-forward kernels behind k_attn_op instead
+static Form layer_form(const dsg_handle* h, const KernelSel& k, int l) {
+    return h->cfgB > 0 && l == h->L - 1 && leaves_x0a(k.form) ? Form::ATTN_OP : k.form;
 }
 
 // buffers only one kernel set needs, allocated when a call first runs that set (never inside a graph capture / packet recording:
 // the callers invoke this right after select_kernels)
 static int ensure_set_buffers(dsg_handle* h, const KernelSel& k) {
-    if (k.ffn_split && !h->ffn_part) {
+    if ((k.form == Form::ATTN_OP_SPLIT || k.form == Form::CLIP_SPLIT) && !h->ffn_part) {
         const bool was = h->alloc_uc;
         h->alloc_uc = true;
         const int rc = dalloc(h, &h->ffn_part, (size_t)(ffn_split_wide(h) ? 8 : 4) * h->ffn_slab);      // [S][M_pad][D] fp32, loop-written: uncached like the other activations
@@ -1150,12 +1176,7 @@ static int ensure_set_buffers(dsg_handle* h, const KernelSel& k) {
 extern "C" int dsg_set_kernel_set(dsg_handle* h, int set) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
     if (set < DSG_KSET_AUTO || set > DSG_KSET_ROWS) return fail(DSG_E_INVALID, "dsg_set_kernel_set: unknown kernel set");
-    if (set == DSG_KSET_LATENCY && h->D > 512) return fail(DSG_E_NOT_IMPLEMENTED, "kernel set LATENCY: latent_dim > 512");
-    if ((set == DSG_KSET_STREAM || set == DSG_KSET_ROWS) && !stream_set_ok(h) && !(set == DSG_KSET_ROWS && (rows_w2_ok(h) || rows_wide_ok(h))))
-        return fail(DSG_E_NOT_IMPLEMENTED, "kernel sets STREAM / ROWS: bf16 (ROWS: bf16w2 as well), latent_dim 128 / 256, 4 heads, ff 128 / 1024 only");
-    // (the same rule as select_kernels: round-5 advisor -- this entry point used to accept LATENCY at latent_dim 384 / 512, and every later call failed)
-    if (h->prec == DSG_PREC_BF16W2 && ((set > DSG_KSET_TILE && !(set == DSG_KSET_ROWS && rows_w2_ok(h))) || (set == DSG_KSET_LATENCY && h->D > 256)))
-        return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2: kernel sets LATENCY (latent_dim <= 256), TILE and ROWS (latent_dim 128 / 256) only");
+    if (set != DSG_KSET_AUTO) CHK(check_set(h, set));      // (round-5 advisor: this entry point used to accept LATENCY at latent_dim 384 / 512, and every later call failed)
     if (getenv("DSG_KSET")) {                  // an A/B run pinned the set for the whole process: say so once, keep the pinned set
         static std::atomic<bool> said{false};
         if (set != h->kset_req && !said.exchange(true))
@@ -1186,7 +1207,8 @@ extern "C" int dsg_last_kernel_set(dsg_handle* h, int* set) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// one denoising step = 3 + 4*L dispatches (TILE / BLOCK with k_attn_op; 3 + 5*L without) or 2 + 3*L (LATENCY, batch 1)
+// one denoising step = the pose embedding + local attention (k_in + k_loc; LATENCY: k_inloc), L layers of one form (2 .. 5 dispatches each,
+// enum Form) and the pose head: 3 + 2L (ROWS / STREAM) .. 3 + 5L (TILE without k_attn_op), LATENCY 2 + 3L at batch 1
 // ---------------------------------------------------------------------------------------------------------
 struct StepCtx {
     int B;                  // batch rows the kernels run on (with guidance: conditional elements + their twins)
@@ -1296,14 +1318,6 @@ static int launch_ws(dsg_handle* h, GemmArgs g) {
         if (K == 384) return step_launch<&k_ws<EPI, 24, true>>(h, grid1, dim3(256), g);      // (round 6: the DSG+ widths, one workgroup per CU)
         if (K == 512) return step_launch<&k_ws<EPI, 32, true>>(h, grid1, dim3(256), g);
     } else {
-        if constexpr (EPI == EPI_QKV) {      // (round 6: the DSG+ widths, one workgroup per CU)
-            if (K == 384 || K == 512) {
-                g.ws_G = ws_groups(P, MB, 1);
-                const dim3 gridw(ws_grid_x(P, g.ws_G));
-                if (K == 384) return step_launch<&k_ws<EPI, 24>>(h, gridw, dim3(256), g);
-                return step_launch<&k_ws<EPI, 32>>(h, gridw, dim3(256), g);
-            }
-        }
         const dim3 grid(ws_grid_x(P, g.ws_G));
         if (K == 256) return step_launch<&k_ws<EPI, 16>>(h, grid, dim3(256), g);
         if (K == 128) return step_launch<&k_ws<EPI, 8>>(h, grid, dim3(256), g);
@@ -1355,28 +1369,20 @@ template <class P, int PRO, int EPI>
 static int launch_gemm_w(dsg_handle* h, const GemmArgs& g, const KernelSel& ks) {
     constexpr bool blk_wins = EPI == EPI_QKV || EPI == EPI_GELU;
     if constexpr (sizeof(typename P::elem) == 2 && !P::W2 && PRO == PRO_DIRECT && (EPI == EPI_GELU || EPI == EPI_QKV || EPI == EPI_OUT)) {
-        if (ks.stream && g.a_frag) return launch_ws<EPI>(h, g);      // STREAM: linear1 on the fragment-major LayerNorm1 rows of k_attn_op
-        // (round 6, ROWS at the DSG+ widths: the weight-stationary QKV GEMM with a 192 / 256-register panel, one workgroup per CU -- bit-identical to the block form.
-        //  latent 384 from 1200 rows: BEAT 1 x 16 clips 417.9 -> 402.7 us per step, 4 x 8: 616 -> 591, 4 x 16: 1161 -> 1050, 4 x 4 even; latent 512 only with
-        //  several lanes: TWH 4 x 8: 799 -> 780, but 1 x 16: 526 -> 540, 1 x 24: 661 -> 682 -- profiles/r06_df_*)
-        if constexpr (EPI == EPI_QKV) {
-            if (ks.ffn16_wide && g.a_frag && g.M >= 1200 && (g.D == 384 || h->lanes_now >= 2)) return launch_ws<EPI>(h, g);
-        }
+        if (ks.stream() && g.a_frag) return launch_ws<EPI>(h, g);      // STREAM: linear1 on the fragment-major LayerNorm1 rows of k_attn_op
         // (the streaming pose head below the STREAM sizes loses: BLOCK 1 x 16 clips 207.5 -> 211.6 us per step, 4 x 4: 197.5 -> 205.4 -- profiles/r06_h_*, round 6)
         // (... at the DSG+ widths it wins or is even everywhere in ROWS -- k_ws<OUT, 24 / 32, ONE>: 112 VGPRs + 32 AGPRs, the panel re-read per block: BEAT 1 x 16 clips
         //  358.3 -> 353.8 us per step, 4 x 8: 440.9 -> 423.3, 4 x 16: 615.6 -> 568.3; TWH 1 x 16 even, 4 x 16: 878 -> 844 -- profiles/r06_ds_*; 32 x 32 x 16 MFMAs: the
         //  pose head's last bits differ from the 16 x 16 tiles', so it belongs to the set, not to the lane count)
-#ifndef DSG_X_NO_WS_OUT_WIDE
         if constexpr (EPI == EPI_OUT) {
-            if (ks.ffn16_wide && g.a_frag) return launch_ws<EPI>(h, g);
+            if (ks.form == Form::CLIP_W_FFN && g.a_frag) return launch_ws<EPI>(h, g);
         }
-#endif
     }
     if constexpr (sizeof(typename P::elem) == 2 && !P::W2 && PRO == PRO_LN && (EPI == EPI_QKV || EPI == EPI_OUT)) {
-        if (ks.stream) return launch_ln_ws<EPI>(h, g);                    // STREAM: LayerNorm once per row, then the same streaming GEMM
+        if (ks.stream()) return launch_ln_ws<EPI>(h, g);                    // STREAM: LayerNorm once per row, then the same streaming GEMM
     }
     if constexpr (EPI != EPI_PARTIAL && !P::W2) {
-        if (ks.blk && blk_wins && g.KBtot * P::KB <= 512) return launch_blk<P, PRO, EPI>(h, g);
+        if (ks.blk() && blk_wins && g.KBtot * P::KB <= 512) return launch_blk<P, PRO, EPI>(h, g);
     }
     if constexpr (PRO == PRO_LN) {
         if (g.M >= 512) {
@@ -1398,10 +1404,10 @@ static int launch_gemm_w(dsg_handle* h, const GemmArgs& g, const KernelSel& ks) 
 template <class P>
 static int launch_gemm_k4(dsg_handle* h, const GemmArgs& g, const KernelSel& ks) {
     if constexpr (sizeof(typename P::elem) == 2 && !P::W2) {
-        if (ks.stream && g.a_frag) return launch_ws2<EPI_RESID>(h, g);
+        if (ks.stream() && g.a_frag) return launch_ws2<EPI_RESID>(h, g);
     }
     if constexpr (!P::W2) {
-        if (ks.blk) return launch_blk_k<P, EPI_RESID>(h, g);
+        if (ks.blk()) return launch_blk_k<P, EPI_RESID>(h, g);
     }
     return launch_gemm<P, PRO_DIRECT, EPI_RESID, 1, 4>(h, g);
 }
@@ -1412,7 +1418,10 @@ static int launch_attn_t(dsg_handle* h, const AttnArgs& a) {
     return step_launch<&k_attn<P, HD, NKT>>(h, dim3(nqt, a.H, a.B), dim3(64), a);
 }
 template <class P>
-static int launch_attn(dsg_handle* h, const AttnArgs& a) {
+static int launch_attn(dsg_handle* h, int B) {
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = h->q; a.k = h->k; a.vt = h->vt; a.out = h->attn; a.B = B; a.H = h->H; a.ntok = h->ntok; a.Tp = h->Tp; a.D = h->D;
     const int key = h->hd * 1000 + h->Tp / 16;
     switch (key) {
         case 32 * 1000 + 2: return launch_attn_t<P, 32, 2>(h, a);
@@ -1485,6 +1494,275 @@ static StepTables step_tables(const dsg_handle* h) {
     return st;
 }
 
+// the GemmArgs every GEMM of a step of B batch rows starts from
+static GemmArgs gemm_base(const dsg_handle* h, int B) {
+    GemmArgs z;
+    memset(&z, 0, sizeof(z));
+    z.KS = 1; z.B = B; z.ntok = h->ntok; z.Tp = h->Tp; z.H = h->H; z.hd = h->hd; z.T = h->T; z.J = h->J; z.Jp = h->Jp;
+    z.Jq = h->Jq; z.D = h->D; z.inv_ntok4 = fastdiv_inv(rup(h->ntok, 4));
+    return z;
+}
+// k_loc / k_inloc: the embedding's KS partial sums -> the local attention -> X0 (fp32) + X0a (in the layout x0a_frag)
+static LocArgs loc_args(const dsg_handle* h, int B, int KS, const StepCtl* ctl, int x0a_frag) {
+    LocArgs la;
+    memset(&la, 0, sizeof(la));
+    la.partial = h->partial; la.KS = KS; la.Min_pad = cdiv(B * h->T, 16) * 16; la.Cf = h->Cf; la.TE2 = h->TE2; la.TE = h->TE;
+    la.emb1 = h->emb1; la.ctl = ctl; la.t_arr = h->t_arr;
+    la.rcos = h->rcos; la.rsin = h->rsin; la.mask = h->mask; la.mb = h->mb; la.inv_mask_div = fastdiv_inv((int)((long long)B * h->Hl / h->mb)); la.B = B; la.T = h->T; la.D = h->D; la.Hl = h->Hl;
+    la.hd = h->hdl; la.W = h->W; la.X0 = h->X0; la.X0a = h->X0a; la.nomask = h->nomask; la.x0a_frag = x0a_frag;
+    return la;
+}
+static MidArgs mid_args(const dsg_handle* h, const Layer& ly, const float* R, int M) {
+    MidArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = h->attn; a.R = R; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1;
+    a.W1 = ly.W1; a.b1 = ly.b1; a.X1 = h->X1; a.hidden = h->hidden; a.M = M; a.MT = cdiv(M, 16); a.ff = h->ff;
+    return a;
+}
+
+// What one encoder layer's launches read
+struct LayerCtx {
+    const KernelSel& ks;
+    const GemmArgs& z;      // gemm_base of the step
+    const Layer& ly;
+    int M, MT;
+    const float* R;         // the rows the attention block adds back: the embedding (X0) in layer 0, LayerNorm2 of the previous layer (Xn) after it
+    int in_frag;            // where the layer's input rows are: X0a in that layout (layer 0: ks.x0a_frag; after a form that leaves X0a: 1), or
+    const Layer* prev;      // -1: pre2, with LayerNorm2 of the previous layer (prev) applied on read
+};
+static ClipAttnArgs clip_attn_args(const dsg_handle* h, const LayerCtx& y) {
+    ClipAttnArgs a;
+    a.X = h->X0a; a.Wqkv = y.ly.Wqkv; a.bqkv = y.ly.bqkv; a.out = h->attn; a.B = y.z.B; a.ntok = h->ntok;
+    return a;
+}
+// k_ffn: linear1 + GELU + linear2 + residual + LayerNorm2 -> Xn fp32 + X0a in the GEMM type.  OP: out_proj + residual + LayerNorm1
+// as the prologue (A = the attention rows); else A = k_attn_op's fragment-major LayerNorm1 rows
+static FfnArgs ffn_args(const dsg_handle* h, const LayerCtx& y, bool op) {
+    const Layer& ly = y.ly;
+    FfnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = h->X1a; a.R = h->X1; a.W1 = ly.W1; a.b1 = ly.b1; a.W2 = ly.W2; a.b2 = ly.b2; a.ln_g = ly.g2; a.ln_b = ly.be2;
+    a.Xn = h->Xn; a.Xa = h->X0a; a.M = y.M; a.MT = y.MT;
+    if (op) { a.A = h->attn; a.R = y.R; a.Wo = ly.Wo; a.bo = ly.bo; a.ln1_g = ly.g1; a.ln1_b = ly.be1; a.X1 = h->X1; }
+    return a;
+}
+
+// ---- the launches the layer forms share
+template <class P>
+static int qkv_gemm(dsg_handle* h, const LayerCtx& y) {
+    GemmArgs g = y.z;
+    g.M = y.M; g.MT = y.MT; g.NT = 3 * h->D / 16; g.KBtot = h->D / P::KB; g.Wp = y.ly.Wqkv; g.bias = y.ly.bqkv;
+    g.q = h->q; g.k = h->k; g.vt = h->vt;
+    if (y.in_frag >= 0) {
+        g.A = h->X0a; g.lda = h->D; g.a_frag = y.in_frag;
+        return launch_gemm_w<P, PRO_DIRECT, EPI_QKV>(h, g, y.ks);
+    }
+    g.X = h->pre2; g.ln_g = y.prev->g2; g.ln_b = y.prev->be2; g.Xn = h->Xn;
+    return launch_gemm_w<P, PRO_LN, EPI_QKV>(h, g, y.ks);
+}
+// attention + out_proj + residual + LayerNorm1 in one kernel per (query tile, batch element); the next kernel reads the normalised rows in the
+// GEMM type (k_attn_op2 -- two query tiles per workgroup -- is retired: experiments/dsg_rejected_kernels.h)
+template <class P>
+static int attn_op(dsg_handle* h, const LayerCtx& y) {
+    const Layer& ly = y.ly;
+    AttnOpArgs a;
+    a.q = h->q; a.k = h->k; a.vt = h->vt; a.R = y.R; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1;
+    a.X1 = h->X1; a.X1a = h->X1a; a.B = y.z.B; a.ntok = h->ntok; a.Tp = h->Tp;
+    const dim3 grid(cdiv(h->ntok, 16), y.z.B);
+    const int D = h->D;
+    if constexpr (sizeof(typename P::elem) == 2) {
+        if (D == 256 && h->Tp == 96) return step_launch<&k_attn_op<P, 4, 6>>(h, grid, dim3(256), a);
+        if (D == 128 && h->Tp == 32) return step_launch<&k_attn_op<P, 2, 2>>(h, grid, dim3(256), a);
+        if (D == 384) return step_launch<&k_attn_op_w<P, 6, 10>>(h, grid, dim3(256), a);
+        return step_launch<&k_attn_op_w<P, 8, 10>>(h, grid, dim3(256), a);
+    } else {
+        if (D == 256) return step_launch<&k_attn_op_w<P, 4, 6>>(h, grid, dim3(256), a);
+        return step_launch<&k_attn_op_w<P, 2, 2>>(h, grid, dim3(256), a);
+    }
+}
+// round 5: per (clip, head) -- QKV slices + attention in one kernel (k_clip_attn); out_proj + residual + LayerNorm1 are the prologue of the
+// feed-forward kernel behind it (OP): Q / K / V never leave the CU and the QKV GEMM is gone as a dispatch
+template <class P>
+static int clip_attn(dsg_handle* h, const LayerCtx& y) {
+    const ClipAttnArgs a = clip_attn_args(h, y);
+    if (h->D == 256) return step_launch<&k_clip_attn<P, 4, 6>>(h, dim3(4, y.z.B), dim3(384), a);
+    return step_launch<&k_clip_attn<P, 2, 2>>(h, dim3(4, y.z.B), dim3(128), a);
+}
+template <class P>
+static int linear1_gelu(dsg_handle* h, const LayerCtx& y) {      // on k_attn_op's fragment-major LayerNorm1 rows -> hidden
+    GemmArgs g = y.z;
+    g.M = y.M; g.MT = y.MT; g.NT = h->ff / 16; g.KBtot = h->D / P::KB; g.Wp = y.ly.W1; g.bias = y.ly.b1;
+    g.A = h->X1a; g.lda = h->D; g.a_frag = 1; g.out = h->hidden; g.ldo = h->ff; g.out_frag = 1;
+    return launch_gemm_w<P, PRO_DIRECT, EPI_GELU>(h, g, y.ks);
+}
+template <class P>
+static int linear2(dsg_handle* h, const LayerCtx& y) {      // linear2 + residual -> pre2 (K = ff split over the 4 waves of the workgroup)
+    GemmArgs g = y.z;
+    g.M = y.M; g.MT = y.MT; g.NT = h->D / 16; g.KBtot = h->ff / P::KB; g.Wp = y.ly.W2; g.bias = y.ly.b2;
+    g.A = h->hidden; g.lda = h->ff; g.a_frag = 1; g.out = h->pre2; g.ldo = h->D; g.R = h->X1;
+    return launch_gemm_k4<P>(h, g, y.ks);
+}
+// BLOCK below the STREAM threshold (round 4): k_ffn split over the hidden dimension (k_ffn_part) + the slab sum / LayerNorm2 pass (k_ffn_ln).
+// profiles/r04_q_*: 1 x 16 230.9 -> 218.8 us, 4 x 4 222.4 -> 214.4, 4 x 8 288.9 -> 240.8.  OP: out_proj + residual + LayerNorm1 as the prologue
+template <class P, bool OP>
+static int ffn_split(dsg_handle* h, const LayerCtx& y) {
+    const Layer& ly = y.ly;
+    FfnPartArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = h->X1a; a.W1 = ly.W1; a.b1 = ly.b1; a.W2 = ly.W2; a.part = h->ffn_part; a.slab = h->ffn_slab; a.M = y.M; a.MT = y.MT;
+    if (OP) { a.A = h->attn; a.R = y.R; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1; a.X1 = h->X1; }
+    FfnLnArgs b;
+    b.part = h->ffn_part; b.slab = h->ffn_slab; b.R = h->X1; b.b2 = ly.b2; b.ln_g = ly.g2; b.ln_b = ly.be2; b.Xn = h->Xn; b.Xa = h->X0a; b.M = y.M;
+    const int G = cdiv(y.MT, 2);
+    const dim3 gl(cdiv(y.M, 8));
+    if constexpr (sizeof(typename P::elem) == 4) {
+        // fp32 at the ZEGGS widths (round 5, round-4 verdict item 7): the same split, 8 ways (16 k-blocks of 16 per K = 256 operand)
+        CHK((step_launch<&k_ffn_part<P, 4, 16, 2, 4, 8>>(h, dim3(G * 8), dim3(256), a)));
+        return step_launch<&k_ffn_ln<P, 4, 8, 8>>(h, gl, dim3(128), b);
+    } else {
+        if (h->D == 256) {
+            CHK((step_launch<&k_ffn_part<P, 4, 16, 2, 4, 4, OP>>(h, dim3(G * 4), dim3(256), a)));
+            return step_launch<&k_ffn_ln<P, 4, 4, 8>>(h, gl, dim3(128), b);
+        }
+        if (h->D == 128) {
+            CHK((step_launch<&k_ffn_part<P, 2, 2, 2, 4, 2, OP>>(h, dim3(G * 2), dim3(256), a)));
+            return step_launch<&k_ffn_ln<P, 2, 2, 8>>(h, gl, dim3(128), b);
+        }
+        // DSG+ widths (round 5, k_attn_op_w only): 8 ff-splits, one row tile per workgroup-pair batch of fragments
+        if (h->D == 384) {
+            CHK((step_launch<&k_ffn_part<P, 6, 16, 2, 4, 8>>(h, dim3(G * 8), dim3(256), a)));
+            return step_launch<&k_ffn_ln<P, 6, 8, 8>>(h, gl, dim3(128), b);
+        }
+        CHK((step_launch<&k_ffn_part<P, 8, 16, 2, 4, 8>>(h, dim3(G * 8), dim3(256), a)));
+        return step_launch<&k_ffn_ln<P, 8, 8, 8>>(h, gl, dim3(128), b);
+    }
+}
+
+// ---- one function per layer form (enum Form): the launches of one encoder layer, in order
+template <class P>
+static int layer_mid(dsg_handle* h, const LayerCtx& y) {
+    CHK(qkv_gemm<P>(h, y));
+    const MidArgs a = mid_args(h, y.ly, y.R, y.M);      // [attention +] out_proj + residual + LayerNorm1 + linear1 slice + GELU
+    if (y.ks.attn_in_mid) {
+        AttnMidArgs am;
+        am.mid = a; am.q = h->q; am.k = h->k; am.vt = h->vt; am.ntok = h->ntok; am.Tp = h->Tp;
+        CHK(launch_attn_mid<P>(h, am));
+    } else {
+        CHK(launch_attn<P>(h, y.z.B));
+        CHK(launch_mid<P>(h, a));
+    }
+    return linear2<P>(h, y);
+}
+template <class P>
+static int layer_unfused(dsg_handle* h, const LayerCtx& y) {
+    const int D = h->D;
+    CHK(qkv_gemm<P>(h, y));
+    CHK(launch_attn<P>(h, y.z.B));
+    {   // out_proj + residual -> pre1
+        GemmArgs g = y.z;
+        g.M = y.M; g.MT = y.MT; g.NT = D / 16; g.KBtot = D / P::KB; g.Wp = y.ly.Wo; g.bias = y.ly.bo;
+        g.A = h->attn; g.lda = D; g.a_frag = 1; g.out = h->pre1; g.ldo = D; g.R = y.R;
+        CHK((launch_gemm_w<P, PRO_DIRECT, EPI_RESID>(h, g, y.ks)));
+    }
+    {   // LayerNorm1-on-read + linear1 + GELU -> hidden ; X1 = LN1(pre1)
+        GemmArgs g = y.z;
+        g.M = y.M; g.MT = y.MT; g.NT = h->ff / 16; g.KBtot = D / P::KB; g.Wp = y.ly.W1; g.bias = y.ly.b1;
+        g.X = h->pre1; g.ln_g = y.ly.g1; g.ln_b = y.ly.be1; g.Xn = h->X1; g.out = h->hidden; g.ldo = h->ff; g.out_frag = 1;
+        CHK((launch_gemm_w<P, PRO_LN, EPI_GELU>(h, g, y.ks)));
+    }
+    return linear2<P>(h, y);
+}
+template <class P>
+static int layer_attn_op(dsg_handle* h, const LayerCtx& y) {
+    CHK(qkv_gemm<P>(h, y));
+    CHK(attn_op<P>(h, y));
+    CHK(linear1_gelu<P>(h, y));
+    return linear2<P>(h, y);
+}
+template <class P>
+static int layer_attn_op_split(dsg_handle* h, const LayerCtx& y) {
+    CHK(qkv_gemm<P>(h, y));
+    CHK(attn_op<P>(h, y));
+    return ffn_split<P, false>(h, y);
+}
+template <class P>
+static int layer_clip_split(dsg_handle* h, const LayerCtx& y) {
+    CHK(clip_attn<P>(h, y));
+    return ffn_split<P, true>(h, y);
+}
+// 64 rows per workgroup when several lanes fill the GPU with large batches: half the weight bytes through the CUs' load paths per row, half
+// the workgroups (select_kernels)
+template <class P>
+static int layer_attn_op_ffn(dsg_handle* h, const LayerCtx& y) {
+    CHK(qkv_gemm<P>(h, y));
+    CHK(attn_op<P>(h, y));
+    const FfnArgs f = ffn_args(h, y, false);
+    if (y.ks.ffn_rows == 64) return step_launch<&k_ffn<P, 4, 16, 4, 8, 1, true>>(h, dim3(cdiv(y.MT, 4)), dim3(512), f);
+    if (h->D == 256) return step_launch<&k_ffn<P, 4, 16, 2, 8, 2, true>>(h, dim3(cdiv(y.MT, 2)), dim3(512), f);
+    return step_launch<&k_ffn<P, 2, 2, 2, 4>>(h, dim3(cdiv(y.MT, 2)), dim3(256), f);
+}
+// (the weights of both phases on one rolling ring of fragments: 12 slots on 64-row blocks, 32 on 16- / 32-row blocks; the double-buffered groups of
+//  rounds 4-5 are retired)
+template <class P>
+static int layer_clip_ffn(dsg_handle* h, const LayerCtx& y) {
+    CHK(clip_attn<P>(h, y));
+    const FfnArgs f = ffn_args(h, y, true);
+    const int MT = y.MT;
+    const bool d256 = h->D == 256;
+    if constexpr (P::W2) {      // bf16w2 in the ROWS set (round 6): one 16-row tile per workgroup, two-register fragments
+        if (d256) return step_launch<&k_ffn<P, 4, 16, 1, 8, 2, true, true, 12>>(h, dim3(MT), dim3(512), f);
+        return step_launch<&k_ffn<P, 2, 2, 1, 4, 2, false, true, 8>>(h, dim3(MT), dim3(256), f);
+    } else {
+        if (y.ks.ffn_rows == 16) {      // ROWS: one 16-row tile per workgroup
+            if (d256) return step_launch<&k_ffn<P, 4, 16, 1, 8, 2, true, true, 32>>(h, dim3(MT), dim3(512), f);
+            return step_launch<&k_ffn<P, 2, 2, 1, 4, 2, false, true>>(h, dim3(MT), dim3(256), f);
+        }
+        if (y.ks.ffn_rows == 64) return step_launch<&k_ffn<P, 4, 16, 4, 8, 1, true, true, 12>>(h, dim3(cdiv(MT, 4)), dim3(512), f);
+        if (d256) return step_launch<&k_ffn<P, 4, 16, 2, 8, 2, true, true, 32>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
+        return step_launch<&k_ffn<P, 2, 2, 2, 4, 2, false, true>>(h, dim3(cdiv(MT, 2)), dim3(256), f);
+    }
+}
+// ROWS at the DSG+ widths (round 6): QKV slices + attention per (clip, head) -- k_clip_attn_w (dsg_stream.h) -- and k_ffn<OP>
+template <class P>
+static int layer_clip_w_ffn(dsg_handle* h, const LayerCtx& y) {
+    const int B = y.z.B, MT = y.MT;
+    const ClipAttnArgs a = clip_attn_args(h, y);
+    // one pass over the rows at both widths -- 384: three column tiles on waves 0 - 1 (144 weight registers fit: 236 VGPRs; the two-pass form: 1 x 16 clips
+    // 371.3 vs 360.0 us per step, 4 x 16: 614 vs 604 -- profiles/r06_dq_*); 512: 192 weight registers, so the bias waits in the LDS and the A fragments have no
+    // look-ahead (254 VGPRs).  The two-pass form (Q / K, then V in pairs on waves 0 - 3) read the rows from the LDS 1.5 times and reloaded weights in between:
+    // TWH 1 x 16 clips 475.1 vs 472.9 us per step, 4 x 8: 601 vs 585, 4 x 16: 836.7 vs 830.1, bit-identical -- profiles/r06_dw_*; since retired
+    if (h->D == 384) CHK((step_launch<&k_clip_attn_w<6, 10, 4>>(h, dim3(4, B), dim3(512), a)));
+    else CHK((step_launch<&k_clip_attn_w<8, 10, 2>>(h, dim3(4, B), dim3(512), a)));
+    const FfnArgs f = ffn_args(h, y, true);
+    // latent_dim 384: W_o (36 fragments per wave) waits in registers as at the ZEGGS widths; 512: 64 fragments do not fit -- W_o leads the weight ring.
+    // Round 6: with >= 3 lanes whose row tiles together need more than one round of the 256 CUs, 32-row blocks -- W_o | W1 | W2 (1.8 / 2.5 MB) streamed once
+    // per 32 rows; W_o leads the ring at both widths (20 / 12 slots: 250 VGPRs), at 512 the fp32 LayerNorm1 rows wait in X1 instead of the LDS.
+    // Bit-identical to the 16-row form.  BEAT 4 x 16 clips 946 -> 825 us per step, 4 x 8: 542 -> 516; 1 x 16: 375 -> 412, 4 x 4: 375 -> 398, 2 x 16 even
+    // (profiles/r06_dj_*)
+    if (y.ks.ffn_rows == 32) {
+        if (h->D == 384) return step_launch<&k_ffn<P, 6, 16, 2, 8, 2, true, true, 20, true>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
+        return step_launch<&k_ffn<P, 8, 16, 2, 8, 2, true, true, 12, true>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
+    }
+    if (h->D == 384) return step_launch<&k_ffn<P, 6, 16, 1, 8, 2, true, true, 24>>(h, dim3(MT), dim3(512), f);      // (W_o leading the ring here too: 353.1 -> 357.8 us per step at 16 clips, r06_ea)
+    return step_launch<&k_ffn<P, 8, 16, 1, 8, 2, true, true, 24, true>>(h, dim3(MT), dim3(512), f);
+}
+// the forms that exist for precision P (select_kernels picks no other): fp32 has no k_clip_attn / k_ffn, bf16w2 no k_attn_op
+template <class P>
+static int run_layer(dsg_handle* h, Form f, const LayerCtx& y) {
+    constexpr bool bf16 = std::is_same<P, PBF16>::value;
+    switch (f) {
+        case Form::MID: return layer_mid<P>(h, y);
+        case Form::UNFUSED: return layer_unfused<P>(h, y);
+        case Form::ATTN_OP: if constexpr (!P::W2) return layer_attn_op<P>(h, y); break;
+        case Form::ATTN_OP_SPLIT: if constexpr (!P::W2) return layer_attn_op_split<P>(h, y); break;
+        case Form::CLIP_SPLIT: if constexpr (bf16) return layer_clip_split<P>(h, y); break;
+        case Form::ATTN_OP_FFN: if constexpr (bf16) return layer_attn_op_ffn<P>(h, y); break;
+        case Form::CLIP_FFN: if constexpr (bf16 || P::W2) return layer_clip_ffn<P>(h, y); break;
+        case Form::CLIP_W_FFN: if constexpr (bf16) return layer_clip_w_ffn<P>(h, y); break;
+    }
+    return fail(DSG_E_NOT_IMPLEMENTED, "layer form without an instantiation for this precision");
+}
+
 template <class P>
 static int run_step(dsg_handle* h, const StepCtx& c) {
     const int B = c.B, D = h->D, T = h->T, ntok = h->ntok;
@@ -1492,25 +1770,11 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
     const int MTin = cdiv(Min, 16), MT = cdiv(M, 16);
     const int KB = P::KB;
     const KernelSel& ks = c.ks;
-    GemmArgs z;
-    memset(&z, 0, sizeof(z));
-    z.KS = 1; z.kb_per_split = 0; z.B = B; z.ntok = ntok; z.Tp = h->Tp; z.H = h->H; z.hd = h->hd; z.T = T; z.J = h->J; z.Jp = h->Jp;
-    z.Jq = h->Jq; z.D = D; z.inv_ntok4 = fastdiv_inv(rup(ntok, 4));
-
-    LocArgs la;
-    memset(&la, 0, sizeof(la));
-    // split-K of the pose-embedding GEMM across workgroups: one split per 256 pose features for the 16 x 16 tile kernel; the
-    // block kernel splits K over its 4 waves already, so 2 workgroup splits keep a wave's share at <= 8 k-blocks (one batch of
-    // loads) without fragmenting the work 5 ways
-    const int ks_in = ks.xs_frag ? (h->Jp > 1152 ? 2 : 1) : ((ks.blk && !P::W2) ? std::min(h->KSin, 2) : h->KSin);      // (streamed embedding: K stays whole, see k_ws2; bf16w2: the 16 x 16 tiles)
-    la.partial = h->partial; la.KS = ks_in; la.Min_pad = MTin * 16; la.Cf = h->Cf; la.TE2 = h->TE2; la.TE = h->TE;
-    la.emb1 = h->emb1; la.ctl = c.use_ctr ? h->ctl : nullptr; la.t_arr = h->t_arr;
-    la.rcos = h->rcos; la.rsin = h->rsin; la.mask = h->mask; la.mb = h->mb; la.inv_mask_div = fastdiv_inv((int)((long long)B * h->Hl / h->mb)); la.B = B; la.T = T; la.D = D; la.Hl = h->Hl;
-    la.hd = h->hdl; la.W = h->W; la.X0 = h->X0; la.X0a = h->X0a; la.nomask = h->nomask;
-    la.x0a_frag = ((ks.stream || ks.clip_attn || ks.ffn16_wide) && sizeof(typename P::elem) == 2) ? (P::W2 ? 2 : 1) : 0;      // (bf16w2: as a hi + lo pair)
+    const GemmArgs z = gemm_base(h, B);
+    const LocArgs la = loc_args(h, B, ks.ks_in, c.use_ctr ? h->ctl : nullptr, ks.x0a_frag);
     h->fence_next = 1;         // the first packet of a step reads the state the previous step's last packet wrote (state_fences)
-    if (ks.lat) {              // pose embedding + local attention in one launch (in the batched sets it loses: 1 x 16 clips 192.1 -> 198.5 us per
-                               // step, 1 x 64: 258 -> 291, 4 x 4 even -- profiles/r06_ab_*, round 6)
+    if (ks.set == DSG_KSET_LATENCY) {      // pose embedding + local attention in one launch (in the batched sets it loses: 1 x 16 clips 192.1 -> 198.5 us
+                                           // per step, 1 x 64: 258 -> 291, 4 x 4 even -- profiles/r06_ab_*, round 6)
         InLocArgs a;
         a.xs = is_bf16(h) ? h->xsA : (void*)h->xs32; a.Jp = h->Jp; a.Wp = h->Wp_in; a.KBtot = h->Jp / KB;
         a.loc = la; a.ctl_upd = c.use_ctr ? h->ctl : nullptr; a.st = step_tables(h); a.n_tab = h->n_run;
@@ -1518,7 +1782,7 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
     } else {
         {   // k_in: partial[s] = xs[:, chunk s] . Wfold[:, chunk s]^T
             GemmArgs g = z;
-            g.M = Min; g.MT = MTin; g.NT = D / 16; g.KBtot = h->Jp / KB; g.KS = ks_in; g.Wp = h->Wp_in;
+            g.M = Min; g.MT = MTin; g.NT = D / 16; g.KBtot = h->Jp / KB; g.KS = ks.ks_in; g.Wp = h->Wp_in;
             g.kb_per_split = cdiv(g.KBtot, g.KS);
             g.A = is_bf16(h) ? h->xsA : (void*)h->xs32; g.lda = h->Jp;
             g.out = h->partial; g.ldo = D;
@@ -1528,7 +1792,7 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
                 if (ks.xs_frag) { g.a_frag = 1; CHK(launch_ws2<EPI_PARTIAL>(h, g)); done = true; }      // the state shadow is fragment-major
             }
             if constexpr (!P::W2) {
-                if (!done && ks.blk) { CHK((launch_blk_k<P, EPI_PARTIAL>(h, g))); done = true; }
+                if (!done && ks.blk()) { CHK((launch_blk_k<P, EPI_PARTIAL>(h, g))); done = true; }
             }
             if (!done) CHK((launch_gemm<P, PRO_DIRECT, EPI_PARTIAL, 4, 1>(h, g)));
         }
@@ -1540,224 +1804,12 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
         if (h->Hl * (T / h->W) * B >= h->env_loc64_from) DSG_LOC1_DISPATCH(la, dim3(h->Hl, T / h->W, B));
         else DSG_LOC_DISPATCH(k_loc, la, dim3(h->Hl, T / h->W, B));
     }
+    int in_frag = ks.x0a_frag;
     for (int l = 0; l < h->L; ++l) {
-        const Layer& ly = h->layers[l];
-        // (guidance: the last layer leaves pre2 to the two-pass pose head, i.e. it runs the round-3 feed-forward kernels, which read k_attn_op's rows)
-        const bool clip_l = ks.clip_attn && (l < h->L - 1 || h->cfgB == 0);
-        bool clip_w_done = false;
-        if constexpr (sizeof(typename P::elem) == 2 && !P::W2) {
-            if (ks.clip_w) {      // ROWS at the DSG+ widths (round 6): QKV slices + attention per (clip, head) -- k_clip_attn_w (dsg_stream.h); X0a holds the embedding output /
-                                  // LayerNorm2 of the previous layer, fragment-major
-                ClipAttnArgs a;
-                a.X = h->X0a; a.Wqkv = ly.Wqkv; a.bqkv = ly.bqkv; a.out = h->attn; a.B = B; a.ntok = ntok;
-                // latent_dim 384: ONE pass over the rows, three column tiles on waves 0 - 1 (144 weight registers fit: 236 VGPRs)
-                // (384 in the two-pass form: 1 x 16 clips 371.3 vs 360.0 us per step, 4 x 16: 614 vs 604 -- profiles/r06_dq_*)
-                if (D == 384) CHK((step_launch<&k_clip_attn_w<6, 10, 4, true>>(h, dim3(4, B), dim3(512), a)));
-                // 512: one pass as well -- 192 weight registers, so the bias waits in the LDS and the A fragments have no look-ahead (254 VGPRs); the two-pass form
-                // (Q / K, then V in pairs on waves 0 - 3) reads the rows from the LDS 1.5 times and reloads weights in between: TWH 1 x 16 clips 475.1 vs 472.9 us per
-                // step, 4 x 8: 601 vs 585, 4 x 16: 836.7 vs 830.1, bit-identical -- profiles/r06_dw_*
-#ifdef DSG_X_TWH_TWOPASS
-                else CHK((step_launch<&k_clip_attn_w<8, 10, 2, false>>(h, dim3(4, B), dim3(512), a)));
-#else
-                else CHK((step_launch<&k_clip_attn_w<8, 10, 2, true>>(h, dim3(4, B), dim3(512), a)));
-#endif
-                clip_w_done = true;
-            }
-        }
-        if (!clip_l && !clip_w_done) {   // QKV projection (LayerNorm2 of the previous layer applied on read)
-            GemmArgs g = z;
-            g.M = M; g.MT = MT; g.NT = 3 * D / 16; g.KBtot = D / KB; g.Wp = ly.Wqkv; g.bias = ly.bqkv;
-            g.q = h->q; g.k = h->k; g.vt = h->vt;
-            if (l == 0) {
-                g.A = h->X0a; g.lda = D; g.a_frag = la.x0a_frag;
-                CHK((launch_gemm_w<P, PRO_DIRECT, EPI_QKV>(h, g, ks)));
-            } else if (ks.ffn || ks.ffn_split) {      // k_ffn / k_ffn_ln left LayerNorm2(previous layer) in X0a, fragment-major
-                g.A = h->X0a; g.lda = D; g.a_frag = 1;
-                CHK((launch_gemm_w<P, PRO_DIRECT, EPI_QKV>(h, g, ks)));
-            } else {
-                g.X = h->pre2; g.ln_g = h->layers[l - 1].g2; g.ln_b = h->layers[l - 1].be2; g.Xn = h->Xn;
-                CHK((launch_gemm_w<P, PRO_LN, EPI_QKV>(h, g, ks)));
-            }
-        }
-        if (!ks.attn_in_mid && !ks.attn_op && !clip_w_done) {   // attention
-            AttnArgs a;
-            memset(&a, 0, sizeof(a));
-            a.q = h->q; a.k = h->k; a.vt = h->vt; a.out = h->attn; a.B = B; a.H = h->H; a.ntok = ntok; a.Tp = h->Tp;
-            a.D = D;
-            CHK(launch_attn<P>(h, a));
-        }
-        if (ks.lat) {      // [attention +] out_proj + residual + LayerNorm1 + linear1 slice + GELU
-            MidArgs a;
-            memset(&a, 0, sizeof(a));
-            a.A = h->attn; a.R = l == 0 ? h->X0 : h->Xn; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1;
-            a.W1 = ly.W1; a.b1 = ly.b1; a.X1 = h->X1; a.hidden = h->hidden; a.M = M; a.MT = MT; a.ff = h->ff;
-            if (ks.attn_in_mid) {
-                AttnMidArgs am;
-                am.mid = a; am.q = h->q; am.k = h->k; am.vt = h->vt; am.ntok = ntok; am.Tp = h->Tp;
-                CHK(launch_attn_mid<P>(h, am));
-            } else {
-                CHK(launch_mid<P>(h, a));
-            }
-        } else if (ks.attn_op) {
-          if constexpr (P::W2) {         // bf16w2 in the ROWS set (round 6): k_clip_attn + k_ffn on one 16-row tile, two-register fragments
-            if (!clip_l || !ks.ffn16) return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2: k_clip_attn + k_ffn in the ROWS set only");
-            ClipAttnArgs a;
-            a.X = h->X0a; a.Wqkv = ly.Wqkv; a.bqkv = ly.bqkv; a.out = h->attn; a.B = B; a.ntok = ntok;
-            if (D == 256) CHK((step_launch<&k_clip_attn<P, 4, 6>>(h, dim3(4, B), dim3(384), a)));
-            else CHK((step_launch<&k_clip_attn<P, 2, 2>>(h, dim3(4, B), dim3(128), a)));
-            FfnArgs f;
-            memset(&f, 0, sizeof(f));
-            f.W1 = ly.W1; f.b1 = ly.b1; f.W2 = ly.W2; f.b2 = ly.b2; f.ln_g = ly.g2; f.ln_b = ly.be2; f.Xn = h->Xn; f.Xa = h->X0a; f.M = M; f.MT = MT;
-            f.A = h->attn; f.R = l == 0 ? h->X0 : h->Xn; f.Wo = ly.Wo; f.bo = ly.bo; f.ln1_g = ly.g1; f.ln1_b = ly.be1; f.X1 = h->X1;
-            if (D == 256) CHK((step_launch<&k_ffn<P, 4, 16, 1, 8, 2, true, true, 12>>(h, dim3(MT), dim3(512), f)));
-            else CHK((step_launch<&k_ffn<P, 2, 2, 1, 4, 2, false, true, 8>>(h, dim3(MT), dim3(256), f)));
-            continue;
-          } else {                       // (bf16w2 runs LATENCY / TILE without k_attn_op: select_kernels)
-            // attention + out_proj + residual + LayerNorm1 in one kernel per (query tile, batch element); linear1 reads the
-            // normalised rows in the GEMM type
-            if (clip_l) {
-                // round 5: per (clip, head) -- QKV slices + attention in one kernel (k_clip_attn); out_proj + residual + LayerNorm1 are the
-                // prologue of k_ffn_part below (OP): Q / K / V never leave the CU and the QKV GEMM is gone as a dispatch
-                if constexpr (sizeof(typename P::elem) == 2) {
-                    ClipAttnArgs a;
-                    a.X = h->X0a; a.Wqkv = ly.Wqkv; a.bqkv = ly.bqkv; a.out = h->attn; a.B = B; a.ntok = ntok;
-                    if (D == 256) CHK((step_launch<&k_clip_attn<P, 4, 6>>(h, dim3(4, B), dim3(384), a)));
-                    else CHK((step_launch<&k_clip_attn<P, 2, 2>>(h, dim3(4, B), dim3(128), a)));
-                }
-            } else {
-                AttnOpArgs a;
-                a.q = h->q; a.k = h->k; a.vt = h->vt; a.R = l == 0 ? h->X0 : h->Xn; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1;
-                a.X1 = h->X1; a.X1a = h->X1a; a.B = B; a.ntok = ntok; a.Tp = h->Tp;
-                const dim3 grid(cdiv(ntok, 16), B);
-                if constexpr (sizeof(typename P::elem) == 2) {
-                    // (k_attn_op2 -- two query tiles per workgroup -- is retired: since round 5 this branch only serves the last layer under fused
-                    //  guidance and DSG_CLIP_ATTN=0; experiments/dsg_rejected_kernels.h)
-                    if (D == 256 && h->Tp == 96) CHK((step_launch<&k_attn_op<P, 4, 6>>(h, grid, dim3(256), a)));
-                    else if (D == 128 && h->Tp == 32) CHK((step_launch<&k_attn_op<P, 2, 2>>(h, grid, dim3(256), a)));
-                    else if (D == 384) CHK((step_launch<&k_attn_op_w<P, 6, 10>>(h, grid, dim3(256), a)));
-                    else CHK((step_launch<&k_attn_op_w<P, 8, 10>>(h, grid, dim3(256), a)));
-                } else {
-                    if (D == 256) CHK((step_launch<&k_attn_op_w<P, 4, 6>>(h, grid, dim3(256), a)));
-                    else CHK((step_launch<&k_attn_op_w<P, 2, 2>>(h, grid, dim3(256), a)));
-                }
-            }
-            // (guidance: the last layer leaves pre2 to the two-pass pose head k_gemm_cfg, which normalises on read)
-            if (ks.ffn && !(h->cfgB > 0 && l == h->L - 1)) {      // linear1 + GELU + linear2 + residual + LayerNorm2 (k_ffn): Xn fp32 + X0a in the GEMM type
-                FfnArgs a;
-                memset(&a, 0, sizeof(a));
-                a.A = h->X1a; a.R = h->X1; a.W1 = ly.W1; a.b1 = ly.b1; a.W2 = ly.W2; a.b2 = ly.b2; a.ln_g = ly.g2; a.ln_b = ly.be2;
-                a.Xn = h->Xn; a.Xa = h->X0a; a.M = M; a.MT = MT;
-                if (clip_l) {      // out_proj + residual + LayerNorm1 as the prologue (OP): A = the attention rows
-                    a.A = h->attn; a.R = l == 0 ? h->X0 : h->Xn; a.Wo = ly.Wo; a.bo = ly.bo; a.ln1_g = ly.g1; a.ln1_b = ly.be1; a.X1 = h->X1;
-                }
-                if constexpr (sizeof(typename P::elem) == 2) {
-                    const dim3 grid(cdiv(MT, 2));
-                    if (clip_l) {
-                        // (the weights of both phases on one rolling ring of fragments: 12 slots on 64-row blocks, 32 on 32-row blocks; the double-buffered
-                        //  groups of rounds 4-5 are retired)
-                        if (ks.ffn16) {         // ROWS: one 16-row tile per workgroup
-                            if (D == 256) CHK((step_launch<&k_ffn<P, 4, 16, 1, 8, 2, true, true, 32>>(h, dim3(MT), dim3(512), a)));
-                            else CHK((step_launch<&k_ffn<P, 2, 2, 1, 4, 2, false, true>>(h, dim3(MT), dim3(256), a)));
-                            continue;
-                        }
-                        if (D == 256 && ks.ffn_rt4) CHK((step_launch<&k_ffn<P, 4, 16, 4, 8, 1, true, true, 12>>(h, dim3(cdiv(MT, 4)), dim3(512), a)));
-                        else if (D == 256) CHK((step_launch<&k_ffn<P, 4, 16, 2, 8, 2, true, true, 32>>(h, grid, dim3(512), a)));
-                        else CHK((step_launch<&k_ffn<P, 2, 2, 2, 4, 2, false, true>>(h, grid, dim3(256), a)));
-                        continue;
-                    }
-                    // 64 rows per workgroup (bit-identical: same waves, same k order) when several lanes fill the GPU with large batches:
-                    // half the weight bytes through the CUs' load paths per row, half the workgroups (ffn_rt4 in select_kernels)
-                    if (D == 256 && ks.ffn_rt4) CHK((step_launch<&k_ffn<P, 4, 16, 4, 8, 1, true>>(h, dim3(cdiv(MT, 4)), dim3(512), a)));
-                    else if (D == 256) CHK((step_launch<&k_ffn<P, 4, 16, 2, 8, 2, true>>(h, grid, dim3(512), a)));
-                    else CHK((step_launch<&k_ffn<P, 2, 2, 2, 4>>(h, grid, dim3(256), a)));
-                }
-                continue;
-            }
-            // BLOCK below the STREAM threshold (round 4): k_ffn split 4 ways over the hidden dimension + the slab sum / LayerNorm2 pass; the
-            // next QKV projection and the pose head become direct GEMMs.  (Guidance: the last layer leaves pre2 to k_gemm_cfg, which
-            // normalises on read.)  profiles/r04_q_*: 1 x 16 230.9 -> 218.8 us, 4 x 4 222.4 -> 214.4, 4 x 8 288.9 -> 240.8.
-            if (ks.ffn_split && (l < h->L - 1 || h->cfgB == 0)) {
-                if constexpr (sizeof(typename P::elem) == 2) {
-                    FfnPartArgs a;
-                    memset(&a, 0, sizeof(a));
-                    a.A = h->X1a; a.W1 = ly.W1; a.b1 = ly.b1; a.W2 = ly.W2; a.part = h->ffn_part; a.slab = h->ffn_slab; a.M = M; a.MT = MT;
-                    if (clip_l) {      // out_proj + residual + LayerNorm1 as the prologue (OP)
-                        a.A = h->attn; a.R = l == 0 ? h->X0 : h->Xn; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1; a.X1 = h->X1;
-                    }
-                    FfnLnArgs b;
-                    b.part = h->ffn_part; b.slab = h->ffn_slab; b.R = h->X1; b.b2 = ly.b2; b.ln_g = ly.g2; b.ln_b = ly.be2; b.Xn = h->Xn; b.Xa = h->X0a; b.M = M;
-                    if (D == 256) {
-                        if (clip_l) CHK((step_launch<&k_ffn_part<P, 4, 16, 2, 4, 4, true>>(h, dim3(cdiv(MT, 2) * 4), dim3(256), a)));
-                        else CHK((step_launch<&k_ffn_part<P, 4, 16, 2, 4, 4>>(h, dim3(cdiv(MT, 2) * 4), dim3(256), a)));
-                        CHK((step_launch<&k_ffn_ln<P, 4, 4, 8>>(h, dim3(cdiv(M, 8)), dim3(128), b)));
-                    } else if (D == 384) {      // DSG+ widths (round 5): 8 ff-splits, one row tile per workgroup-pair batch of fragments
-                        CHK((step_launch<&k_ffn_part<P, 6, 16, 2, 4, 8>>(h, dim3(cdiv(MT, 2) * 8), dim3(256), a)));
-                        CHK((step_launch<&k_ffn_ln<P, 6, 8, 8>>(h, dim3(cdiv(M, 8)), dim3(128), b)));
-                    } else if (D == 512) {
-                        CHK((step_launch<&k_ffn_part<P, 8, 16, 2, 4, 8>>(h, dim3(cdiv(MT, 2) * 8), dim3(256), a)));
-                        CHK((step_launch<&k_ffn_ln<P, 8, 8, 8>>(h, dim3(cdiv(M, 8)), dim3(128), b)));
-                    } else {
-                        if (clip_l) CHK((step_launch<&k_ffn_part<P, 2, 2, 2, 4, 2, true>>(h, dim3(cdiv(MT, 2) * 2), dim3(256), a)));
-                        else CHK((step_launch<&k_ffn_part<P, 2, 2, 2, 4, 2>>(h, dim3(cdiv(MT, 2) * 2), dim3(256), a)));
-                        CHK((step_launch<&k_ffn_ln<P, 2, 2, 8>>(h, dim3(cdiv(M, 8)), dim3(128), b)));
-                    }
-                } else {
-                    // fp32 at the ZEGGS widths (round 5, round-4 verdict item 7): the same split, 8 ways (16 k-blocks of 16 per K = 256 operand)
-                    FfnPartArgs a;
-                    memset(&a, 0, sizeof(a));
-                    a.A = h->X1a; a.W1 = ly.W1; a.b1 = ly.b1; a.W2 = ly.W2; a.part = h->ffn_part; a.slab = h->ffn_slab; a.M = M; a.MT = MT;
-                    FfnLnArgs b;
-                    b.part = h->ffn_part; b.slab = h->ffn_slab; b.R = h->X1; b.b2 = ly.b2; b.ln_g = ly.g2; b.ln_b = ly.be2; b.Xn = h->Xn; b.Xa = h->X0a; b.M = M;
-                    CHK((step_launch<&k_ffn_part<P, 4, 16, 2, 4, 8>>(h, dim3(cdiv(MT, 2) * 8), dim3(256), a)));
-                    CHK((step_launch<&k_ffn_ln<P, 4, 8, 8>>(h, dim3(cdiv(M, 8)), dim3(128), b)));
-                }
-                continue;
-            }
-            {   // linear1 + GELU -> hidden
-                GemmArgs g = z;
-                g.M = M; g.MT = MT; g.NT = h->ff / 16; g.KBtot = D / KB; g.Wp = ly.W1; g.bias = ly.b1;
-                g.A = h->X1a; g.lda = D; g.a_frag = 1; g.out = h->hidden; g.ldo = h->ff; g.out_frag = 1;
-                CHK((launch_gemm_w<P, PRO_DIRECT, EPI_GELU>(h, g, ks)));
-            }
-          }
-        } else if (ks.ffn16_wide) {
-            if constexpr (sizeof(typename P::elem) == 2 && !P::W2) {
-                FfnArgs a;
-                memset(&a, 0, sizeof(a));
-                a.W1 = ly.W1; a.b1 = ly.b1; a.W2 = ly.W2; a.b2 = ly.b2; a.ln_g = ly.g2; a.ln_b = ly.be2; a.Xn = h->Xn; a.Xa = h->X0a; a.M = M; a.MT = MT;
-                a.A = h->attn; a.R = l == 0 ? h->X0 : h->Xn; a.Wo = ly.Wo; a.bo = ly.bo; a.ln1_g = ly.g1; a.ln1_b = ly.be1; a.X1 = h->X1;
-                // latent_dim 384: W_o (36 fragments per wave) waits in registers as at the ZEGGS widths; 512: 64 fragments do not fit -- W_o leads the weight ring
-                // Round 6: with >= 3 lanes whose row tiles together need more than one round of the 256 CUs, 32-row blocks -- W_o | W1 | W2 (1.8 / 2.5 MB) streamed once
-                // per 32 rows; W_o leads the ring at both widths (20 / 12 slots: 250 VGPRs), at 512 the fp32 LayerNorm1 rows wait in X1 instead of the LDS.
-                // Bit-identical to the 16-row form.  BEAT 4 x 16 clips 946 -> 825 us per step, 4 x 8: 542 -> 516; 1 x 16: 375 -> 412, 4 x 4: 375 -> 398, 2 x 16 even
-                // (profiles/r06_dj_*)
-                if (ks.ffn_rt2w) {
-                    if (D == 384) CHK((step_launch<&k_ffn<P, 6, 16, 2, 8, 2, true, true, 20, true>>(h, dim3(cdiv(MT, 2)), dim3(512), a)));
-                    else CHK((step_launch<&k_ffn<P, 8, 16, 2, 8, 2, true, true, 12, true>>(h, dim3(cdiv(MT, 2)), dim3(512), a)));
-                } else if (D == 384) CHK((step_launch<&k_ffn<P, 6, 16, 1, 8, 2, true, true, 24>>(h, dim3(MT), dim3(512), a)));      // (W_o leading the ring here too: 353.1 -> 357.8 us per step at 16 clips, r06_ea)
-                else CHK((step_launch<&k_ffn<P, 8, 16, 1, 8, 2, true, true, 24, true>>(h, dim3(MT), dim3(512), a)));
-                continue;
-            }
-        } else {
-            {   // out_proj + residual -> pre1
-                GemmArgs g = z;
-                g.M = M; g.MT = MT; g.NT = D / 16; g.KBtot = D / KB; g.Wp = ly.Wo; g.bias = ly.bo;
-                g.A = h->attn; g.lda = D; g.a_frag = 1; g.out = h->pre1; g.ldo = D; g.R = l == 0 ? h->X0 : h->Xn;
-                CHK((launch_gemm_w<P, PRO_DIRECT, EPI_RESID>(h, g, ks)));
-            }
-            {   // LayerNorm1-on-read + linear1 + GELU -> hidden ; X1 = LN1(pre1)
-                GemmArgs g = z;
-                g.M = M; g.MT = MT; g.NT = h->ff / 16; g.KBtot = D / KB; g.Wp = ly.W1; g.bias = ly.b1;
-                g.X = h->pre1; g.ln_g = ly.g1; g.ln_b = ly.be1; g.Xn = h->X1; g.out = h->hidden; g.ldo = h->ff; g.out_frag = 1;
-                CHK((launch_gemm_w<P, PRO_LN, EPI_GELU>(h, g, ks)));
-            }
-        }
-        {   // linear2 + residual -> pre2   (K = ff split over the 4 waves of the workgroup)
-            GemmArgs g = z;
-            g.M = M; g.MT = MT; g.NT = D / 16; g.KBtot = h->ff / KB; g.Wp = ly.W2; g.bias = ly.b2;
-            g.A = h->hidden; g.lda = h->ff; g.a_frag = 1; g.out = h->pre2; g.ldo = D; g.R = h->X1;
-            CHK(launch_gemm_k4<P>(h, g, ks));
-        }
+        const Form f = layer_form(h, ks, l);
+        const LayerCtx y = {ks, z, h->layers[l], M, MT, l == 0 ? h->X0 : h->Xn, in_frag, l == 0 ? nullptr : &h->layers[l - 1]};
+        CHK(run_layer<P>(h, f, y));
+        in_frag = leaves_x0a(f) ? 1 : -1;
     }
     {   // final LayerNorm-on-read + pose head + sampler update
         GemmArgs g = z;
@@ -1781,7 +1833,7 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
             }
             if (!done && pick_ch(g.KBtot) == 12) { CHK((step_launch<&k_gemm_cfg<P, 12>>(h, grid, dim3(256), g))); done = true; }
             if (!done) CHK((step_launch<&k_gemm_cfg<P>>(h, grid, dim3(256), g)));
-        } else if (ks.ffn || ks.ffn_split) {      // the rows are normalised already (k_ffn / k_ffn_ln of the last layer; cfgB == 0 here)
+        } else if (leaves_x0a(ks.form)) {      // the last layer left its rows normalised in X0a (cfgB == 0 here: layer_form)
             g.X = nullptr; g.ln_g = nullptr; g.ln_b = nullptr; g.A = h->X0a; g.lda = D; g.a_frag = 1;
             CHK((launch_gemm_w<P, PRO_DIRECT, EPI_OUT>(h, g, ks)));
         } else {
@@ -1799,17 +1851,9 @@ template <class P>
 static int debug_launch(dsg_handle* h, int which, int i, int B) {
     const int D = h->D, T = h->T, ntok = h->ntok, M = B * ntok, MT = cdiv(M, 16), Min = B * T, MTin = cdiv(Min, 16);
     const int KB = P::KB;
-    GemmArgs z;
-    memset(&z, 0, sizeof(z));
-    z.KS = 1; z.B = B; z.ntok = ntok; z.Tp = h->Tp; z.H = h->H; z.hd = h->hd; z.T = T; z.J = h->J; z.Jp = h->Jp;
-    z.Jq = h->Jq; z.D = D; z.inv_ntok4 = fastdiv_inv(rup(ntok, 4));
+    const GemmArgs z = gemm_base(h, B);
     const Layer& ly = h->layers[(which == 1) ? 0 : i % h->L];
-    LocArgs la;
-    memset(&la, 0, sizeof(la));
-    la.partial = h->partial; la.KS = h->KSin; la.Min_pad = MTin * 16; la.Cf = h->Cf; la.TE2 = h->TE2; la.TE = h->TE;
-    la.emb1 = h->emb1; la.ctl = nullptr; la.t_arr = h->t_arr;
-    la.rcos = h->rcos; la.rsin = h->rsin; la.mask = h->mask; la.mb = h->mb; la.inv_mask_div = fastdiv_inv((int)((long long)B * h->Hl / h->mb)); la.B = B; la.T = T; la.D = D; la.Hl = h->Hl;
-    la.hd = h->hdl; la.W = h->W; la.X0 = h->X0; la.X0a = h->X0a; la.nomask = h->nomask;
+    const LocArgs la = loc_args(h, B, h->KSin, nullptr, 0);
     if (which == 20) return debug_launch<P>(h, (i & 1) ? 1 : 4, i, B);                 // alternate 2 kernels
     if (which == 21) { const int seq[4] = {1, 4, 7, 9}; return debug_launch<P>(h, seq[i & 3], i, B); }   // 4 kernels
     if (which == 22) { const int seq[6] = {12, 9, 5, 10, 4, 8}; return debug_launch<P>(h, seq[i % 6], i, B); } // the step's 6 kernels
@@ -1827,9 +1871,7 @@ static int debug_launch(dsg_handle* h, int which, int i, int B) {
             GemmArgs g = z; g.M = M; g.MT = MT; g.NT = D / 16; g.KBtot = h->ff / KB; g.Wp = ly.W2; g.bias = ly.b2;
             g.A = h->hidden; g.lda = h->ff; g.a_frag = 1; g.out = h->pre2; g.ldo = D; g.R = h->X1;
             return launch_gemm<P, PRO_DIRECT, EPI_RESID, 1, 4>(h, g); }
-        case 5: {
-            AttnArgs a; memset(&a, 0, sizeof(a)); a.q = h->q; a.k = h->k; a.vt = h->vt; a.out = h->attn; a.B = B; a.H = h->H; a.ntok = ntok;
-            a.Tp = h->Tp; a.D = D; return launch_attn<P>(h, a); }
+        case 5: return launch_attn<P>(h, B);
         case 6: DSG_LOC_DISPATCH(k_loc, la, dim3(h->Hl, T / h->W, B)); return 0;
         case 7: {
             GemmArgs g = z; g.M = Min; g.MT = MTin; g.NT = D / 16; g.KBtot = h->Jp / KB; g.KS = h->KSin; g.Wp = h->Wp_in;
@@ -1844,10 +1886,7 @@ static int debug_launch(dsg_handle* h, int which, int i, int B) {
             GemmArgs g = z; g.M = M; g.MT = MT; g.NT = 3 * D / 16; g.KBtot = D / KB; g.Wp = ly.Wqkv; g.bias = ly.bqkv;
             g.q = h->q; g.k = h->k; g.vt = h->vt; g.X = h->pre2; g.ln_g = ly.g2; g.ln_b = ly.be2; g.Xn = h->Xn;
             return launch_gemm<P, PRO_LN, EPI_QKV, 4, 1>(h, g); }
-        case 10: {
-            MidArgs a; memset(&a, 0, sizeof(a)); a.A = h->attn; a.R = h->Xn; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1;
-            a.W1 = ly.W1; a.b1 = ly.b1; a.X1 = h->X1; a.hidden = h->hidden; a.M = M; a.MT = MT; a.ff = h->ff;
-            return launch_mid<P>(h, a); }
+        case 10: return launch_mid<P>(h, mid_args(h, ly, h->Xn, M));
         case 12: {
             InLocArgs a; a.xs = is_bf16(h) ? h->xsA : (void*)h->xs32; a.Jp = h->Jp; a.Wp = h->Wp_in;
             a.KBtot = h->Jp / KB; a.loc = la; a.ctl_upd = nullptr; a.st = step_tables(h); a.n_tab = 1;

@@ -456,12 +456,12 @@ __global__ __launch_bounds__(256, 1) void k_ws2(const GemmArgs g) {
 // and k_attn disappear as dispatches, Q / K / V^T never reach memory.  What differs from the narrow kernel, because nothing fits as laid out there:
 //   * the clip's rows (10 row tiles x 12 / 16 KB) pass through the LDS in chunks of XR row tiles, double-buffered with global -> LDS loads (no registers):
 //     the next chunk is in flight while a chunk is projected;
-//   * 8 waves, column tile t of the head's [Q | K | V] order by wave t % 8, ONE pass over the rows (ONEP): at latent_dim 384 18 tiles = three on waves 0 - 1, two
+//   * 8 waves, column tile t of the head's [Q | K | V] order by wave t % 8, ONE pass over the rows: at latent_dim 384 18 tiles = three on waves 0 - 1, two
 //     on the others (144 weight registers: 236 VGPRs); at 512 24 tiles = three on every wave (192 weight registers: the bias waits in the LDS and the A fragments
 //     have no look-ahead -- 254 VGPRs).  Every wave reads ALL of the rows from the LDS once -- 8 x 120 / 160 KB at 128 B / clk is what bounds the pass.  The
-//     TWO-pass form (!ONEP; kept as the A/B reference, -DDSG_X_TWH_TWOPASS): two tiles per wave (128 registers), pass A the 16 Q / K tiles, pass B the 8 V tiles
-//     in pairs on waves 0 - 3 with the chunk's two row tiles side by side (four accumulation chains: one wave per SIMD) -- 1.5 x the LDS reads and a weight
-//     reload in between: 475.1 vs 472.9 us per TWH step at 16 clips, 4 x 8 clips 601 vs 585;
+//     two-pass form it replaced at 512 (two tiles per wave, 128 registers: pass A the 16 Q / K tiles, pass B the 8 V tiles in pairs on waves 0 - 3 with the
+//     chunk's two row tiles side by side) read the rows 1.5 x and reloaded weights in between: 475.1 vs 472.9 us per TWH step at 16 clips, 4 x 8 clips 601 vs
+//     585, bit-identical (profiles/r06_dw_*);
 //   * EVERY tile is computed as W . X^T (a lane holds 4 consecutive dims of one token) -- one operand order -- and a V tile is transposed when it moves
 //     into V^T (four 2-byte LDS stores per row tile instead of one 8-byte store); the V tiles wait in registers, rounded, until every wave is done with the
 //     rows: V^T takes their place;
@@ -495,30 +495,7 @@ __device__ __forceinline__ void clip_w_proj(const f32x4 (&wf)[CW][KD], const f32
         }
     }
 }
-// ... two column tiles against TWO row tiles side by side: four independent accumulation chains (pass B of the two-pass form: one wave per SIMD)
-template <int KD>
-__device__ __forceinline__ void clip_w_proj2(const f32x4 (&wf)[2][KD], const f32x4 (*xrow0)[64], const f32x4 (*xrow1)[64], int lane, f32x4 (&acc0)[2], f32x4 (&acc1)[2]) {
-    f32x4 a[2][2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { a[0][0][i] = xrow0[i][lane]; a[0][1][i] = xrow1[i][lane]; }
-#pragma unroll
-    for (int kg = 0; kg < KD / 2; ++kg) {
-        if (kg + 1 < KD / 2) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) { a[(kg + 1) & 1][0][i] = xrow0[2 * (kg + 1) + i][lane]; a[(kg + 1) & 1][1][i] = xrow1[2 * (kg + 1) + i][lane]; }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                acc0[j] = PBF16::mma(wf[j][2 * kg + i], a[kg & 1][0][i], acc0[j]);
-                acc1[j] = PBF16::mma(wf[j][2 * kg + i], a[kg & 1][1][i], acc1[j]);
-            }
-        DSG_LOADS_ISSUED();
-    }
-}
-
-template <int DT, int NKT, int XR, bool ONEP>      // D = 64 DT, H = 4, hd = 16 DT, Tp = 16 NKT; XR row tiles per LDS chunk; ONEP: one pass over the rows (three column tiles per wave fit)
+template <int DT, int NKT, int XR>      // D = 64 DT, H = 4, hd = 16 DT, Tp = 16 NKT; XR row tiles per LDS chunk
 __global__ __launch_bounds__(512, 1) void k_clip_attn_w(const ClipAttnArgs g) {
     DSG_TL_SCOPE();
     typedef PBF16 P;
@@ -526,11 +503,10 @@ __global__ __launch_bounds__(512, 1) void k_clip_attn_w(const ClipAttnArgs g) {
     constexpr int NW = 8;
     constexpr int D = DT * 64, HD = DT * 16;
     constexpr int KD = D / P::KB, KDH = HD / P::KB, ND = HD / 16, NVF = NKT / 2;
-    constexpr int CT = 3 * ND, NP = ND / 2;          // column tiles of the head; V tile pairs (pass B)
-    constexpr int CW = ONEP ? 3 : 2;
+    constexpr int CT = 3 * ND;                       // column tiles of the head
+    constexpr int CW = 3;
     constexpr int NCH = (NKT + XR - 1) / XR, CF = XR * KD, CFW = (CF + NW - 1) / NW;
-    static_assert(NKT % 2 == 0 && HD % P::KB == 0 && ND % 2 == 0 && 2 * ND <= 2 * NW && NP <= NW && CT <= 3 * NW && CT > 2 * NW, "shape");
-    static_assert(ONEP || XR == 2, "two passes: pass B takes the row tiles in pairs");
+    static_assert(NKT % 2 == 0 && HD % P::KB == 0 && ND % 2 == 0 && 2 * ND <= 2 * NW && CT <= 3 * NW && CT > 2 * NW, "shape");
     __shared__ __attribute__((aligned(16))) f32x4 xs[2][CF][64];
     __shared__ __attribute__((aligned(16))) f32x4 qs[NKT * KDH][64];
     __shared__ __attribute__((aligned(16))) f32x4 ks[NKT * KDH][64];
@@ -556,14 +532,14 @@ __global__ __launch_bounds__(512, 1) void k_clip_attn_w(const ClipAttnArgs g) {
     issue_x(0);
     const f32x4* wq = (const f32x4*)g.Wqkv + lane;
     f32x4 wf[CW][KD];
-    constexpr bool LB = ONEP && KD > 12;             // (one pass at latent_dim 512: 192 weight registers -- the bias waits in the LDS, no look-ahead for the A fragments)
+    constexpr bool LB = KD > 12;             // (one pass at latent_dim 512: 192 weight registers -- the bias waits in the LDS, no look-ahead for the A fragments)
     f32x4 pb[LB ? 1 : CW];
     __shared__ __attribute__((aligned(16))) float bs[LB ? CT * 16 : 4];
     if constexpr (LB) {
         const int c4 = threadIdx.x;                  // four bias values of the head's [Q | K | V] columns
         if (c4 < CT * 4) { const int which = (4 * c4) / HD, within = 4 * c4 - which * HD; *(f32x4*)&bs[4 * c4] = *(const f32x4*)(g.bqkv + which * D + h * HD + within); }
     }
-    bf16x4v vkeep[NKT][ONEP ? 1 : 2];                // the wave's V tile(s), 4 dims of one token per row tile
+    bf16x4v vkeep[NKT];                              // the wave's V tile, 4 dims of one token per row tile
     // the wave's column tiles in the head's [Q | K | V] order (ND tiles each): packed in_proj column tile, weights, bias
     auto load_tiles = [&](const int (&t)[CW]) {
 #pragma unroll
@@ -576,107 +552,49 @@ __global__ __launch_bounds__(512, 1) void k_clip_attn_w(const ClipAttnArgs g) {
         }
         DSG_LOADS_ISSUED();
     };
-    int dv[2] = {0, 0};                              // first dim of the parked V tile(s) inside the head
-    bool vb = false;                                 // this wave holds V tiles
-    if constexpr (ONEP) {
-        // ---- one pass: tiles wave, wave + 8, wave + 16 (18 tiles: waves 0 - 1 three, the others two; at most one of them a V tile)
-        int t[3];
+    // ---- tiles wave, wave + 8, wave + 16 (18 tiles: waves 0 - 1 three, the others two; at most one of them a V tile)
+    int t[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) t[j] = min(wave + NW * j, CT - 1);
-        const bool three = wave + 2 * NW < CT;
-        load_tiles(t);
-        DSG_TL_MARK(0);      // first chunk of rows + the wave's columns requested
-        const int jv = t[1] >= 2 * ND ? 1 : 2;       // slot of the V tile, if any
-        vb = t[1] >= 2 * ND || three;
-        dv[0] = (t[jv] - 2 * ND) * 16;
+    for (int j = 0; j < 3; ++j) t[j] = min(wave + NW * j, CT - 1);
+    const bool three = wave + 2 * NW < CT;
+    load_tiles(t);
+    DSG_TL_MARK(0);      // first chunk of rows + the wave's columns requested
+    const int jv = t[1] >= 2 * ND ? 1 : 2;           // slot of the V tile, if any
+    const bool vb = t[1] >= 2 * ND || three;         // this wave holds a V tile
+    const int dv = (t[jv] - 2 * ND) * 16;            // its first dim inside the head
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            glds_wait();
-            DSG_LDS_BARRIER();            // chunk c has landed for every wave; every wave is done with the other buffer
-            if (c + 1 < NCH) issue_x(c + 1);
+    for (int c = 0; c < NCH; ++c) {
+        glds_wait();
+        DSG_LDS_BARRIER();            // chunk c has landed for every wave; every wave is done with the other buffer
+        if (c + 1 < NCH) issue_x(c + 1);
 #pragma unroll
-            for (int rl = 0; rl < XR; ++rl) {
-                const int rt = c * XR + rl;
-                if (rt < NKT) {
-                    f32x4 acc[3] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-                    if (three) clip_w_proj<3, 3, KD, !LB>(wf, &xs[c & 1][rl * KD], lane, acc);
-                    else clip_w_proj<2, 3, KD, !LB>(wf, &xs[c & 1][rl * KD], lane, acc);
+        for (int rl = 0; rl < XR; ++rl) {
+            const int rt = c * XR + rl;
+            if (rt < NKT) {
+                f32x4 acc[3] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+                if (three) clip_w_proj<3, 3, KD, !LB>(wf, &xs[c & 1][rl * KD], lane, acc);
+                else clip_w_proj<2, 3, KD, !LB>(wf, &xs[c & 1][rl * KD], lane, acc);
 #pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        if (j < 2 || three) {
-                            const int which = t[j] / ND, d0 = (t[j] - which * ND) * 16;
-                            f32x4 pbj;
-                            if constexpr (LB) pbj = *(const f32x4*)&bs[t[j] * 16 + 4 * lg]; else pbj = pb[j];
-                            const f32x4 y = acc[j] + pbj;
-                            if (which < 2) P::store4((elem*)(which == 0 ? &qs[0][0] : &ks[0][0]) + qk_off<P>(rt * 16 + lr, d0 + 4 * lg, KDH), y);
-                            else vkeep[rt][0] = __builtin_convertvector(y, bf16x4v);      // (P::store4's rounding)
-                        }
+                for (int j = 0; j < 3; ++j) {
+                    if (j < 2 || three) {
+                        const int which = t[j] / ND, d0 = (t[j] - which * ND) * 16;
+                        f32x4 pbj;
+                        if constexpr (LB) pbj = *(const f32x4*)&bs[t[j] * 16 + 4 * lg]; else pbj = pb[j];
+                        const f32x4 y = acc[j] + pbj;
+                        if (which < 2) P::store4((elem*)(which == 0 ? &qs[0][0] : &ks[0][0]) + qk_off<P>(rt * 16 + lr, d0 + 4 * lg, KDH), y);
+                        else vkeep[rt] = __builtin_convertvector(y, bf16x4v);      // (P::store4's rounding)
                     }
-                }
-            }
-        }
-        DSG_TL_MARK(1);      // projection done
-    } else {
-        // ---- pass A: Q / K tiles wave, wave + 8
-        const int ta[2] = {wave, min(wave + NW, 2 * ND - 1)};
-        const int nja = wave + NW < 2 * ND ? 2 : 1;
-        load_tiles(ta);
-        DSG_TL_MARK(0);      // first chunk of rows + the Q / K columns requested
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            glds_wait();
-            DSG_LDS_BARRIER();            // chunk c has landed for every wave; every wave is done with the other buffer
-            issue_x(c + 1);               // (the last one: chunk 0 again, for pass B)
-#pragma unroll
-            for (int rl = 0; rl < XR; ++rl) {
-                const int rt = c * XR + rl;
-                if (rt < NKT) {
-                    f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-                    if (nja == 2) clip_w_proj<2, 2, KD>(wf, &xs[c & 1][rl * KD], lane, acc);
-                    else clip_w_proj<1, 2, KD>(wf, &xs[c & 1][rl * KD], lane, acc);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        if (j < nja) {
-                            const int which = ta[j] / ND, d0 = (ta[j] - which * ND) * 16;
-                            P::store4((elem*)(which == 0 ? &qs[0][0] : &ks[0][0]) + qk_off<P>(rt * 16 + lr, d0 + 4 * lg, KDH), acc[j] + pb[j]);
-                        }
-                    }
-                }
-            }
-        }
-        DSG_TL_MARK(1);      // pass A done: Q / K of the head in LDS
-        // ---- pass B: V tiles in pairs (waves 0 .. NP - 1), the chunk's two row tiles side by side (four accumulation chains: one wave per SIMD)
-        vb = wave < NP;
-        const int tb[2] = {2 * ND + min(wave, NP - 1), 2 * ND + min(wave, NP - 1) + NP};
-        dv[0] = (tb[0] - 2 * ND) * 16; dv[1] = (tb[1] - 2 * ND) * 16;
-        if (vb) load_tiles(tb);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int i = NCH + c;
-            glds_wait();
-            DSG_LDS_BARRIER();
-            if (c + 1 < NCH) issue_x(i + 1);
-            if (vb) {
-                f32x4 acc0[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}}, acc1[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-                static_assert(NKT % 2 == 0, "pairs");
-                clip_w_proj2<KD>(wf, &xs[i & 1][0], &xs[i & 1][KD], lane, acc0, acc1);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    vkeep[2 * c][j] = __builtin_convertvector(acc0[j] + pb[j], bf16x4v);      // (P::store4's rounding)
-                    vkeep[2 * c + 1][j] = __builtin_convertvector(acc1[j] + pb[j], bf16x4v);
                 }
             }
         }
     }
+    DSG_TL_MARK(1);      // projection done
     DSG_LDS_BARRIER();                                            // every wave is done with the rows: V^T moves in
     if (vb) {
 #pragma unroll
-        for (int j = 0; j < (ONEP ? 1 : 2); ++j) {
+        for (int rt = 0; rt < NKT; ++rt)
 #pragma unroll
-            for (int rt = 0; rt < NKT; ++rt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) *((__bf16*)&vs[0][0] + vt_off<P>(dv[j] + 4 * lg + r, rt * 16 + lr, NVF)) = vkeep[rt][j][r];
-        }
+            for (int r = 0; r < 4; ++r) *((__bf16*)&vs[0][0] + vt_off<P>(dv + 4 * lg + r, rt * 16 + lr, NVF)) = vkeep[rt][r];
     }
     DSG_LDS_BARRIER();
     DSG_TL_MARK(2);      // Q / K / V^T of the head in LDS
