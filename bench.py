@@ -6,6 +6,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py ... --dump-outputs DIR                    (also writes the poses of the last timed step as DIR/poses.npy:
                                                               same arguments, same inputs -- two builds compare output for output)
+    python bench.py ... --full                                (also measures everything beyond the headline figure: see below)
 
 A "step" is one pass of the hot path over one batch of synthetic input = sampling `--clips-per-gpu` 320-frame clips per GPU
 (4 windows x 1000 denoising steps each).  Default: 1 clip at batch 1 = BASELINE config[1].  `--clips-per-gpu 16` is the
@@ -19,10 +20,15 @@ per-GPU share of config[3] (8 GPUs x 16 = 128 clips); how the clips of a GPU are
 Clips are independent, so N GPUs run N x clips-per-gpu clips (weak scaling, no collective on the data path); the finished
 poses are gathered to rank 0 with one RCCL gather inside the timed region.  Inputs (synthetic WavLM features, synthetic
 weights) are resident in HBM when the clock starts.  De-normalisation + .bvh writing (C++, rank 0) is timed separately
-(`postprocess_ms_per_clip`, `value_end_to_end`).  Prints ONE JSON line on rank 0.
+(`postprocess_ms_per_clip`, `value_end_to_end`; `--full` only).  Prints ONE JSON line on rank 0.
 
-The default line (`python bench.py`, 1 GPU, config[1]) also carries time-bounded SUB-RECORDS for the other BASELINE configs
-(`--sub-records off` drops them; each has its own value / us_per_denoise_step / kernel_set / roofline, about 25 s in all):
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the line: the headline figure and what the timed
+steps themselves report (us_per_denoise_step, kernel_set, roofline).  `--full` adds everything else (about 60 s on the default line):
+the .bvh post-processing (`--no-postprocess` drops it), `cpu_baseline` (the numpy oracle on the host cores; `--no-cpu-baseline`
+drops it), the `config3` sub-record of a multi-GPU run of the default workload (`--config3 on|off` forces it either way), and on
+the default line (`python bench.py --full`, 1 GPU, config[1]) time-bounded SUB-RECORDS for the other BASELINE configs
+(`--sub-records on|off` forces them either way; each has its own value / us_per_denoise_step / kernel_set / roofline, about 25 s
+in all):
     config2   50-step DDIM, batch 16 in lock step                      (BASELINE config[2])
     config3   16 clips as 4 lanes x batch 4 = config[3]'s per-GPU share (with --gpus N: N x 16 clips gathered over RCCL)
     config4   DiffuseStyleGesture+ BEAT and TWH denoisers, batch 1, 2 of the 16 windows of an 1830-frame clip (config[4]);
@@ -66,11 +72,14 @@ def parse(argv=None):
     p.add_argument("--no-postprocess", action="store_true")
     p.add_argument("--cpu-baseline-steps", type=int, default=1000)
     p.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even for a single rank")
+    p.add_argument("--full", action="store_true",
+                   help="measure everything beyond the headline figure as well: the .bvh post-processing, the CPU baseline and "
+                        "(auto) the sub-records and the config3 pass")
     p.add_argument("--config3", default="auto", choices=["auto", "on", "off"],
                    help="second timed pass at config[3]'s per-GPU share (16 clips: 4 lanes x batch 4) reported as `config3` "
-                        "(auto: whenever --gpus > 1 runs the default 1-clip-per-GPU workload)")
+                        "(auto: with --full whenever --gpus > 1 runs the default 1-clip-per-GPU workload)")
     p.add_argument("--sub-records", default="auto", choices=["auto", "on", "off"],
-                   help="config2 / config3 / config4 / stream sub-records in the JSON line (auto: the default 1-GPU config[1] run)")
+                   help="config2 / config3 / config4 / stream sub-records in the JSON line (auto: with --full on the default 1-GPU config[1] run)")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write the poses of the last timed step (all clips, gathered to rank 0) as DIR/poses.npy "
                         "(float32; beyond 64 MB a fixed seeded sample of whole clips)")
@@ -110,6 +119,19 @@ def dump_outputs(d, poses):
         poses = poses[np.sort(keep)]
     os.makedirs(d, exist_ok=True)
     np.save(os.path.join(d, "poses.npy"), poses)
+
+
+def extras(a, world, emu, variant):
+    """What the run measures beyond its headline figure (module docstring): nothing in a plain run; with `--full` what the line carried
+    before the option existed.  `--sub-records on` / `--config3 on` force their records in any run; `off` and the `--no-*` switches drop
+    theirs from a full one.  `variant` = the model variant the run samples (3 = DiffuseStyleGesture)."""
+    headline = variant == 3 and a.sampler == "ddpm" and a.clips_per_gpu == 1 and a.config == "zeggs"
+    want_sub = a.sub_records == "on" or (a.sub_records == "auto" and a.full and headline and world == 1 and not emu)
+    want_c3 = a.config3 == "on" or (a.config3 == "auto" and headline and ((a.full and a.gpus > 1) or want_sub))
+    return {"config3": want_c3 and variant == 3 and a.sampler == "ddpm",
+            "sub_records": want_sub and world == 1,
+            "postprocess": a.full and not a.no_postprocess and variant == 3 and not emu,
+            "cpu_baseline": a.full and not a.no_cpu_baseline and world == 1 and a.config == "zeggs" and a.sampler == "ddpm" and not emu}
 
 
 def self_launch(a):
@@ -413,18 +435,16 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if emu else f"cuda:{local}")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    # ---- sub-records: the other BASELINE configurations, bounded (module docstring).  config3 is also what a multi-GPU run of the
-    #      default workload carries (N x 16 clips gathered over RCCL); the single-GPU-only records run on one rank only.
-    headline = cfg.variant == 3 and a.sampler == "ddpm" and NC == 1 and a.config == "zeggs"
-    want_sub = a.sub_records == "on" or (a.sub_records == "auto" and headline and world == 1 and not emu)
-    want_c3 = a.config3 == "on" or (a.config3 == "auto" and headline and (a.gpus > 1 or want_sub))
+    # ---- sub-records (--full): the other BASELINE configurations, bounded (module docstring).  config3 is also what a multi-GPU run of
+    #      the default workload carries (N x 16 clips gathered over RCCL); the single-GPU-only records run on one rank only.
+    want = extras(a, world, emu, cfg.variant)
     subs = {}
-    if want_c3 and cfg.variant == 3 and a.sampler == "ddpm":
+    if want["config3"]:
         # "one clip per stream" is realised as 4 HSA queues x batch 4: four compute queues overlap on this GPU, a fifth collapses the
         # rate (16 x 1: 726 frames/s vs 5817 for 4 x 4; DESIGN.md s7, profiles/r04_b_multiproc_lanes.log)
         subs["config3"] = sub_record("config[3] per-GPU share: 16 clips, one clip per stream realised as 4 queues x batch 4 (a 5th "
                                      "queue collapses the rate)", "zeggs", 16, 4, "ddpm", 1, gather=True)
-    if want_sub and world == 1:
+    if want["sub_records"]:
         subs["config2"] = sub_record("config[2]: 50-step DDIM, batch 16 in lock step", "zeggs", 16, 1, "ddim50", 3)
         subs["config4"] = {
             name: sub_record(f"config[4]: DiffuseStyleGesture+ {name.upper()} denoiser, batch 1, 2 of the 16 windows of an 1830-frame clip",
@@ -475,7 +495,7 @@ def main():
             "us_per_denoise_step": round(us, 2),
             "roofline": roof,
         }
-        if not a.no_postprocess and cfg.variant == 3 and not emu and gathered is not None:
+        if want["postprocess"] and gathered is not None:
             # de-normalisation + Savitzky-Golay + .bvh text for every clip of the last pass (C++, host threads), outside the
             # timed region as the metric defines it; value_end_to_end charges it to the job
             from diffusestylegesture_amd.bvh import pose2bvh_batch
@@ -492,7 +512,7 @@ def main():
             out["postprocess_ms_per_pass"] = round(1000.0 * post, 3)
             out["value_end_to_end"] = round(n_clips * frames_per_clip / (dt + post * a.steps), 2)
         out.update(subs)
-        if world == 1 and not a.no_cpu_baseline and a.config == "zeggs" and a.sampler == "ddpm" and not emu:
+        if want["cpu_baseline"]:
             out["cpu_baseline"] = cpu_baseline(a.cpu_baseline_steps)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -82,6 +82,29 @@ def test_bench_dump_outputs_is_the_last_timed_step(emu_lib, tmp_path):
     assert got.dtype == np.float32 and np.array_equal(got, want)
 
 
+def test_bench_plain_run_measures_only_the_headline():
+    """A plain run measures nothing beyond its headline figure; `--full` adds what the line carried before the option existed (the
+    config3 pass and the sub-records of the default workload, the .bvh post-processing, the CPU baseline), and the explicit switches
+    still force or drop their parts -- decided by bench.extras, checked here for runs on the GPU and under the emulator."""
+    import bench
+    want = lambda argv, world=1, emu=False, variant=3: bench.extras(bench.parse(argv), world, emu, variant)
+    none = {"config3": False, "sub_records": False, "postprocess": False, "cpu_baseline": False}
+    assert want(["--gpus", "1", "--steps", "20", "--warmup", "5"]) == none
+    assert want(["--gpus", "8", "--steps", "3"], world=8) == none
+    assert want(["--clips-per-gpu", "16"]) == none
+    assert want(["--full"]) == {k: True for k in none}
+    assert want(["--full", "--gpus", "8"], world=8) == dict(none, config3=True, postprocess=True)
+    assert want(["--full", "--clips-per-gpu", "16"]) == dict(none, postprocess=True, cpu_baseline=True)
+    assert want(["--full", "--sampler", "ddim50"]) == dict(none, postprocess=True)
+    assert want(["--full", "--config", "beat"], variant=4) == none
+    assert want(["--full", "--sub-records", "off", "--no-cpu-baseline", "--no-postprocess"]) == none
+    assert want(["--full", "--config3", "off"]) == dict(none, sub_records=True, postprocess=True, cpu_baseline=True)
+    assert want(["--config3", "on"]) == dict(none, config3=True)
+    assert want(["--sub-records", "on"]) == dict(none, config3=True, sub_records=True)
+    assert want(["--full"], emu=True) == none
+    assert want(["--full", "--gpus", "2"], world=2, emu=True) == dict(none, config3=True)
+
+
 def test_bench_dump_outputs_caps_size(tmp_path):
     """An output above 64 MB is dumped as a fixed seeded sample of whole clips, in clip order; a smaller one whole."""
     import numpy as np

@@ -6,8 +6,8 @@ O=gpurun_out; mkdir -p $O
 cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 python -c 'import __graft_entry__ as g; g.smoke()' > $O/${TAG}_smoke.log 2>&1; tail -3 $O/${TAG}_smoke.log
 timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider --durations=8 > $O/${TAG}_pytest_gpu.log 2>&1; tail -3 $O/${TAG}_pytest_gpu.log
-timeout 500 python bench.py > $O/${TAG}_bench.log 2>&1
-B="timeout 300 python bench.py --no-cpu-baseline"
+timeout 500 python bench.py --full > $O/${TAG}_bench.log 2>&1
+B="timeout 300 python bench.py --full --no-cpu-baseline"
 for c in beat twh; do
   $B --config $c --steps 1 > $O/${TAG}_bench_${c}.log 2>&1
   $B --config $c --clips-per-gpu 16 --steps 1 --warmup 1 > $O/${TAG}_bench_${c}_16clips_l4_b4.log 2>&1

@@ -10,8 +10,8 @@ if [ -n "$WITH_TESTS" ]; then
   tail -12 $O/${TAG}_pytest_gpu.log
 fi
 # bench lines: headline, config[3]'s share (4 lanes x 4) + lock step, config[2] (DDIM-50, batch 16), larger per-GPU shares, DSG+ dims
-timeout 400 python bench.py > $O/${TAG}_bench.log 2>&1
-B="timeout 300 python bench.py --no-cpu-baseline"
+timeout 400 python bench.py --full > $O/${TAG}_bench.log 2>&1
+B="timeout 300 python bench.py --full --no-cpu-baseline"
 $B --clips-per-gpu 16 --steps 2 --warmup 1 > $O/${TAG}_bench_16clips_l4_b4.log 2>&1
 $B --clips-per-gpu 16 --lanes 1 --steps 2 --warmup 1 > $O/${TAG}_bench_16clips_lockstep.log 2>&1
 $B --clips-per-gpu 16 --lanes 1 --sampler ddim50 --steps 5 --warmup 1 > $O/${TAG}_bench_ddim50_b16_lockstep.log 2>&1
