@@ -114,11 +114,25 @@ struct SharedWeights {
     ~SharedWeights() { for (void* p : allocs) (void)hipFree(p); }
 };
 
+// The encoder core of a handle: (latent_dim, heads, padded tokens), the shape the fused attention / feed-forward kernels are instantiated per.  Each tuple is
+// written HERE and nowhere else; OTHER = every remaining shape dsg_create accepts (the generic TILE / BLOCK / LATENCY kernels serve it).  Which fused forms
+// exist per (core, precision, ff_size, pose width): the predicates above auto_kernel_set; which instantiation: the launchers' switches, closed by no_inst
+enum class Core { OTHER, C128, C256, C384, C512 };
+static Core classify_core(int D, int H, int Tp) {
+    if (H != 4) return Core::OTHER;
+    if (D == 128 && Tp == 32) return Core::C128;      // tiny (test dims)
+    if (D == 256 && Tp == 96) return Core::C256;      // ZEGGS
+    if (D == 384 && Tp == 160) return Core::C384;     // BEAT (DSG+)
+    if (D == 512 && Tp == 160) return Core::C512;     // TWH (DSG+)
+    return Core::OTHER;
+}
+
 struct dsg_handle {
     dsg_config cfg;
     int prec = 0, es = 4, kbk = 16;      // element size / k-block of the precision policy
     int J, T, S, D, As, A, W, L, H, hd, ff, Hl, hdl, ntok, Tp, Jp, Jq, Bmax, Ta, n_te;
     int KSin = 4;                        // split-K of the pose-embedding GEMM: one split per 256 pose features
+    Core core = Core::OTHER;             // classify_core(D, H, Tp), set once at dsg_create
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
     std::vector<void*> allocs;                       // per-lane buffers (state, activations, conditioning)
@@ -201,6 +215,13 @@ struct dsg_handle {
 
 // bf16 activations (DSG_PREC_BF16, DSG_PREC_BF16W2): the compute-dtype shadows / fragment layouts of the bf16 kernels
 static inline bool is_bf16(const dsg_handle* h) { return h->prec != DSG_PREC_FP32; }
+static inline bool core_narrow(const dsg_handle* h) { return h->core == Core::C128 || h->core == Core::C256; }      // the ZEGGS / tiny widths
+static inline bool core_wide(const dsg_handle* h) { return h->core == Core::C384 || h->core == Core::C512; }        // the DSG+ widths
+// the closed end of every launcher that switches on the core: select_kernels / check_set let no such call through
+static int no_inst(const dsg_handle* h, const char* kernel) {
+    return fail(DSG_E_NOT_IMPLEMENTED, std::string(kernel) + ": no instantiation for (latent_dim, heads, padded tokens) = (" + std::to_string(h->D) + ", " +
+                                           std::to_string(h->H) + ", " + std::to_string(h->Tp) + ") in precision " + std::to_string(h->prec));
+}
 
 // Uncached device memory is never handed back to the HIP allocator while a handle may still be created (round 4).  Found with
 // tools/debug_rowdep*.py: after a handle with uncached loop buffers had been destroyed, a NEW handle whose buffers landed on the
@@ -482,6 +503,7 @@ extern "C" int dsg_create(const dsg_config* c, dsg_handle** out) {
     h->Hl = c->local_heads; h->hdl = hdl; h->ntok = ntok; h->Tp = Tp;
     h->Jp = rup(h->J, 128); h->Jq = rup(h->J, 4); h->Bmax = c->max_batch;
     h->KSin = cdiv(h->Jp, 256);
+    h->core = classify_core(h->D, h->H, h->Tp);
     h->Ta = c->variant == 3 ? h->T : h->T - h->S * (c->variant == 5 ? 2 : 1);
     h->n_te = c->train_steps > 0 ? c->train_steps : 1000;
     if (h->n_te > c->pe_max_len) { delete h; return fail(DSG_E_INVALID, "train_steps > pe_max_len"); }
@@ -950,7 +972,7 @@ extern "C" int dsg_set_window_cond_cfg(dsg_handle* h, const float* style, const 
 //   With several lanes sharing the GPU the redundant recompute of LATENCY costs from batch 2 (4 x 2: 3507 frames/s TILE vs
 //   3303 LATENCY): dsg_recommend_kernel_set(B, lanes) encodes the multi-lane column; the caller applies it to its lanes.
 //   k_attn_op (attention + out_proj + LayerNorm1 in one kernel) replaces k_attn + out_proj in TILE / BLOCK wherever an
-//   instantiation exists (bf16, 4 heads, ZEGGS / tiny dims): 1 x 16: 292 -> 254 us, 4 x 4: 4640 -> 5074 frames/s.  Within a set
+//   instantiation exists (bf16, Core::C256 / C128 = ZEGGS / tiny dims): 1 x 16: 292 -> 254 us, 4 x 4: 4640 -> 5074 frames/s.  Within a set
 //   nothing depends on the batch but the grid (and the register budget of the LayerNorm GEMMs from 512 rows, same arithmetic):
 //   a row's result is bit-identical whatever the batch it rides in.
 // ---------------------------------------------------------------------------------------------------------
@@ -961,11 +983,11 @@ enum class Form {
     MID,            // QKV, [k_attn], k_mid | k_attn_mid, linear2                       LATENCY
     UNFUSED,        // QKV, k_attn, out_proj, LayerNorm1 + linear1, linear2              TILE / BLOCK without k_attn_op
     ATTN_OP,        // QKV, k_attn_op[_w], linear1, linear2                             TILE / BLOCK with k_attn_op; the last layer under fused guidance
-    ATTN_OP_SPLIT,  // QKV, k_attn_op[_w], k_ffn_part, k_ffn_ln                         BLOCK: DSG+ widths, fp32 ZEGGS, DSG_CLIP_ATTN=0
-    CLIP_SPLIT,     // k_clip_attn, k_ffn_part<OP>, k_ffn_ln                            BLOCK, bf16 ZEGGS / tiny
+    ATTN_OP_SPLIT,  // QKV, k_attn_op[_w], k_ffn_part, k_ffn_ln                         BLOCK: C384 / C512 (bf16), C256 in fp32, DSG_CLIP_ATTN=0
+    CLIP_SPLIT,     // k_clip_attn, k_ffn_part<OP>, k_ffn_ln                            BLOCK, bf16 at C256 / C128
     ATTN_OP_FFN,    // QKV, k_attn_op, k_ffn                                            STREAM / ROWS under DSG_CLIP_ATTN=0
-    CLIP_FFN,       // k_clip_attn, k_ffn<OP>                                           STREAM, ROWS (bf16, bf16w2)
-    CLIP_W_FFN,     // k_clip_attn_w, k_ffn<OP>                                         ROWS at latent_dim 384 / 512
+    CLIP_FFN,       // k_clip_attn, k_ffn<OP>                                           STREAM, ROWS (bf16, bf16w2) at C256 / C128
+    CLIP_W_FFN,     // k_clip_attn_w, k_ffn<OP>                                         ROWS at C384 / C512
 };
 static bool leaves_x0a(Form f) { return f >= Form::ATTN_OP_SPLIT; }
 struct KernelSel {
@@ -981,17 +1003,17 @@ struct KernelSel {
     bool stream() const { return set == DSG_KSET_STREAM; }   // weight-stationary streaming GEMMs (dsg_stream.h)
 };
 static bool have_attn_mid(const dsg_handle* h, int B) {
-    return B == 1 && h->H == 4 && ((h->D == 256 && h->Tp == 96) || (h->D == 128 && h->Tp == 32));
+    return B == 1 && core_narrow(h);
 }
-// k_attn_op with all of W_o in registers: bf16 at the ZEGGS / tiny widths (the STREAM set and k_attn_op2 build on it)
+// The predicates below are the supported-shape matrix: (precision, Core) -- named in classify_core -- plus ff_size / the padded pose width where a form needs them.
+// k_attn_op with all of W_o in registers: bf16 at C256 / C128 (the STREAM set builds on it)
 static bool have_attn_op_narrow(const dsg_handle* h) {
-    return h->prec == DSG_PREC_BF16 && h->H == 4 && ((h->D == 256 && h->Tp == 96) || (h->D == 128 && h->Tp == 32));
+    return h->prec == DSG_PREC_BF16 && core_narrow(h);
 }
-// ... or k_attn_op_w (W_o streamed in chunks, round 4): the DSG+ widths in bf16, the ZEGGS / tiny widths in fp32
+// ... or k_attn_op_w (W_o streamed in chunks, round 4): C384 / C512 in bf16, C256 / C128 in fp32
 static bool have_attn_op_wide(const dsg_handle* h) {
-    if (h->H != 4 || h->prec == DSG_PREC_BF16W2) return false;
-    if (h->prec == DSG_PREC_BF16) return (h->D == 384 || h->D == 512) && h->Tp == 160;
-    return (h->D == 256 && h->Tp == 96) || (h->D == 128 && h->Tp == 32);
+    if (h->prec == DSG_PREC_BF16) return core_wide(h);
+    return h->prec == DSG_PREC_FP32 && core_narrow(h);
 }
 static bool have_attn_op(const dsg_handle* h) { return have_attn_op_narrow(h) || have_attn_op_wide(h); }
 static bool latency_set_ok(const dsg_handle* h) {
@@ -1003,29 +1025,30 @@ static bool latency_set_ok(const dsg_handle* h) {
     return h->D <= 256 && (dt == 1 || dt == 2 || dt == 4);
 }
 static bool stream_set_ok(const dsg_handle* h) {
-    // k_ws keeps 64 columns x K = D of W per wave in registers (D = 128 / 256), k_ws2 a quarter of K = ff (ff = 128 / 1024);
+    // k_ws keeps 64 columns x K = D of W per wave in registers (C128 / C256), k_ws2 a quarter of K = ff (ff = 128 / 1024);
     // linear1 reads the fragment-major LayerNorm1 rows k_attn_op writes
-    return have_attn_op_narrow(h) && (h->D == 256 || h->D == 128) && (h->ff == 1024 || h->ff == 128) && (h->Jp == 1152 || h->Jp == 128);
+    return have_attn_op_narrow(h) && (h->ff == 1024 || h->ff == 128) && (h->Jp == 1152 || h->Jp == 128);
 }
 // k_ffn_part + k_ffn_ln exist for the shapes the STREAM set exists for and (round 5) for the DSG+ widths in bf16 (latent_dim 384 / 512, ff 1024:
 // 8 ff-splits -- the two-batch weight fragments of these widths do not fit 4), behind k_attn_op_w
 static bool ffn_split_wide(const dsg_handle* h) {
-    if (h->prec == DSG_PREC_FP32) return have_attn_op_wide(h) && h->ff == 1024 && h->D == 256;      // (fp32, ZEGGS widths: K = 256 is 16 k-blocks of 16)
-    return h->prec == DSG_PREC_BF16 && have_attn_op_wide(h) && h->ff == 1024 && (h->D == 384 || h->D == 512);
+    if (h->prec == DSG_PREC_FP32) return h->core == Core::C256 && h->ff == 1024;      // (fp32, ZEGGS widths: K = 256 is 16 k-blocks of 16)
+    return h->prec == DSG_PREC_BF16 && core_wide(h) && h->ff == 1024;
 }
 static bool ffn_split_ok(const dsg_handle* h) { return stream_set_ok(h) || ffn_split_wide(h); }
 // ROWS at the DSG+ widths (round 6, bf16): k_clip_attn_w (dsg_stream.h: the clip's rows do not fit the LDS next to Q / K / V -- they pass through it in chunks; first
 // version: the direct QKV GEMM + k_attn) feeds k_ffn<OP> on one 16-row tile (out_proj + LayerNorm1 as its prologue): no k_attn_op_w, no ff-split, no slabs, no slab-sum
 // pass; streamed pose embedding (K over two workgroups) and pose head
 static bool rows_wide_ok(const dsg_handle* h) {
-    return h->prec == DSG_PREC_BF16 && h->H == 4 && h->Tp == 160 && h->ff == 1024 && (h->D == 384 || h->D == 512);
+    return h->prec == DSG_PREC_BF16 && core_wide(h) && h->ff == 1024;
 }
 // bf16w2 (round 6): the ROWS pair -- k_clip_attn + k_ffn on one 16-row tile -- exists with the two-register fragments at the ZEGGS / tiny widths
 // (not under fused guidance: its last layer runs the QKV GEMM + k_attn_op, which have no bf16w2 form)
 static bool rows_w2_ok(const dsg_handle* h) {
-    return h->prec == DSG_PREC_BF16W2 && h->H == 4 && ((h->D == 256 && h->Tp == 96 && h->ff == 1024) || (h->D == 128 && h->Tp == 32 && h->ff == 128));
+    return h->prec == DSG_PREC_BF16W2 && ((h->core == Core::C256 && h->ff == 1024) || (h->core == Core::C128 && h->ff == 128));
 }
 // the streamed pose embedding at the DSG+ pose widths (round 6: k_ws2<EPI_PARTIAL, 17 / 18, 2>, K over two workgroups) -- in the ROWS set
+// (a GEMM of K = Jp, N = latent_dim: it depends on those two widths alone, not on the attention core -- any head count / clip length)
 static bool xs_frag_wide(const dsg_handle* h, int set) {
     return (set == DSG_KSET_ROWS || set == DSG_KSET_BLOCK) && (h->Jp == 2176 || h->Jp == 2304) && (h->D == 384 || h->D == 512);
 }
@@ -1053,8 +1076,8 @@ static int auto_kernel_set(const dsg_handle* h, int B, int lanes) {
         //  (... and past one round of the CUs as well: BEAT 1 x 32 clips 702 vs 844 us BLOCK, 1 x 48: 822 vs 1179; TWH 1 x 32: 925 vs 1058 -- profiles/r06_dm_*)
         //  (with k_clip_attn_w -- 24 us at latent_dim 512 whatever the batch -- BLOCK keeps 9 .. 12 TWH clips: 1 x 9: 417 vs 452 us, 1 x 12: 457 vs 466, 1 x 14: 551 vs 472;
         //   BEAT 1 x 9: 356 vs 339 ROWS -- profiles/r06_dv_*)
-        if (rows_wide_ok(h) && h->cfgB == 0 && rows >= (h->D == 512 ? 1960 : 1300)) return DSG_KSET_ROWS;
-        if (ffn_split_wide(h) && h->prec == DSG_PREC_BF16 && (h->D == 384 || h->D == 512) && h->env_ffn_split != 0 && rows >= 600) return DSG_KSET_BLOCK;
+        if (rows_wide_ok(h) && h->cfgB == 0 && rows >= (h->core == Core::C512 ? 1960 : 1300)) return DSG_KSET_ROWS;
+        if (ffn_split_wide(h) && h->prec == DSG_PREC_BF16 && h->env_ffn_split != 0 && rows >= 600) return DSG_KSET_BLOCK;
         // (round 6, bf16 ZEGGS widths: BLOCK from 6 clips -- 1 x 6: 177.6 vs 190.1 TILE, 1 x 5: 176.4 vs 161.6, 1 x 4: 173.9 vs 157.4)
         return rows >= (s_ok ? 500 : 1000) ? DSG_KSET_BLOCK : DSG_KSET_TILE;
     }
@@ -1111,7 +1134,7 @@ static int select_kernels(const dsg_handle* h, int B, KernelSel& k) {
     const bool clip = have_attn_op_narrow(h) && h->env_clip_attn != 0;      // (A/B: DSG_CLIP_ATTN=0 = QKV GEMM + k_attn_op, round 4)
     // k_ffn on 64-row blocks: 4 lanes x >= 4000 token rows (4 x 64 clips: 981 -> 903 us per step of the 4 lanes; 1 x 64: 376 -> 432, 4 x 16: 334 -> 392,
     // 4 x 32 even -- profiles/r04_y2_sweep_ffn_rt4_*.log).  DSG_FFN_RT4=<rows> (test hook / A/B): from that many token rows at any lane count; 0: never
-    const bool rt4 = h->D == 256 && (e >= 0 ? (e > 0 && rows >= e) : (h->lanes_now >= 4 && rows >= 4000));
+    const bool rt4 = h->core == Core::C256 && (e >= 0 ? (e > 0 && rows >= e) : (h->lanes_now >= 4 && rows >= 4000));
     switch (set) {
         case DSG_KSET_LATENCY:
             k.form = Form::MID;
@@ -1333,9 +1356,11 @@ static int launch_ln_ws(dsg_handle* h, GemmArgs g) {
     GemmArgs l = g;
     l.out = h->X1a;
     const dim3 grid(cdiv(rup(g.M, 64), 16));
-    if (g.D == 256) CHK((step_launch<&k_ln_frag<4>>(h, grid, dim3(256), l)));
-    else if (g.D == 128) CHK((step_launch<&k_ln_frag<2>>(h, grid, dim3(256), l)));
-    else return fail(DSG_E_NOT_IMPLEMENTED, "k_ln_frag: latent_dim must be 128 or 256");
+    switch (h->core) {
+        case Core::C256: CHK((step_launch<&k_ln_frag<4>>(h, grid, dim3(256), l))); break;
+        case Core::C128: CHK((step_launch<&k_ln_frag<2>>(h, grid, dim3(256), l))); break;
+        default: return fail(DSG_E_NOT_IMPLEMENTED, "k_ln_frag: latent_dim must be 128 or 256");
+    }
     h->fence_next = fence;
     g.A = h->X1a; g.lda = g.D; g.a_frag = 1; g.X = nullptr; g.Xn = nullptr;
     return launch_ws<EPI>(h, g);
@@ -1434,44 +1459,37 @@ static int launch_attn(dsg_handle* h, int B) {
     }
 }
 
-// k_loc / k_inloc are instantiated per (local head dim, window)
-#define DSG_LOC_DISPATCH(KERNEL, ARGS, GRID)                                                                         \
-    do {                                                                                                             \
-        const int key_ = h->hdl * 100 + h->W;                                                                        \
-        if (key_ == 32 * 100 + 11) CHK((step_launch<&KERNEL<P, 32, 11>>(h, GRID, dim3(256), ARGS)));                 \
-        else if (key_ == 48 * 100 + 15) CHK((step_launch<&KERNEL<P, 48, 15>>(h, GRID, dim3(256), ARGS)));            \
-        else if (key_ == 64 * 100 + 15) CHK((step_launch<&KERNEL<P, 64, 15>>(h, GRID, dim3(256), ARGS)));            \
-        else if (key_ == 16 * 100 + 11) CHK((step_launch<&KERNEL<P, 16, 11>>(h, GRID, dim3(256), ARGS)));            \
-        else if (key_ == 8 * 100 + 15) CHK((step_launch<&KERNEL<P, 8, 15>>(h, GRID, dim3(256), ARGS)));              \
-        else return fail(DSG_E_NOT_IMPLEMENTED, "no local-attention instantiation for (head dim, window) = (" +      \
-                                                    std::to_string(h->hdl) + ", " + std::to_string(h->W) + ")");     \
-    } while (0)
-
-// k_loc with TWO waves per (head, window, clip) instead of four (round 6): see the call site
-#define DSG_LOC1_DISPATCH(ARGS, GRID)                                                                                \
-    do {                                                                                                             \
-        const int key_ = h->hdl * 100 + h->W;                                                                        \
-        if (key_ == 32 * 100 + 11) CHK((step_launch<&k_loc<P, 32, 11, 128>>(h, GRID, dim3(128), ARGS)));               \
-        else if (key_ == 48 * 100 + 15) CHK((step_launch<&k_loc<P, 48, 15, 128>>(h, GRID, dim3(128), ARGS)));          \
-        else if (key_ == 64 * 100 + 15) CHK((step_launch<&k_loc<P, 64, 15, 128>>(h, GRID, dim3(128), ARGS)));          \
-        else if (key_ == 16 * 100 + 11) CHK((step_launch<&k_loc<P, 16, 11, 128>>(h, GRID, dim3(128), ARGS)));          \
-        else if (key_ == 8 * 100 + 15) CHK((step_launch<&k_loc<P, 8, 15, 128>>(h, GRID, dim3(128), ARGS)));            \
-        else return fail(DSG_E_NOT_IMPLEMENTED, "no local-attention instantiation for (head dim, window) = (" +      \
-                                                    std::to_string(h->hdl) + ", " + std::to_string(h->W) + ")");     \
-    } while (0)
+// k_loc / k_inloc are instantiated per (local head dim, window).  INLOC: k_inloc (LATENCY), else k_loc with NT threads per (head, window, clip):
+// 256, or 128 = its two-wave form (round 6: see the call site)
+template <class P, bool INLOC, int NT, int HD, int W, class A>
+static int launch_loc_t(dsg_handle* h, dim3 grid, const A& a) {
+    if constexpr (INLOC) return step_launch<&k_inloc<P, HD, W>>(h, grid, dim3(NT), a);
+    else return step_launch<&k_loc<P, HD, W, NT>>(h, grid, dim3(NT), a);
+}
+template <class P, bool INLOC, int NT, class A>
+static int launch_loc(dsg_handle* h, dim3 grid, const A& a) {
+    switch (h->hdl * 100 + h->W) {
+        case 32 * 100 + 11: return launch_loc_t<P, INLOC, NT, 32, 11>(h, grid, a);
+        case 48 * 100 + 15: return launch_loc_t<P, INLOC, NT, 48, 15>(h, grid, a);
+        case 64 * 100 + 15: return launch_loc_t<P, INLOC, NT, 64, 15>(h, grid, a);
+        case 16 * 100 + 11: return launch_loc_t<P, INLOC, NT, 16, 11>(h, grid, a);
+        case 8 * 100 + 15: return launch_loc_t<P, INLOC, NT, 8, 15>(h, grid, a);
+        default: return fail(DSG_E_NOT_IMPLEMENTED, "no local-attention instantiation for (head dim, window) = (" +
+                                                        std::to_string(h->hdl) + ", " + std::to_string(h->W) + ")");
+    }
+}
 
 template <class P>
 static int launch_mid(dsg_handle* h, const MidArgs& a) {
     const dim3 grid(xcd_grid_x(a.ff / 64), a.MT);
-    switch (h->D / 64) {
+    switch (h->D / 64) {      // (any head count: k_mid is instantiated per latent_dim, not per core)
         case 1: return step_launch<&k_mid<P, 1>>(h, grid, dim3(256), a);
         case 2: return step_launch<&k_mid<P, 2>>(h, grid, dim3(256), a);
         case 4: return step_launch<&k_mid<P, 4>>(h, grid, dim3(256), a);
+        // (bf16w2: two-register weight fragments, LATENCY up to latent_dim 256 -- check_set)
+        case 6: if constexpr (!P::W2) return step_launch<&k_mid<P, 6>>(h, grid, dim3(256), a); break;
+        case 8: if constexpr (!P::W2) return step_launch<&k_mid<P, 8>>(h, grid, dim3(256), a); break;
         default: break;
-    }
-    if constexpr (!P::W2) {      // (bf16w2: two-register weight fragments, LATENCY up to latent_dim 256 -- select_kernels)
-        if (h->D == 384) return step_launch<&k_mid<P, 6>>(h, grid, dim3(256), a);
-        if (h->D == 512) return step_launch<&k_mid<P, 8>>(h, grid, dim3(256), a);
     }
     return fail(DSG_E_NOT_IMPLEMENTED, "k_mid: latent_dim / 64 must be 1, 2, 4, 6 or 8 (bf16w2: 1, 2 or 4)");
 }
@@ -1483,9 +1501,11 @@ static int launch_mid(dsg_handle* h, const MidArgs& a) {
 template <class P>
 static int launch_attn_mid(dsg_handle* h, const AttnMidArgs& a) {
     const dim3 grid(xcd_grid_x(a.mid.ff / 64), a.mid.MT);
-    if (h->D == 256 && h->Tp == 96) return step_launch<&k_attn_mid<P, 4, 6>>(h, grid, dim3(256), a);
-    if (h->D == 128 && h->Tp == 32) return step_launch<&k_attn_mid<P, 2, 2>>(h, grid, dim3(256), a);
-    return fail(DSG_E_NOT_IMPLEMENTED, "no fused attention+mid instantiation");
+    switch (h->core) {
+        case Core::C256: return step_launch<&k_attn_mid<P, 4, 6>>(h, grid, dim3(256), a);
+        case Core::C128: return step_launch<&k_attn_mid<P, 2, 2>>(h, grid, dim3(256), a);
+        default: return fail(DSG_E_NOT_IMPLEMENTED, "no fused attention+mid instantiation");
+    }
 }
 
 static StepTables step_tables(const dsg_handle* h) {
@@ -1502,6 +1522,54 @@ static GemmArgs gemm_base(const dsg_handle* h, int B) {
     z.Jq = h->Jq; z.D = h->D; z.inv_ntok4 = fastdiv_inv(rup(h->ntok, 4));
     return z;
 }
+// One builder per GEMM of the step (the layer functions, run_step and debug_launch start from these).  M = the rows it runs on.
+static GemmArgs gemm_of(const dsg_handle* h, const GemmArgs& z, int M, int N, int K, const void* Wp, const float* bias) {
+    GemmArgs g = z;
+    g.M = M; g.MT = cdiv(M, 16); g.NT = N / 16; g.KBtot = K / h->kbk; g.Wp = Wp; g.bias = bias;
+    return g;
+}
+// k_in: partial[s] = xs[:, chunk s] . Wfold[:, chunk s]^T over KS workgroup splits of K (the step adds its control block: step_ctl)
+static GemmArgs gemm_pose_in(const dsg_handle* h, const GemmArgs& z, int Min, int KS) {
+    GemmArgs g = gemm_of(h, z, Min, h->D, h->Jp, h->Wp_in, nullptr);
+    g.KS = KS; g.kb_per_split = cdiv(g.KBtot, g.KS);
+    g.A = is_bf16(h) ? h->xsA : (void*)h->xs32; g.lda = h->Jp; g.out = h->partial; g.ldo = h->D;
+    return g;
+}
+// QKV -> q / k / v^T: on the rows in X0a (in_frag >= 0: their layout) or on pre2 with LayerNorm2 of layer `prev` applied on read (-> Xn)
+static GemmArgs gemm_qkv(const dsg_handle* h, const GemmArgs& z, int M, const Layer& ly, int in_frag, const Layer* prev) {
+    GemmArgs g = gemm_of(h, z, M, 3 * h->D, h->D, ly.Wqkv, ly.bqkv);
+    g.q = h->q; g.k = h->k; g.vt = h->vt;
+    if (in_frag >= 0) { g.A = h->X0a; g.lda = h->D; g.a_frag = in_frag; }
+    else { g.X = h->pre2; g.ln_g = prev->g2; g.ln_b = prev->be2; g.Xn = h->Xn; }
+    return g;
+}
+static GemmArgs gemm_out_proj(const dsg_handle* h, const GemmArgs& z, int M, const Layer& ly, const float* R) {      // + residual R -> pre1
+    GemmArgs g = gemm_of(h, z, M, h->D, h->D, ly.Wo, ly.bo);
+    g.A = h->attn; g.lda = h->D; g.a_frag = 1; g.out = h->pre1; g.ldo = h->D; g.R = R;
+    return g;
+}
+// linear1 + GELU -> hidden: with LayerNorm1 of pre1 on read (X1 = LN1(pre1)), or (frag) on k_attn_op's fragment-major LayerNorm1 rows
+static GemmArgs gemm_linear1(const dsg_handle* h, const GemmArgs& z, int M, const Layer& ly, bool frag) {
+    GemmArgs g = gemm_of(h, z, M, h->ff, h->D, ly.W1, ly.b1);
+    if (frag) { g.A = h->X1a; g.lda = h->D; g.a_frag = 1; }
+    else { g.X = h->pre1; g.ln_g = ly.g1; g.ln_b = ly.be1; g.Xn = h->X1; }
+    g.out = h->hidden; g.ldo = h->ff; g.out_frag = 1;
+    return g;
+}
+static GemmArgs gemm_linear2(const dsg_handle* h, const GemmArgs& z, int M, const Layer& ly) {      // + residual X1 -> pre2
+    GemmArgs g = gemm_of(h, z, M, h->D, h->ff, ly.W2, ly.b2);
+    g.A = h->hidden; g.lda = h->ff; g.a_frag = 1; g.out = h->pre2; g.ldo = h->D; g.R = h->X1;
+    return g;
+}
+// pose head on pre2 with LayerNorm2 of layer `last` on read + the sampler update (the step adds out_mode, noise and its control block)
+static GemmArgs gemm_pose_head(const dsg_handle* h, const GemmArgs& z, int M, const Layer& last) {
+    GemmArgs g = gemm_of(h, z, M, h->Jp, h->D, h->Wp_out, h->b_out);
+    g.X = h->pre2; g.ln_g = last.g2; g.ln_b = last.be2;
+    g.xs32 = h->xs32; g.xsA = is_bf16(h) ? h->xsA : nullptr; g.fwd_out = h->fwd_out; g.dyn = h->dyn;
+    return g;
+}
+// the step control of the two GEMMs that read / advance it (k_in, pose head)
+static void step_ctl(const dsg_handle* h, GemmArgs& g, StepCtl* ctl) { g.ctl = ctl; g.st = step_tables(h); g.n_tab = h->n_run; }
 // k_loc / k_inloc: the embedding's KS partial sums -> the local attention -> X0 (fp32) + X0a (in the layout x0a_frag)
 static LocArgs loc_args(const dsg_handle* h, int B, int KS, const StepCtl* ctl, int x0a_frag) {
     LocArgs la;
@@ -1511,6 +1579,12 @@ static LocArgs loc_args(const dsg_handle* h, int B, int KS, const StepCtl* ctl, 
     la.rcos = h->rcos; la.rsin = h->rsin; la.mask = h->mask; la.mb = h->mb; la.inv_mask_div = fastdiv_inv((int)((long long)B * h->Hl / h->mb)); la.B = B; la.T = h->T; la.D = h->D; la.Hl = h->Hl;
     la.hd = h->hdl; la.W = h->W; la.X0 = h->X0; la.X0a = h->X0a; la.nomask = h->nomask; la.x0a_frag = x0a_frag;
     return la;
+}
+static InLocArgs inloc_args(const dsg_handle* h, const LocArgs& la, StepCtl* ctl_upd, int n_tab) {
+    InLocArgs a;
+    a.xs = is_bf16(h) ? h->xsA : (void*)h->xs32; a.Jp = h->Jp; a.Wp = h->Wp_in; a.KBtot = h->Jp / h->kbk;
+    a.loc = la; a.ctl_upd = ctl_upd; a.st = step_tables(h); a.n_tab = n_tab;
+    return a;
 }
 static MidArgs mid_args(const dsg_handle* h, const Layer& ly, const float* R, int M) {
     MidArgs a;
@@ -1550,14 +1624,8 @@ static FfnArgs ffn_args(const dsg_handle* h, const LayerCtx& y, bool op) {
 // ---- the launches the layer forms share
 template <class P>
 static int qkv_gemm(dsg_handle* h, const LayerCtx& y) {
-    GemmArgs g = y.z;
-    g.M = y.M; g.MT = y.MT; g.NT = 3 * h->D / 16; g.KBtot = h->D / P::KB; g.Wp = y.ly.Wqkv; g.bias = y.ly.bqkv;
-    g.q = h->q; g.k = h->k; g.vt = h->vt;
-    if (y.in_frag >= 0) {
-        g.A = h->X0a; g.lda = h->D; g.a_frag = y.in_frag;
-        return launch_gemm_w<P, PRO_DIRECT, EPI_QKV>(h, g, y.ks);
-    }
-    g.X = h->pre2; g.ln_g = y.prev->g2; g.ln_b = y.prev->be2; g.Xn = h->Xn;
+    const GemmArgs g = gemm_qkv(h, y.z, y.M, y.ly, y.in_frag, y.prev);
+    if (y.in_frag >= 0) return launch_gemm_w<P, PRO_DIRECT, EPI_QKV>(h, g, y.ks);
     return launch_gemm_w<P, PRO_LN, EPI_QKV>(h, g, y.ks);
 }
 // attention + out_proj + residual + LayerNorm1 in one kernel per (query tile, batch element); the next kernel reads the normalised rows in the
@@ -1569,41 +1637,43 @@ static int attn_op(dsg_handle* h, const LayerCtx& y) {
     a.q = h->q; a.k = h->k; a.vt = h->vt; a.R = y.R; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1;
     a.X1 = h->X1; a.X1a = h->X1a; a.B = y.z.B; a.ntok = h->ntok; a.Tp = h->Tp;
     const dim3 grid(cdiv(h->ntok, 16), y.z.B);
-    const int D = h->D;
     if constexpr (sizeof(typename P::elem) == 2) {
-        if (D == 256 && h->Tp == 96) return step_launch<&k_attn_op<P, 4, 6>>(h, grid, dim3(256), a);
-        if (D == 128 && h->Tp == 32) return step_launch<&k_attn_op<P, 2, 2>>(h, grid, dim3(256), a);
-        if (D == 384) return step_launch<&k_attn_op_w<P, 6, 10>>(h, grid, dim3(256), a);
-        return step_launch<&k_attn_op_w<P, 8, 10>>(h, grid, dim3(256), a);
+        switch (h->core) {
+            case Core::C256: return step_launch<&k_attn_op<P, 4, 6>>(h, grid, dim3(256), a);
+            case Core::C128: return step_launch<&k_attn_op<P, 2, 2>>(h, grid, dim3(256), a);
+            case Core::C384: return step_launch<&k_attn_op_w<P, 6, 10>>(h, grid, dim3(256), a);
+            case Core::C512: return step_launch<&k_attn_op_w<P, 8, 10>>(h, grid, dim3(256), a);
+            default: break;
+        }
     } else {
-        if (D == 256) return step_launch<&k_attn_op_w<P, 4, 6>>(h, grid, dim3(256), a);
-        return step_launch<&k_attn_op_w<P, 2, 2>>(h, grid, dim3(256), a);
+        switch (h->core) {
+            case Core::C256: return step_launch<&k_attn_op_w<P, 4, 6>>(h, grid, dim3(256), a);
+            case Core::C128: return step_launch<&k_attn_op_w<P, 2, 2>>(h, grid, dim3(256), a);
+            default: break;
+        }
     }
+    return no_inst(h, "k_attn_op");
 }
 // round 5: per (clip, head) -- QKV slices + attention in one kernel (k_clip_attn); out_proj + residual + LayerNorm1 are the prologue of the
 // feed-forward kernel behind it (OP): Q / K / V never leave the CU and the QKV GEMM is gone as a dispatch
 template <class P>
 static int clip_attn(dsg_handle* h, const LayerCtx& y) {
     const ClipAttnArgs a = clip_attn_args(h, y);
-    if (h->D == 256) return step_launch<&k_clip_attn<P, 4, 6>>(h, dim3(4, y.z.B), dim3(384), a);
-    return step_launch<&k_clip_attn<P, 2, 2>>(h, dim3(4, y.z.B), dim3(128), a);
+    switch (h->core) {
+        case Core::C256: return step_launch<&k_clip_attn<P, 4, 6>>(h, dim3(4, y.z.B), dim3(384), a);
+        case Core::C128: return step_launch<&k_clip_attn<P, 2, 2>>(h, dim3(4, y.z.B), dim3(128), a);
+        default: return no_inst(h, "k_clip_attn");
+    }
 }
 template <class P>
-static int linear1_gelu(dsg_handle* h, const LayerCtx& y) {      // on k_attn_op's fragment-major LayerNorm1 rows -> hidden
-    GemmArgs g = y.z;
-    g.M = y.M; g.MT = y.MT; g.NT = h->ff / 16; g.KBtot = h->D / P::KB; g.Wp = y.ly.W1; g.bias = y.ly.b1;
-    g.A = h->X1a; g.lda = h->D; g.a_frag = 1; g.out = h->hidden; g.ldo = h->ff; g.out_frag = 1;
-    return launch_gemm_w<P, PRO_DIRECT, EPI_GELU>(h, g, y.ks);
-}
-template <class P>
-static int linear2(dsg_handle* h, const LayerCtx& y) {      // linear2 + residual -> pre2 (K = ff split over the 4 waves of the workgroup)
-    GemmArgs g = y.z;
-    g.M = y.M; g.MT = y.MT; g.NT = h->D / 16; g.KBtot = h->ff / P::KB; g.Wp = y.ly.W2; g.bias = y.ly.b2;
-    g.A = h->hidden; g.lda = h->ff; g.a_frag = 1; g.out = h->pre2; g.ldo = h->D; g.R = h->X1;
-    return launch_gemm_k4<P>(h, g, y.ks);
-}
+static int linear2(dsg_handle* h, const LayerCtx& y) { return launch_gemm_k4<P>(h, gemm_linear2(h, y.z, y.M, y.ly), y.ks); }      // (K = ff split over the 4 waves of the workgroup)
 // BLOCK below the STREAM threshold (round 4): k_ffn split over the hidden dimension (k_ffn_part) + the slab sum / LayerNorm2 pass (k_ffn_ln).
 // profiles/r04_q_*: 1 x 16 230.9 -> 218.8 us, 4 x 4 222.4 -> 214.4, 4 x 8 288.9 -> 240.8.  OP: out_proj + residual + LayerNorm1 as the prologue
+template <class P, int DT, int FT, int S, bool OP>      // latent_dim = 64 DT, ff = 64 FT, S ff-splits (= slabs)
+static int ffn_split_t(dsg_handle* h, const LayerCtx& y, const FfnPartArgs& a, const FfnLnArgs& b) {
+    CHK((step_launch<&k_ffn_part<P, DT, FT, 2, 4, S, OP>>(h, dim3(cdiv(y.MT, 2) * S), dim3(256), a)));
+    return step_launch<&k_ffn_ln<P, DT, S, 8>>(h, dim3(cdiv(y.M, 8)), dim3(128), b);
+}
 template <class P, bool OP>
 static int ffn_split(dsg_handle* h, const LayerCtx& y) {
     const Layer& ly = y.ly;
@@ -1613,29 +1683,20 @@ static int ffn_split(dsg_handle* h, const LayerCtx& y) {
     if (OP) { a.A = h->attn; a.R = y.R; a.Wo = ly.Wo; a.bo = ly.bo; a.ln_g = ly.g1; a.ln_b = ly.be1; a.X1 = h->X1; }
     FfnLnArgs b;
     b.part = h->ffn_part; b.slab = h->ffn_slab; b.R = h->X1; b.b2 = ly.b2; b.ln_g = ly.g2; b.ln_b = ly.be2; b.Xn = h->Xn; b.Xa = h->X0a; b.M = y.M;
-    const int G = cdiv(y.MT, 2);
-    const dim3 gl(cdiv(y.M, 8));
     if constexpr (sizeof(typename P::elem) == 4) {
         // fp32 at the ZEGGS widths (round 5, round-4 verdict item 7): the same split, 8 ways (16 k-blocks of 16 per K = 256 operand)
-        CHK((step_launch<&k_ffn_part<P, 4, 16, 2, 4, 8>>(h, dim3(G * 8), dim3(256), a)));
-        return step_launch<&k_ffn_ln<P, 4, 8, 8>>(h, gl, dim3(128), b);
+        if (h->core == Core::C256) return ffn_split_t<P, 4, 16, 8, false>(h, y, a, b);
     } else {
-        if (h->D == 256) {
-            CHK((step_launch<&k_ffn_part<P, 4, 16, 2, 4, 4, OP>>(h, dim3(G * 4), dim3(256), a)));
-            return step_launch<&k_ffn_ln<P, 4, 4, 8>>(h, gl, dim3(128), b);
+        switch (h->core) {
+            case Core::C256: return ffn_split_t<P, 4, 16, 4, OP>(h, y, a, b);
+            case Core::C128: return ffn_split_t<P, 2, 2, 2, OP>(h, y, a, b);
+            // DSG+ widths (round 5, k_attn_op_w only): 8 ff-splits, one row tile per workgroup-pair batch of fragments
+            case Core::C384: return ffn_split_t<P, 6, 16, 8, false>(h, y, a, b);
+            case Core::C512: return ffn_split_t<P, 8, 16, 8, false>(h, y, a, b);
+            default: break;
         }
-        if (h->D == 128) {
-            CHK((step_launch<&k_ffn_part<P, 2, 2, 2, 4, 2, OP>>(h, dim3(G * 2), dim3(256), a)));
-            return step_launch<&k_ffn_ln<P, 2, 2, 8>>(h, gl, dim3(128), b);
-        }
-        // DSG+ widths (round 5, k_attn_op_w only): 8 ff-splits, one row tile per workgroup-pair batch of fragments
-        if (h->D == 384) {
-            CHK((step_launch<&k_ffn_part<P, 6, 16, 2, 4, 8>>(h, dim3(G * 8), dim3(256), a)));
-            return step_launch<&k_ffn_ln<P, 6, 8, 8>>(h, gl, dim3(128), b);
-        }
-        CHK((step_launch<&k_ffn_part<P, 8, 16, 2, 4, 8>>(h, dim3(G * 8), dim3(256), a)));
-        return step_launch<&k_ffn_ln<P, 8, 8, 8>>(h, gl, dim3(128), b);
     }
+    return no_inst(h, "k_ffn_part");
 }
 
 // ---- one function per layer form (enum Form): the launches of one encoder layer, in order
@@ -1655,28 +1716,17 @@ static int layer_mid(dsg_handle* h, const LayerCtx& y) {
 }
 template <class P>
 static int layer_unfused(dsg_handle* h, const LayerCtx& y) {
-    const int D = h->D;
     CHK(qkv_gemm<P>(h, y));
     CHK(launch_attn<P>(h, y.z.B));
-    {   // out_proj + residual -> pre1
-        GemmArgs g = y.z;
-        g.M = y.M; g.MT = y.MT; g.NT = D / 16; g.KBtot = D / P::KB; g.Wp = y.ly.Wo; g.bias = y.ly.bo;
-        g.A = h->attn; g.lda = D; g.a_frag = 1; g.out = h->pre1; g.ldo = D; g.R = y.R;
-        CHK((launch_gemm_w<P, PRO_DIRECT, EPI_RESID>(h, g, y.ks)));
-    }
-    {   // LayerNorm1-on-read + linear1 + GELU -> hidden ; X1 = LN1(pre1)
-        GemmArgs g = y.z;
-        g.M = y.M; g.MT = y.MT; g.NT = h->ff / 16; g.KBtot = D / P::KB; g.Wp = y.ly.W1; g.bias = y.ly.b1;
-        g.X = h->pre1; g.ln_g = y.ly.g1; g.ln_b = y.ly.be1; g.Xn = h->X1; g.out = h->hidden; g.ldo = h->ff; g.out_frag = 1;
-        CHK((launch_gemm_w<P, PRO_LN, EPI_GELU>(h, g, y.ks)));
-    }
+    CHK((launch_gemm_w<P, PRO_DIRECT, EPI_RESID>(h, gemm_out_proj(h, y.z, y.M, y.ly, y.R), y.ks)));
+    CHK((launch_gemm_w<P, PRO_LN, EPI_GELU>(h, gemm_linear1(h, y.z, y.M, y.ly, false), y.ks)));
     return linear2<P>(h, y);
 }
 template <class P>
 static int layer_attn_op(dsg_handle* h, const LayerCtx& y) {
     CHK(qkv_gemm<P>(h, y));
     CHK(attn_op<P>(h, y));
-    CHK(linear1_gelu<P>(h, y));
+    CHK((launch_gemm_w<P, PRO_DIRECT, EPI_GELU>(h, gemm_linear1(h, y.z, y.M, y.ly, true), y.ks)));
     return linear2<P>(h, y);
 }
 template <class P>
@@ -1697,9 +1747,13 @@ static int layer_attn_op_ffn(dsg_handle* h, const LayerCtx& y) {
     CHK(qkv_gemm<P>(h, y));
     CHK(attn_op<P>(h, y));
     const FfnArgs f = ffn_args(h, y, false);
-    if (y.ks.ffn_rows == 64) return step_launch<&k_ffn<P, 4, 16, 4, 8, 1, true>>(h, dim3(cdiv(y.MT, 4)), dim3(512), f);
-    if (h->D == 256) return step_launch<&k_ffn<P, 4, 16, 2, 8, 2, true>>(h, dim3(cdiv(y.MT, 2)), dim3(512), f);
-    return step_launch<&k_ffn<P, 2, 2, 2, 4>>(h, dim3(cdiv(y.MT, 2)), dim3(256), f);
+    switch (h->core) {
+        case Core::C256:
+            if (y.ks.ffn_rows == 64) return step_launch<&k_ffn<P, 4, 16, 4, 8, 1, true>>(h, dim3(cdiv(y.MT, 4)), dim3(512), f);
+            return step_launch<&k_ffn<P, 4, 16, 2, 8, 2, true>>(h, dim3(cdiv(y.MT, 2)), dim3(512), f);
+        case Core::C128: return step_launch<&k_ffn<P, 2, 2, 2, 4>>(h, dim3(cdiv(y.MT, 2)), dim3(256), f);      // (32-row blocks only: select_kernels, rt4)
+        default: return no_inst(h, "k_ffn");
+    }
 }
 // (the weights of both phases on one rolling ring of fragments: 12 slots on 64-row blocks, 32 on 16- / 32-row blocks; the double-buffered groups of
 //  rounds 4-5 are retired)
@@ -1707,20 +1761,24 @@ template <class P>
 static int layer_clip_ffn(dsg_handle* h, const LayerCtx& y) {
     CHK(clip_attn<P>(h, y));
     const FfnArgs f = ffn_args(h, y, true);
-    const int MT = y.MT;
-    const bool d256 = h->D == 256;
-    if constexpr (P::W2) {      // bf16w2 in the ROWS set (round 6): one 16-row tile per workgroup, two-register fragments
-        if (d256) return step_launch<&k_ffn<P, 4, 16, 1, 8, 2, true, true, 12>>(h, dim3(MT), dim3(512), f);
-        return step_launch<&k_ffn<P, 2, 2, 1, 4, 2, false, true, 8>>(h, dim3(MT), dim3(256), f);
-    } else {
-        if (y.ks.ffn_rows == 16) {      // ROWS: one 16-row tile per workgroup
-            if (d256) return step_launch<&k_ffn<P, 4, 16, 1, 8, 2, true, true, 32>>(h, dim3(MT), dim3(512), f);
-            return step_launch<&k_ffn<P, 2, 2, 1, 4, 2, false, true>>(h, dim3(MT), dim3(256), f);
-        }
-        if (y.ks.ffn_rows == 64) return step_launch<&k_ffn<P, 4, 16, 4, 8, 1, true, true, 12>>(h, dim3(cdiv(MT, 4)), dim3(512), f);
-        if (d256) return step_launch<&k_ffn<P, 4, 16, 2, 8, 2, true, true, 32>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
-        return step_launch<&k_ffn<P, 2, 2, 2, 4, 2, false, true>>(h, dim3(cdiv(MT, 2)), dim3(256), f);
+    const int MT = y.MT, rows = y.ks.ffn_rows;
+    // ROWS: one 16-row tile per workgroup (bf16w2, round 6: the only form, two-register fragments on a shorter ring); STREAM: 32-row blocks, C256: 64 as well (rt4)
+    constexpr int RING256 = P::W2 ? 12 : 32, RING128 = P::W2 ? 8 : 0;
+    switch (h->core) {
+        case Core::C256:
+            if (P::W2 || rows == 16) return step_launch<&k_ffn<P, 4, 16, 1, 8, 2, true, true, RING256>>(h, dim3(MT), dim3(512), f);
+            if constexpr (!P::W2) {
+                if (rows == 64) return step_launch<&k_ffn<P, 4, 16, 4, 8, 1, true, true, 12>>(h, dim3(cdiv(MT, 4)), dim3(512), f);
+                return step_launch<&k_ffn<P, 4, 16, 2, 8, 2, true, true, 32>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
+            }
+            break;
+        case Core::C128:
+            if (P::W2 || rows == 16) return step_launch<&k_ffn<P, 2, 2, 1, 4, 2, false, true, RING128>>(h, dim3(MT), dim3(256), f);
+            if constexpr (!P::W2) return step_launch<&k_ffn<P, 2, 2, 2, 4, 2, false, true>>(h, dim3(cdiv(MT, 2)), dim3(256), f);
+            break;
+        default: break;
     }
+    return no_inst(h, "k_ffn<OP>");
 }
 // ROWS at the DSG+ widths (round 6): QKV slices + attention per (clip, head) -- k_clip_attn_w (dsg_stream.h) -- and k_ffn<OP>
 template <class P>
@@ -1731,20 +1789,27 @@ static int layer_clip_w_ffn(dsg_handle* h, const LayerCtx& y) {
     // 371.3 vs 360.0 us per step, 4 x 16: 614 vs 604 -- profiles/r06_dq_*); 512: 192 weight registers, so the bias waits in the LDS and the A fragments have no
     // look-ahead (254 VGPRs).  The two-pass form (Q / K, then V in pairs on waves 0 - 3) read the rows from the LDS 1.5 times and reloaded weights in between:
     // TWH 1 x 16 clips 475.1 vs 472.9 us per step, 4 x 8: 601 vs 585, 4 x 16: 836.7 vs 830.1, bit-identical -- profiles/r06_dw_*; since retired
-    if (h->D == 384) CHK((step_launch<&k_clip_attn_w<6, 10, 4>>(h, dim3(4, B), dim3(512), a)));
-    else CHK((step_launch<&k_clip_attn_w<8, 10, 2>>(h, dim3(4, B), dim3(512), a)));
+    switch (h->core) {
+        case Core::C384: CHK((step_launch<&k_clip_attn_w<6, 10, 4>>(h, dim3(4, B), dim3(512), a))); break;
+        case Core::C512: CHK((step_launch<&k_clip_attn_w<8, 10, 2>>(h, dim3(4, B), dim3(512), a))); break;
+        default: return no_inst(h, "k_clip_attn_w");
+    }
     const FfnArgs f = ffn_args(h, y, true);
     // latent_dim 384: W_o (36 fragments per wave) waits in registers as at the ZEGGS widths; 512: 64 fragments do not fit -- W_o leads the weight ring.
     // Round 6: with >= 3 lanes whose row tiles together need more than one round of the 256 CUs, 32-row blocks -- W_o | W1 | W2 (1.8 / 2.5 MB) streamed once
     // per 32 rows; W_o leads the ring at both widths (20 / 12 slots: 250 VGPRs), at 512 the fp32 LayerNorm1 rows wait in X1 instead of the LDS.
     // Bit-identical to the 16-row form.  BEAT 4 x 16 clips 946 -> 825 us per step, 4 x 8: 542 -> 516; 1 x 16: 375 -> 412, 4 x 4: 375 -> 398, 2 x 16 even
     // (profiles/r06_dj_*)
-    if (y.ks.ffn_rows == 32) {
-        if (h->D == 384) return step_launch<&k_ffn<P, 6, 16, 2, 8, 2, true, true, 20, true>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
-        return step_launch<&k_ffn<P, 8, 16, 2, 8, 2, true, true, 12, true>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
+    const bool rows32 = y.ks.ffn_rows == 32;
+    switch (h->core) {
+        case Core::C384:
+            if (rows32) return step_launch<&k_ffn<P, 6, 16, 2, 8, 2, true, true, 20, true>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
+            return step_launch<&k_ffn<P, 6, 16, 1, 8, 2, true, true, 24>>(h, dim3(MT), dim3(512), f);      // (W_o leading the ring here too: 353.1 -> 357.8 us per step at 16 clips, r06_ea)
+        case Core::C512:
+            if (rows32) return step_launch<&k_ffn<P, 8, 16, 2, 8, 2, true, true, 12, true>>(h, dim3(cdiv(MT, 2)), dim3(512), f);
+            return step_launch<&k_ffn<P, 8, 16, 1, 8, 2, true, true, 24, true>>(h, dim3(MT), dim3(512), f);
+        default: return no_inst(h, "k_ffn<OP>");
     }
-    if (h->D == 384) return step_launch<&k_ffn<P, 6, 16, 1, 8, 2, true, true, 24>>(h, dim3(MT), dim3(512), f);      // (W_o leading the ring here too: 353.1 -> 357.8 us per step at 16 clips, r06_ea)
-    return step_launch<&k_ffn<P, 8, 16, 1, 8, 2, true, true, 24, true>>(h, dim3(MT), dim3(512), f);
 }
 // the forms that exist for precision P (select_kernels picks no other): fp32 has no k_clip_attn / k_ffn, bf16w2 no k_attn_op
 template <class P>
@@ -1766,27 +1831,19 @@ static int run_layer(dsg_handle* h, Form f, const LayerCtx& y) {
 template <class P>
 static int run_step(dsg_handle* h, const StepCtx& c) {
     const int B = c.B, D = h->D, T = h->T, ntok = h->ntok;
-    const int Min = B * T, M = B * ntok;
-    const int MTin = cdiv(Min, 16), MT = cdiv(M, 16);
-    const int KB = P::KB;
+    const int Min = B * T, M = B * ntok, MT = cdiv(M, 16);
     const KernelSel& ks = c.ks;
+    StepCtl* const ctl = c.use_ctr ? h->ctl : nullptr;
     const GemmArgs z = gemm_base(h, B);
-    const LocArgs la = loc_args(h, B, ks.ks_in, c.use_ctr ? h->ctl : nullptr, ks.x0a_frag);
+    const LocArgs la = loc_args(h, B, ks.ks_in, ctl, ks.x0a_frag);
     h->fence_next = 1;         // the first packet of a step reads the state the previous step's last packet wrote (state_fences)
     if (ks.set == DSG_KSET_LATENCY) {      // pose embedding + local attention in one launch (in the batched sets it loses: 1 x 16 clips 192.1 -> 198.5 us
                                            // per step, 1 x 64: 258 -> 291, 4 x 4 even -- profiles/r06_ab_*, round 6)
-        InLocArgs a;
-        a.xs = is_bf16(h) ? h->xsA : (void*)h->xs32; a.Jp = h->Jp; a.Wp = h->Wp_in; a.KBtot = h->Jp / KB;
-        a.loc = la; a.ctl_upd = c.use_ctr ? h->ctl : nullptr; a.st = step_tables(h); a.n_tab = h->n_run;
-        DSG_LOC_DISPATCH(k_inloc, a, dim3(h->Hl, T / h->W, B + 1));
+        CHK((launch_loc<P, true, 256>(h, dim3(h->Hl, T / h->W, B + 1), inloc_args(h, la, ctl, h->n_run))));
     } else {
-        {   // k_in: partial[s] = xs[:, chunk s] . Wfold[:, chunk s]^T
-            GemmArgs g = z;
-            g.M = Min; g.MT = MTin; g.NT = D / 16; g.KBtot = h->Jp / KB; g.KS = ks.ks_in; g.Wp = h->Wp_in;
-            g.kb_per_split = cdiv(g.KBtot, g.KS);
-            g.A = is_bf16(h) ? h->xsA : (void*)h->xs32; g.lda = h->Jp;
-            g.out = h->partial; g.ldo = D;
-            g.ctl = c.use_ctr ? h->ctl : nullptr; g.st = step_tables(h); g.n_tab = h->n_run;
+        {
+            GemmArgs g = gemm_pose_in(h, z, Min, ks.ks_in);
+            step_ctl(h, g, ctl);
             bool done = false;
             if constexpr (sizeof(typename P::elem) == 2 && !P::W2) {
                 if (ks.xs_frag) { g.a_frag = 1; CHK(launch_ws2<EPI_PARTIAL>(h, g)); done = true; }      // the state shadow is fragment-major
@@ -1801,8 +1858,8 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
         // resident at once (32 per CU) -- 1 x 64 clips 249.1 -> 245.0 us per step (one wave each: 246.4), 4 x 64: 705 -> 692-702 (29.2-29.6 k frames/s);
         // k_loc itself 13.3 -> 10.0 us at 5696 rows with one wave; below 2048 items the 4-wave form is ahead (16 clips: 184.1 vs 186.0).  Same arithmetic
         // (the matrix-instruction tail is one wave's work in every form): bit-identical.  profiles/r06_cj_*, r06_cl_*
-        if (h->Hl * (T / h->W) * B >= h->env_loc64_from) DSG_LOC1_DISPATCH(la, dim3(h->Hl, T / h->W, B));
-        else DSG_LOC_DISPATCH(k_loc, la, dim3(h->Hl, T / h->W, B));
+        if (h->Hl * (T / h->W) * B >= h->env_loc64_from) CHK((launch_loc<P, false, 128>(h, dim3(h->Hl, T / h->W, B), la)));
+        else CHK((launch_loc<P, false, 256>(h, dim3(h->Hl, T / h->W, B), la)));
     }
     int in_frag = ks.x0a_frag;
     for (int l = 0; l < h->L; ++l) {
@@ -1812,12 +1869,9 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
         in_frag = leaves_x0a(f) ? 1 : -1;
     }
     {   // final LayerNorm-on-read + pose head + sampler update
-        GemmArgs g = z;
-        g.M = M; g.MT = MT; g.NT = h->Jp / 16; g.KBtot = D / KB; g.Wp = h->Wp_out; g.bias = h->b_out;
-        g.X = h->pre2; g.ln_g = h->layers[h->L - 1].g2; g.ln_b = h->layers[h->L - 1].be2; g.Xn = nullptr;
-        g.out_mode = c.out_mode; g.xs32 = h->xs32; g.xsA = is_bf16(h) ? h->xsA : nullptr;
-        g.fwd_out = h->fwd_out; g.ctl = c.use_ctr ? h->ctl : nullptr; g.st = step_tables(h); g.n_tab = h->n_run;
-        g.dyn = h->dyn; g.ext_noise = c.ext_noise; g.const_noise = c.const_noise; g.clip_x0 = c.clip_x0; g.no_noise = c.no_noise;
+        GemmArgs g = gemm_pose_head(h, z, M, h->layers[h->L - 1]);
+        step_ctl(h, g, ctl);
+        g.out_mode = c.out_mode; g.ext_noise = c.ext_noise; g.const_noise = c.const_noise; g.clip_x0 = c.clip_x0; g.no_noise = c.no_noise;
         g.xs_frag = ks.xs_frag ? 1 : 0;
         h->fence_next = 2;     // the last packet of a step writes the state (state_fences)
         if (h->cfgB > 0) {      // guidance: one workgroup per CONDITIONAL row tile evaluates the twin rows as well (k_gemm_cfg)
@@ -1849,48 +1903,33 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
 //      9 LN+QKV cycling, 10 k_mid cycling, 12 k_inloc
 template <class P>
 static int debug_launch(dsg_handle* h, int which, int i, int B) {
-    const int D = h->D, T = h->T, ntok = h->ntok, M = B * ntok, MT = cdiv(M, 16), Min = B * T, MTin = cdiv(Min, 16);
-    const int KB = P::KB;
+    const int T = h->T, M = B * h->ntok;
     const GemmArgs z = gemm_base(h, B);
     const Layer& ly = h->layers[(which == 1) ? 0 : i % h->L];
     const LocArgs la = loc_args(h, B, h->KSin, nullptr, 0);
     if (which == 20) return debug_launch<P>(h, (i & 1) ? 1 : 4, i, B);                 // alternate 2 kernels
     if (which == 21) { const int seq[4] = {1, 4, 7, 9}; return debug_launch<P>(h, seq[i & 3], i, B); }   // 4 kernels
     if (which == 22) { const int seq[6] = {12, 9, 5, 10, 4, 8}; return debug_launch<P>(h, seq[i % 6], i, B); } // the step's 6 kernels
+    // the step's own GemmArgs (gemm_*), every GEMM on the 16 x 16 tile kernel; what a chain of one kernel changes is set after the builder call
     switch (which) {
         case 0: hipLaunchKernelGGL(k_ctr_inc, dim3(96), dim3(256), 0, h->stream, h->ctr); return 0;
         case 1: case 2: {
-            GemmArgs g = z; g.M = M; g.MT = MT; g.NT = D / 16; g.KBtot = D / KB; g.Wp = ly.Wo; g.bias = ly.bo;
-            g.A = h->attn; g.lda = D; g.a_frag = 1; g.out = (i & 1) ? h->pre1 : h->pre2; g.ldo = D; g.R = h->X0;
+            GemmArgs g = gemm_out_proj(h, z, M, ly, h->X0);
+            g.out = (i & 1) ? h->pre1 : h->pre2;      // (two targets in turn)
             return launch_gemm<P, PRO_DIRECT, EPI_RESID, 4, 1>(h, g); }
-        case 3: {
-            GemmArgs g = z; g.M = M; g.MT = MT; g.NT = h->ff / 16; g.KBtot = D / KB; g.Wp = ly.W1; g.bias = ly.b1;
-            g.X = h->pre1; g.ln_g = ly.g1; g.ln_b = ly.be1; g.Xn = h->X1; g.out = h->hidden; g.ldo = h->ff; g.out_frag = 1;
-            return launch_gemm<P, PRO_LN, EPI_GELU, 4, 1>(h, g); }
-        case 4: {
-            GemmArgs g = z; g.M = M; g.MT = MT; g.NT = D / 16; g.KBtot = h->ff / KB; g.Wp = ly.W2; g.bias = ly.b2;
-            g.A = h->hidden; g.lda = h->ff; g.a_frag = 1; g.out = h->pre2; g.ldo = D; g.R = h->X1;
-            return launch_gemm<P, PRO_DIRECT, EPI_RESID, 1, 4>(h, g); }
+        case 3: return launch_gemm<P, PRO_LN, EPI_GELU, 4, 1>(h, gemm_linear1(h, z, M, ly, false));
+        case 4: return launch_gemm<P, PRO_DIRECT, EPI_RESID, 1, 4>(h, gemm_linear2(h, z, M, ly));
         case 5: return launch_attn<P>(h, B);
-        case 6: DSG_LOC_DISPATCH(k_loc, la, dim3(h->Hl, T / h->W, B)); return 0;
-        case 7: {
-            GemmArgs g = z; g.M = Min; g.MT = MTin; g.NT = D / 16; g.KBtot = h->Jp / KB; g.KS = h->KSin; g.Wp = h->Wp_in;
-            g.kb_per_split = cdiv(g.KBtot, g.KS); g.A = is_bf16(h) ? h->xsA : (void*)h->xs32; g.lda = h->Jp;
-            g.out = h->partial; g.ldo = D; return launch_gemm<P, PRO_DIRECT, EPI_PARTIAL, 4, 1>(h, g); }
+        case 6: return launch_loc<P, false, 256>(h, dim3(h->Hl, T / h->W, B), la);
+        case 7: return launch_gemm<P, PRO_DIRECT, EPI_PARTIAL, 4, 1>(h, gemm_pose_in(h, z, B * T, h->KSin));      // (no control block: the step does not advance)
         case 8: {
-            GemmArgs g = z; g.M = M; g.MT = MT; g.NT = h->Jp / 16; g.KBtot = D / KB; g.Wp = h->Wp_out; g.bias = h->b_out;
-            g.X = h->pre2; g.ln_g = ly.g2; g.ln_b = ly.be2; g.out_mode = OUT_FORWARD; g.xs32 = h->xs32; g.fwd_out = h->fwd_out;
-            g.ctl = nullptr; g.st = step_tables(h); g.n_tab = 1; g.dyn = h->dyn;
+            GemmArgs g = gemm_pose_head(h, z, M, ly);
+            g.out_mode = OUT_FORWARD; g.xsA = nullptr;      // a forward: writes fwd_out, leaves the state and its shadow alone
+            g.st = step_tables(h); g.n_tab = 1;             // ... and reads no control block
             return launch_gemm<P, PRO_LN, EPI_OUT, 4, 1>(h, g); }
-        case 9: {
-            GemmArgs g = z; g.M = M; g.MT = MT; g.NT = 3 * D / 16; g.KBtot = D / KB; g.Wp = ly.Wqkv; g.bias = ly.bqkv;
-            g.q = h->q; g.k = h->k; g.vt = h->vt; g.X = h->pre2; g.ln_g = ly.g2; g.ln_b = ly.be2; g.Xn = h->Xn;
-            return launch_gemm<P, PRO_LN, EPI_QKV, 4, 1>(h, g); }
+        case 9: return launch_gemm<P, PRO_LN, EPI_QKV, 4, 1>(h, gemm_qkv(h, z, M, ly, -1, &ly));      // (LayerNorm2 of the same layer)
         case 10: return launch_mid<P>(h, mid_args(h, ly, h->Xn, M));
-        case 12: {
-            InLocArgs a; a.xs = is_bf16(h) ? h->xsA : (void*)h->xs32; a.Jp = h->Jp; a.Wp = h->Wp_in;
-            a.KBtot = h->Jp / KB; a.loc = la; a.ctl_upd = nullptr; a.st = step_tables(h); a.n_tab = 1;
-            DSG_LOC_DISPATCH(k_inloc, a, dim3(h->Hl, T / h->W, B + 1)); return 0; }
+        case 12: return launch_loc<P, true, 256>(h, dim3(h->Hl, T / h->W, B + 1), inloc_args(h, la, nullptr, 1));
         default: return fail(DSG_E_INVALID, "debug_chain: unknown kernel id");
     }
 }

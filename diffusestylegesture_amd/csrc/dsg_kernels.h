@@ -1216,7 +1216,7 @@ __device__ __forceinline__ void local_attn_tail_valu(const LocArgs& a, float (&r
 }
 
 // Tail of k_loc (every other set).  Round 6: the scores and the P V product of the (head, window) tile on fp32 MATRIX instructions (v_mfma_f32_16x16x4_f32),
-// by ONE wave of the workgroup -- which is what lets the kernel run as one wave per item at large batches (dsg_hip.cpp: DSG_LOC1_DISPATCH); k_inloc keeps the
+// by ONE wave of the workgroup -- which is what lets the kernel run as one wave per item at large batches (dsg_hip.cpp: launch_loc); k_inloc keeps the
 // VALU form above: alone on its CU at batch 1, four SIMDs on the tile beat 32 fp32 MFMAs on one (106.1 vs 106.8 us per step, profiles/r06_cm_*).
 // The VALU form read the rotary tile out of LDS once per (query, key) pair and per (query, dim pair) -- ~108 KB of LDS reads per workgroup against a 3 KB
 // tile: phase A alone was 1.8 of the kernel's 5.4 us at 16 clips and the kernel 13.3 us at 64 (4096 workgroups, two rounds of 8 per CU).  Here a lane reads
@@ -1413,7 +1413,7 @@ __device__ __forceinline__ void loc_body(const LocArgs& a, int h, int w, int b) 
     local_attn_tail<P, HD, W, NT>(a, rot, sc, b, w, h, keyok, c2, s2);
 }
 
-template <class P, int HD, int W, int NT = 256>      // NT = 128 (round 6): two waves per (head, window, clip) at large batches -- see dsg_hip.cpp: DSG_LOC1_DISPATCH
+template <class P, int HD, int W, int NT = 256>      // NT = 128 (round 6): two waves per (head, window, clip) at large batches -- see dsg_hip.cpp: launch_loc
 __global__ __launch_bounds__(NT) void k_loc(const LocArgs a) {
     DSG_TL_SCOPE();
     preload_kernargs(a);

@@ -87,7 +87,7 @@ enum {
     DSG_KSET_ROWS = 5       /* ABI 330: BLOCK's pose embedding / local attention / pose head around STREAM's per-layer pair, the feed-forward kernel on
                                ONE 16-row tile per workgroup (no ff-split, no partial slabs, no slab-sum pass: 3 + 2L dispatches).  Every workgroup
                                streams a layer's W_o + W1 + W2 for its 16 rows: it pays while the row tiles of all lanes fit the 256 CUs in one
-                               round -- 1000 .. 4000 token rows in one lane (12 .. 45 ZEGGS clips), fewer per lane with several lanes.  Same shapes
+                               round -- 800 .. 4096 token rows in one lane (9 .. 46 ZEGGS clips), fewer per lane with several lanes.  Same shapes
                                as STREAM, in bf16 and (without fused guidance) bf16w2.  At the DSG+ widths (bf16, latent_dim 384 / 512, 4 heads, ff 1024;
                                no fused guidance): streamed pose embedding, then per layer the attention half per (clip, head) (k_clip_attn_w: the rows pass
                                through the LDS in chunks) + the same feed-forward kernel -- on 32-row blocks when >= 3 lanes together exceed one round of the

@@ -138,8 +138,8 @@ def test_tile_gemm_xcd_balanced_mapping_from_16_row_tiles(emu_lib):
 
 
 def test_local_attention_one_wave_form_is_bit_identical(emu_lib, monkeypatch):
-    """Round 6: k_loc's scores / P V on fp32 matrix instructions by one wave; from 2048 (head, window, clip) items the kernel runs as ONE wave per item
-    (DSG_LOC64_FROM is the test hook for the threshold; two waves per item in the shipped form).  Both forms against the oracle (incl. a key mask and mask_local=None), bit-identical to each other."""
+    """Round 6: k_loc's scores / P V on fp32 matrix instructions by one wave; from 2048 (head, window, clip) items the kernel runs as TWO waves per item
+    instead of four (DSG_LOC64_FROM is the test hook for the threshold).  Both forms against the oracle (incl. a key mask and mask_local=None), bit-identical to each other."""
     from oracle.mdm import MDMOracle
     cfg = C.TINY
     sd = synth_state_dict(cfg, 20240)
@@ -168,7 +168,7 @@ def test_local_attention_one_wave_form_is_bit_identical(emu_lib, monkeypatch):
 
 @pytest.mark.parametrize("name", ["beat", "twh"])
 def test_rows_kernel_set_at_dsgplus_widths(emu_lib, name):
-    """Round 6: ROWS at latent_dim 384 / 512 (streamed pose embedding with K over two workgroups, k_clip_attn_w -- one pass over the rows at 384, two at 512 --, k_ffn<OP> on 16-row
+    """Round 6: ROWS at latent_dim 384 / 512 (streamed pose embedding with K over two workgroups, k_clip_attn_w -- one pass over the rows at both widths --, k_ffn<OP> on 16-row
     tiles -- at 512 W_o leads the weight ring --, the streaming pose head k_ws<OUT, 24 / 32>) -- one forward at batch 1 against
     the oracle under the emulator (the GPU test has batch 16, batch independence and a chain)."""
     from oracle.mdm import MDMOracle
