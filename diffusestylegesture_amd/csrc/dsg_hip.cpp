@@ -154,6 +154,8 @@ struct dsg_handle {
     unsigned char* mask = nullptr; int mb = 1; int nomask = 0;
     // classifier-free guidance (dsg_set_window_cond_cfg): cfgB user batch elements + their unconditional twins = condB rows
     int cfgB = 0; float* cfg_scale = nullptr;
+    // inpainting constraint (dsg_set_inpainting): inpB user batch elements in the state's layout [inpB][T][Jp]; 0 = off.  Allocated on first use
+    int inpB = 0; float* inp32 = nullptr; unsigned char *inp_mask = nullptr, *inp_stage = nullptr;
     int last_path = -1;                  // submission path of the last dsg_sample: 0 HIP launches, 1 AQL packets, 2 hipGraph replay
     bool last_nofence = false;           // ... and whether its packets went without fences
     int kset_req = DSG_KSET_AUTO;        // dsg_set_kernel_set: the kernel set every step of this handle runs (AUTO: by batch, select_kernels)
@@ -202,6 +204,7 @@ struct dsg_handle {
     bool st_valid = false; int st_mode = -1, st_skip = -1; float st_eta = 0.f;      // what the device tables hold
     Sched sched;
     // graphs: key = (B, out_mode, mask batch, const_noise, steps, flags, kernel set) -> exec
+    // (flags: 1 clip_denoised, 2 guidance, 4 no mask_local, 8 k_attn_mid, 16 no noise, 32 inpainting on -- the captured pose head carries the constraint's pointers)
     // n_run is part of the key: the captured kernels carry the step-table length as an argument (n_tab); so is the kernel set
     // (a graph captured under one set must never be replayed for a call that asked for another)
     // (round-4 advisor: n_run = the steps of THIS call, n_tab = the length of the whole chain = what the captured kernels clamp their
@@ -1238,6 +1241,7 @@ struct StepCtx {
     int out_mode; bool use_ctr; const float* ext_noise; int const_noise;
     int no_noise = 0;       // DDIM with eta = 0: no step adds noise (the pose head skips the Philox draw)
     int clip_x0 = 0;        // clip_denoised=True
+    int inpaint = 0;        // the handle's inpainting constraint applies (sampling only: MDM.forward does not inpaint)
     KernelSel ks;           // what select_kernels chose for this call
 };
 
@@ -1873,6 +1877,7 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
         step_ctl(h, g, ctl);
         g.out_mode = c.out_mode; g.ext_noise = c.ext_noise; g.const_noise = c.const_noise; g.clip_x0 = c.clip_x0; g.no_noise = c.no_noise;
         g.xs_frag = ks.xs_frag ? 1 : 0;
+        if (c.inpaint) { g.inp32 = h->inp32; g.inp_mask = h->inp_mask; }      // every pose-head form below reads the same GemmArgs
         h->fence_next = 2;     // the last packet of a step writes the state (state_fences)
         if (h->cfgB > 0) {      // guidance: one workgroup per CONDITIONAL row tile evaluates the twin rows as well (k_gemm_cfg)
             g.B = h->cfgB; g.M = h->cfgB * ntok; g.MT = cdiv(g.M, 16);
@@ -2104,6 +2109,37 @@ static int rows_for(dsg_handle* h, int B, int* rows) {
     return 0;
 }
 
+// y['inpainting_mask'] / y['inpainted_motion'] of the sampling loops (main/diffusion/gaussian_diffusion.py:317-321): both [B, J, 1, T], host or
+// device.  Every step of dsg_sample / dsg_sample_multi then replaces the model's x0 prediction -- after the guidance combination, before the
+// clamp and the posterior -- by the motion wherever the mask is set (GemmArgs::inp32).  Sticky until switched off (both NULL); the window
+// conditioning does not touch it.  The constraint is kept in the state's layout, in cached memory like the conditioning: the loop only reads it.
+extern "C" int dsg_set_inpainting(dsg_handle* h, const uint8_t* mask, const float* motion, int B, void* stream) {
+    if (!h) return fail(DSG_E_INVALID, "null handle");
+    if (!mask && !motion) { h->inpB = 0; return 0; }
+    if (!mask || !motion) return fail(DSG_E_INVALID, "dsg_set_inpainting: mask and motion go together (both NULL switches the constraint off)");
+    if (B <= 0 || B > h->Bmax) return fail(DSG_E_INVALID, "batch exceeds max_batch");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t n = (size_t)B * h->J * h->T, nq = (size_t)B * h->T * (h->Jp / 4);
+    // (each pointer on its own: a call that failed half way through leaves the rest to the next one)
+    if (!h->inp32) CHK(dalloc(h, &h->inp32, (size_t)h->Bmax * h->T * h->Jp));
+    if (!h->inp_mask) CHK(dalloc(h, &h->inp_mask, (size_t)h->Bmax * h->T * h->Jp));
+    if (!h->inp_stage) CHK(dalloc(h, &h->inp_stage, (size_t)h->Bmax * h->J * h->T));
+    CHK(order_after(h, stream));
+    const float* md = nullptr;
+    CHK(to_dev(h, motion, h->io_tmp, n, &md));
+    const uint8_t* kd = mask;
+    if (!is_device_ptr(mask)) {
+        HIPCHK(hipMemcpyAsync(h->inp_stage, mask, n, hipMemcpyHostToDevice, h->stream));
+        kd = h->inp_stage;
+    }
+    hipLaunchKernelGGL(k_inp_in, dim3((int)std::min<size_t>((nq + 255) / 256, 2048)), dim3(256), 0, h->stream, md, kd, B, h->J, h->Jp, h->T,
+                       h->inp32, h->inp_mask);
+    HIPCHK(hipGetLastError());
+    h->inpB = B;
+    CHK(order_before(h, stream));
+    return 0;
+}
+
 extern "C" int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, float* out, int B, void* stream) {
     if (!h || !x || !t || !out) return fail(DSG_E_INVALID, "dsg_forward: null argument");
     if (!h->finalized || !h->cond_set) return fail(DSG_E_STATE, "dsg_forward before finalize / set_window_cond");
@@ -2263,6 +2299,7 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     if (!h->finalized || !h->cond_set) return fail(DSG_E_STATE, "dsg_sample before finalize / set_window_cond");
     int rows = 0;
     CHK(rows_for(h, B, &rows));
+    if (h->inpB > 0 && h->inpB != B) return fail(DSG_E_INVALID, "batch differs from the batch of dsg_set_inpainting");
     if (a->mode != DSG_MODE_DDPM && a->mode != DSG_MODE_DDIM) return fail(DSG_E_INVALID, "mode");
     // (dump points are allowed with DDIM: ddim_sample_loop_progressive is built on them; the Python ddim_sample_loop itself
     // refuses dump_steps like the reference, gaussian_diffusion.py:913-916)
@@ -2319,6 +2356,7 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     c.B = rows; c.out_mode = a->mode == DSG_MODE_DDPM ? OUT_DDPM : OUT_DDIM; c.use_ctr = true; c.ext_noise = ext;
     c.const_noise = a->const_noise; c.clip_x0 = a->clip_denoised ? 1 : 0;
     c.no_noise = (a->mode == DSG_MODE_DDIM && a->eta == 0.f && !ext) ? 1 : 0;
+    c.inpaint = h->inpB > 0 ? 1 : 0;      // (the AQL argument blocks are recorded anew below for every call: on / off needs no invalidation)
     c.ks = ksel;
     n_run = n_iter;                          // from here on: the steps of this call (the tables keep the whole chain: h->n_run)
     job.n_run = n_iter; job.B = B; job.done = 0; job.first = first;
@@ -2372,7 +2410,7 @@ static int sample_run_hip(dsg_handle* h, const dsg_sample_args* a, SampleJob& jo
     if (spg > 0 && n_run >= spg && job.done == 0) {
         // everything that varies between calls (step index, coefficients, noise key, conditioning) lives in device
         // memory, so one captured graph per (batch, sampler, mask batch, const_noise, steps, flags, kernel set) serves every window and clip
-        dsg_handle::GKey key = {c.B, c.out_mode, h->mb, c.const_noise, n_run, h->n_run, (c.clip_x0 ? 1 : 0) | (h->cfgB ? 2 : 0) | (h->nomask ? 4 : 0) | (c.ks.attn_in_mid ? 8 : 0) | (c.no_noise ? 16 : 0),
+        dsg_handle::GKey key = {c.B, c.out_mode, h->mb, c.const_noise, n_run, h->n_run, (c.clip_x0 ? 1 : 0) | (h->cfgB ? 2 : 0) | (h->nomask ? 4 : 0) | (c.ks.attn_in_mid ? 8 : 0) | (c.no_noise ? 16 : 0) | (c.inpaint ? 32 : 0),
                                 c.ks.set};
         auto it = h->graphs.find(key);
         bool ok = true;

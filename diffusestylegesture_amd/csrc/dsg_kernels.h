@@ -559,6 +559,11 @@ struct GemmArgs {
                             // embedding streams it like every other operand (k_ws2<EPI_PARTIAL>)
     int no_noise;           // EPI_OUT: the sampler adds no noise at any step of this call (DDIM with eta = 0: sigma = 0,
                             // gaussian_diffusion.py:782-791) -- the Philox draw is skipped, x_{t-1} = mean + 0 z bit for bit
+    // EPI_OUT, inpainting (gaussian_diffusion.py:317-321; dsg_set_inpainting): x0 = mask ? inp : x0 after the guidance combination and
+    // before the clamp, OUT_DDPM / OUT_DDIM only.  Both in the state's layout [B][T][Jp], the mask one byte per element (0 / 1), read
+    // only by the loop (cached memory).  With guidance they are indexed by the conditional element.  inp32 == null: off (the one test).
+    const float* inp32;
+    const unsigned char* inp_mask;
 };
 
 // Workgroup -> n-group with the n-group pinned to an XCD (workgroups are dealt round-robin to the 8 XCDs in linear
@@ -836,6 +841,16 @@ __device__ __forceinline__ void gemm_epilogue_tile(const GemmArgs& g, int m0, in
                     const float sc = g.cfg_scale[b];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) x0[e] = xu[e] + sc * (x0[e] - xu[e]);
+                }
+                // gaussian_diffusion.py:317-321: the constraint replaces the (combined) prediction before the clamp.  The two loads are
+                // issued here, under the wave-uniform test, not with x_t: the pose heads at the register limit keep their budget, and
+                // a call without a constraint pays one scalar compare (the host leaves the pointer null for OUT_FORWARD)
+                if (g.inp32) {
+                    const unsigned ie = imul24(srow, g.Jp) + (unsigned)j0;      // the state's index of this quad
+                    const f32x4 iv = *(const f32x4*)((const char*)g.inp32 + (size_t)(ie * 4u));
+                    const unsigned mk = *(const unsigned*)(g.inp_mask + ie);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x0[e] = ((mk >> (8 * e)) & 0xffu) ? iv[e] : x0[e];
                 }
                 if (g.clip_x0) {                        // gaussian_diffusion.py:377-379
 #pragma unroll
@@ -1592,6 +1607,27 @@ __global__ void k_x_in(const XInArgs a) {
             *(f32x4*)(a.xs32 + ((size_t)(b + a.dupB) * a.T + f) * a.Jp + j0) = z;
             if (a.xsA) P::store4((elem*)a.xsA + xs_off<P>((b + a.dupB) * a.T + f, j0, a.Jp, a.xs_frag), z);
         }
+    }
+}
+// the inpainting constraint into the state's layout (dsg_set_inpainting): motion / mask [B][J][T] -> inp32 / inp_mask [B][T][Jp], one thread
+// per feature quad; any non-zero mask byte becomes 1, the padded columns are written as 0 / unmasked
+__global__ void k_inp_in(const float* motion, const unsigned char* mask, int B, int J, int Jp, int T, float* inp32, unsigned char* inp_mask) {
+    const size_t n = (size_t)B * T * (Jp / 4);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int j0 = (int)(i % (Jp / 4)) * 4;
+        const size_t bf = i / (Jp / 4);
+        const int f = (int)(bf % T), b = (int)(bf / T);
+        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+        unsigned mk = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (j0 + e < J) {
+                const size_t src = ((size_t)b * J + j0 + e) * T + f;
+                v[e] = motion[src];
+                mk |= (mask[src] ? 1u : 0u) << (8 * e);
+            }
+        *(f32x4*)(inp32 + bf * Jp + j0) = v;
+        *(unsigned*)(inp_mask + bf * Jp + j0) = mk;
     }
 }
 // the framework's noise stream as a tensor: out [B][J][T] (the reference's [B, J, 1, T]) = draw `draw` of (seed, stream) --

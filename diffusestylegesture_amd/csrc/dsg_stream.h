@@ -297,8 +297,10 @@ __device__ __forceinline__ void ws_body(const GemmArgs& g, const WsId id, char* 
     }
 }
 
-template <int EPI, int KD16, bool ONE = false>      // ONE (pose head): a workgroup per (panel, row block), one activation buffer, three workgroups per CU
-__global__ __launch_bounds__(256, KD16 > 16 ? 1 : (ONE ? 3 : 2)) void k_ws(const GemmArgs g) {      // (round 6: K = 384 / 512 -- the DSG+ widths: a 192 / 256-register panel, one workgroup per CU)
+// (ONE is bounded at FOUR workgroups per CU: that is what its 122 / 126 registers and 16 / 32 KB of LDS gave it at K = 128 / 256 all along; the bound
+//  keeps the inpainting branch of the epilogue, dsg_kernels.h, from costing the fourth -- 129 registers under the former bound of three)
+template <int EPI, int KD16, bool ONE = false>      // ONE (pose head): a workgroup per (panel, row block), one activation buffer
+__global__ __launch_bounds__(256, KD16 > 16 ? 1 : (ONE ? 4 : 2)) void k_ws(const GemmArgs g) {      // (round 6: K = 384 / 512 -- the DSG+ widths: a 192 / 256-register panel, one workgroup per CU)
     DSG_TL_SCOPE();
     typedef PBF16 P;
     constexpr int K = 16 * KD16, BM = 64;

@@ -153,6 +153,13 @@ class DSGDiffusion:
         if y is None:
             raise ValueError("model_kwargs['y'] is required")
         model.set_schedule(self)
+        # gaussian_diffusion.py:317-321: the constraint applies when BOTH keys are there (one alone is ignored, as in the reference); the
+        # lane keeps it until a call without the keys switches it off -- no library call for that on a lane that never had one
+        if _INPAINT_KEYS[0] in y and _INPAINT_KEYS[1] in y:
+            model.set_inpainting(_inpaint_mask(y[_INPAINT_KEYS[0]]), y[_INPAINT_KEYS[1]], B)
+        elif model.inpainting:
+            model.set_inpainting(None, None, 0)
+        y = {k: v for k, v in y.items() if k not in _INPAINT_KEYS}
         if guided:
             if "scale" not in y:
                 raise KeyError("scale")
@@ -370,6 +377,16 @@ class DSGDiffusion:
         lib = self._lib or L.default_library()
         if device is None:
             device = next(model.parameters()).device
+        # gaussian_diffusion.py:317-321 (both keys, as in `_prepare`); the shapes are checked before any work is done
+        inp_mask = inp_motion = None
+        y = (model_kwargs or {}).get("y") or {}
+        if _INPAINT_KEYS[0] in y and _INPAINT_KEYS[1] in y:
+            inp_mask = torch.as_tensor(_inpaint_mask(y[_INPAINT_KEYS[0]]))
+            inp_motion = torch.as_tensor(y[_INPAINT_KEYS[1]])
+            for key, v in zip(_INPAINT_KEYS, (inp_mask, inp_motion)):
+                if tuple(v.shape) != tuple(shape):
+                    raise ValueError(f"y['{key}'] shape {tuple(v.shape)} != {tuple(shape)}")
+            inp_mask, inp_motion = inp_mask.to(device), inp_motion.to(device=device, dtype=torch.float32)
         B = int(shape[0])
         per = int(np.prod(shape[1:]))
         stream = L.current_stream_ptr()
@@ -396,6 +413,8 @@ class DSGDiffusion:
             t = torch.full((B,), i, device=device, dtype=torch.long)
             with torch.no_grad():
                 x0 = model(img, tmap[t], **(model_kwargs or {})).contiguous().float()
+                if inp_mask is not None:      # gaussian_diffusion.py:317-321: before denoised_fn and the clamp
+                    x0 = torch.where(inp_mask, inp_motion, x0)
                 if denoised_fn is not None:
                     x0 = denoised_fn(x0).contiguous().float()
                 if clip_denoised:
@@ -431,6 +450,18 @@ class DSGDiffusion:
                                                  coef.ctypes.data, B, per, stream))
             img = out
             yield img
+
+
+_INPAINT_KEYS = ("inpainting_mask", "inpainted_motion")
+
+
+def _inpaint_mask(mask):
+    """y['inpainting_mask'] as booleans (the reference negates it with `~`: a bool tensor); any non-zero entry of another dtype counts as set."""
+    if L.is_torch(mask):
+        import torch
+        return mask if mask.dtype == torch.bool else mask != 0
+    a = np.asarray(mask)
+    return a if a.dtype == np.bool_ else a != 0
 
 
 def create_gaussian_diffusion(timestep_respacing="", steps=1000, noise_schedule="cosine", library=None):

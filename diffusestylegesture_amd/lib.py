@@ -50,6 +50,7 @@ SYMBOLS = {
     "dsg_set_seed_last": (_I, [_P, _P, _I, _P]),
     "dsg_set_window_cond": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dsg_set_window_cond_cfg": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "dsg_set_inpainting": (_I, [_P, _P, _P, _I, _P]),
     "dsg_forward": (_I, [_P, _P, _P, _P, _I, _P]),
     "dsg_sample": (_I, [_P, C.POINTER(dsg_sample_args), _P, _I, _P]),
     "dsg_sample_multi": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_sample_args), C.POINTER(_P), _I, _P]),

@@ -29,6 +29,7 @@ class DSGDenoiser:
         self._loaded = set()
         self._n_params = 0
         self._source = _clone_of          # keeps the weight owner alive as long as any lane exists
+        self.inpainting = False           # this lane holds an inpainting constraint (set_inpainting)
         if _clone_of is not None:
             h = C.c_void_p()
             self.lib.check(self.lib.cdll.dsg_clone(_clone_of.handle, max_batch, C.byref(h)))
@@ -141,6 +142,23 @@ class DSGDenoiser:
             return
         self.lib.check(self.lib.cdll.dsg_set_window_cond(self.handle, style.p, seed.p, audio.p, mbuf.p, mb, batch,
                                                          int(uncond), stream))
+
+    def set_inpainting(self, mask, motion, batch: int):
+        """y['inpainting_mask'] / y['inpainted_motion'] (gaussian_diffusion.py:317-321), both [batch, njoints, 1, n_poses]: every
+        step of the fused loops replaces the x0 prediction by `motion` where `mask` is set (dsg_set_inpainting).  Sticky for this
+        lane; `set_inpainting(None, None, 0)` switches it off."""
+        if mask is None and motion is None:
+            self.lib.check(self.lib.cdll.dsg_set_inpainting(self.handle, None, None, 0, None))
+            self.inpainting = False
+            return
+        mbuf, vbuf = L.Buf(mask, "uint8"), L.Buf(motion)
+        exp = (batch, self.njoints, self.nfeats, self.cfg.n_poses)
+        for key, b in (("inpainting_mask", mbuf), ("inpainted_motion", vbuf)):
+            if tuple(b.obj.shape) != exp:
+                raise ValueError(f"y['{key}'] shape {tuple(b.obj.shape)} != {exp}")
+        stream = L.current_stream_ptr() if (L.is_torch(mask) or L.is_torch(motion)) else None
+        self.lib.check(self.lib.cdll.dsg_set_inpainting(self.handle, mbuf.p, vbuf.p, batch, stream))
+        self.inpainting = True
 
     def _alloc_out(self, shape, use_torch):
         if use_torch:

@@ -22,6 +22,8 @@
  *        GaussianDiffusion.p_sample_loop / ddim_sample_loop          main/diffusion/gaussian_diffusion.py:608-671, :889-936
  *   dsg_set_window_cond_cfg
  *        ClassifierFreeSampleModel.forward (y['scale'], y['uncond'])   main/model/cfg_sampler.py:8-31
+ *   dsg_set_inpainting
+ *        y['inpainting_mask'] / y['inpainted_motion'] in p_mean_variance   main/diffusion/gaussian_diffusion.py:317-321
  *   dsg_clone / dsg_sample_multi / dsg_set_kernel_set / dsg_get_kernel_set / dsg_recommend_kernel_set / dsg_last_kernel_set
  *        (no reference counterpart: the reference samples one clip at a time, sample.py:418 batch_size = 1; these run
  *         several clips of one GPU concurrently over one copy of the weights -- BASELINE config[3] "one clip per stream")
@@ -161,6 +163,16 @@ int dsg_set_window_cond(dsg_handle* h, const float* style, const float* seed, co
  * (y['scale']).  dsg_forward / dsg_sample are then called with the user batch B as usual. */
 int dsg_set_window_cond_cfg(dsg_handle* h, const float* style, const float* seed, const float* audio,
                             const uint8_t* mask_local, int mask_batch, int B, const float* scale, void* stream);
+
+/* Motion inpainting, p_mean_variance with y['inpainting_mask'] and y['inpainted_motion'] (main/diffusion/gaussian_diffusion.py:317-321):
+ * mask uint8 [B, J, 1, T] (non-zero = keep the given motion), motion fp32 [B, J, 1, T], host or device.  Every step of dsg_sample /
+ * dsg_sample_multi then sets x0 = mask ? motion : x0 -- after the guidance combination (the model is the ClassifierFreeSampleModel), before
+ * clip_denoised and the posterior / DDIM update -- inside the pose-head epilogue; dsg_forward is not affected (MDM.forward does not inpaint).
+ * Sticky for the handle: dsg_set_window_cond* leaves it alone, dsg_sample needs the same B.  mask == NULL && motion == NULL switches it off
+ * (B ignored); exactly one NULL, or B > max_batch: DSG_E_INVALID.  A dsg_clone starts without a constraint; every lane of dsg_sample_multi
+ * has its own.  With const_noise only the noise is shared, not the constraint.  Added without a version step: one more export changes no
+ * existing layout or call, dsg_version() stays 330. */
+int dsg_set_inpainting(dsg_handle* h, const uint8_t* mask, const float* motion, int B, void* stream);
 
 /* x, out: [B, J, 1, T] fp32; t: model timesteps int64[B] (each < train_steps) */
 int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, float* out, int B, void* stream);
