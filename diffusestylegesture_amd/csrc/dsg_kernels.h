@@ -1440,6 +1440,12 @@ __global__ __launch_bounds__(NT) void k_loc(const LocArgs a) {
 //   S^T = K_tile . Q^T  -> lane (query = lane&15) holds 4 keys per key tile: row max/sum = in-lane + 2 shuffles.
 //   O^T = V^T_tile . P^T -> the P values a lane already holds ARE its B fragment (k-permutation: the V^T fragment
 //   is gathered with the same key order), so P never leaves registers.
+// The softmax below (mask + scale, row max, exp, row sum, P fragments) is repeated line for line in k_attn_mid, k_attn_op, k_attn_op_w,
+// k_clip_attn (dsg_fused.h) and k_clip_attn_w (dsg_stream.h).  Moving it into shared __forceinline__ functions was tried and is NOT neutral on the
+// device: the callee is simplified before it is inlined, which (1) reorders the instructions of every caller (same operations, another schedule;
+// k_attn_mid is the batch-1 step) and (2) loses the contraction of `s * scale - mx` through the select into one fma, which the copies get wherever
+// 1 / sqrt(hd) is no power of two (hd = 96, 128: 40 v_fma per lane) -- the poses at the DSG+ widths change in the last bits.  Whoever merges the
+// copies has to spell that fma out first (as the LayerNorm1 tail of k_attn_op does for its two sites) and accept new bits once, for all six together.
 // ---------------------------------------------------------------------------------------------------------
 struct AttnArgs {
     const void* q; const void* k; const void* vt;   // [B][H][Tp][hd], [B][H][Tp][hd], [B][H][hd][Tp]
