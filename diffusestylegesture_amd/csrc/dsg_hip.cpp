@@ -1117,7 +1117,7 @@ static int check_set(const dsg_handle* h, int set) {
     if (set < DSG_KSET_LATENCY || set > DSG_KSET_ROWS) return fail(DSG_E_INVALID, "unknown kernel set");
     if (set == DSG_KSET_LATENCY && h->D > 512) return fail(DSG_E_NOT_IMPLEMENTED, "kernel set LATENCY: latent_dim > 512");
     if ((set == DSG_KSET_STREAM || set == DSG_KSET_ROWS) && !stream_set_ok(h) && !(set == DSG_KSET_ROWS && (rows_w2_ok(h) || rows_wide_ok(h))))
-        return fail(DSG_E_NOT_IMPLEMENTED, "kernel sets STREAM / ROWS: bf16 (ROWS: bf16w2 as well), latent_dim 128 / 256, 4 heads, ff 128 / 1024 only");
+        return fail(DSG_E_NOT_IMPLEMENTED, "kernel sets STREAM / ROWS: bf16, latent_dim 128 / 256, 4 heads, ff 128 / 1024 (ROWS: bf16w2 there as well, and bf16 at the DSG+ widths -- latent_dim 384 / 512, ff 1024) only");
     if (h->prec == DSG_PREC_BF16W2 && ((set > DSG_KSET_TILE && !(set == DSG_KSET_ROWS && rows_w2_ok(h))) || (set == DSG_KSET_LATENCY && h->D > 256)))
         return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2: kernel sets LATENCY (latent_dim <= 256), TILE and ROWS (latent_dim 128 / 256) only");
     return 0;
@@ -1127,10 +1127,8 @@ static int select_kernels(const dsg_handle* h, int B, KernelSel& k) {
     if (set == DSG_KSET_AUTO) set = resolve_auto_set(h, B, 1);
     CHK(check_set(h, set));
     const bool w2 = h->prec == DSG_PREC_BF16W2;
-    if (set == DSG_KSET_ROWS && h->cfgB > 0) {      // (the guided last layer runs ATTN_OP: no bf16w2 form, no k_attn_op_w in ROWS)
-        if (w2) return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2, kernel set ROWS: no fused guidance (TILE has it)");
-        if (rows_wide_ok(h)) return fail(DSG_E_NOT_IMPLEMENTED, "kernel set ROWS at the DSG+ widths: no fused guidance (BLOCK has it)");
-    }
+    // (bf16w2: the guided last layer runs ATTN_OP, which has no bf16w2 form; at the DSG+ widths ROWS has its own guided pose head, k_ws_cfg)
+    if (set == DSG_KSET_ROWS && h->cfgB > 0 && w2) return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2, kernel set ROWS: no fused guidance (TILE has it)");
     k = KernelSel();
     k.set = set;
     const int rows = B * h->ntok, e = h->env_ffn_rt4;
@@ -1181,9 +1179,11 @@ static int select_kernels(const dsg_handle* h, int B, KernelSel& k) {
     return 0;
 }
 // fused guidance: the last layer leaves pre2 to the two-pass pose head k_gemm_cfg, which normalises on read -- where the set's form
-// leaves X0a, that layer runs the round-3 feed-forward kernels behind k_attn_op instead
+// leaves X0a, that layer runs the round-3 feed-forward kernels behind k_attn_op instead.  CLIP_W_FFN (ROWS at the DSG+ widths, where no narrow k_attn_op
+// exists) keeps its form: its guided pose head k_ws_cfg streams the conditional rows and their twins from X0a
+static bool cfg_head_streams(Form f) { return f == Form::CLIP_W_FFN; }
 static Form layer_form(const dsg_handle* h, const KernelSel& k, int l) {
-    return h->cfgB > 0 && l == h->L - 1 && leaves_x0a(k.form) ? Form::ATTN_OP : k.form;
+    return h->cfgB > 0 && l == h->L - 1 && leaves_x0a(k.form) && !cfg_head_streams(k.form) ? Form::ATTN_OP : k.form;
 }
 
 // buffers only one kernel set needs, allocated when a call first runs that set (never inside a graph capture / packet recording:
@@ -1350,6 +1350,18 @@ static int launch_ws(dsg_handle* h, GemmArgs g) {
         if (K == 128) return step_launch<&k_ws<EPI, 8>>(h, grid, dim3(256), g);
     }
     return fail(DSG_E_NOT_IMPLEMENTED, "k_ws: K must be 128 or 256");
+}
+// the guided streaming pose head (k_ws_cfg): one workgroup per (panel, block of 32 conditional rows) + the bookkeeping workgroup; g.M / g.B: the conditional half
+static int launch_ws_cfg(dsg_handle* h, GemmArgs g) {
+    g.KS = 1; g.kb_per_split = g.KBtot;
+    g.inv_ntok = fastdiv_inv(g.ntok); g.inv_hd = fastdiv_inv(g.hd);
+    if (g.NT % 8) return fail(DSG_E_INVALID, "k_ws_cfg: N must be a multiple of 128");
+    const int P = g.NT / 8, K = g.KBtot * 32;
+    g.ws_G = rup(cdiv(g.M, 32), 8);
+    const dim3 grid(ws_grid_x(P, g.ws_G) + 8);
+    if (K == 384) return step_launch<&k_ws_cfg<24>>(h, grid, dim3(256), g);
+    if (K == 512) return step_launch<&k_ws_cfg<32>>(h, grid, dim3(256), g);
+    return fail(DSG_E_NOT_IMPLEMENTED, "k_ws_cfg: K must be 384 or 512");
 }
 // STREAM: LayerNorm once per row (k_ln_frag) -> fragment-major bf16 rows in X1a (free between linear1 and the next attention
 // kernel) [+ fp32 rows in Xn], then the GEMM streams them like linear1.  Packet fences of the state (fence_next) belong to the GEMM.
@@ -1879,20 +1891,29 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
         g.xs_frag = ks.xs_frag ? 1 : 0;
         if (c.inpaint) { g.inp32 = h->inp32; g.inp_mask = h->inp_mask; }      // every pose-head form below reads the same GemmArgs
         h->fence_next = 2;     // the last packet of a step writes the state (state_fences)
-        if (h->cfgB > 0) {      // guidance: one workgroup per CONDITIONAL row tile evaluates the twin rows as well (k_gemm_cfg)
+        if (h->cfgB > 0) {      // guidance: one workgroup per CONDITIONAL row tile evaluates the twin rows as well (k_gemm_cfg; ROWS at the DSG+ widths: k_ws_cfg)
             g.B = h->cfgB; g.M = h->cfgB * ntok; g.MT = cdiv(g.M, 16);
             g.cfgB = h->cfgB; g.cfg_off = h->cfgB * ntok; g.cfg_scale = h->cfg_scale;
             g.KS = 1; g.kb_per_split = g.KBtot; g.inv_ntok = fastdiv_inv(g.ntok); g.inv_hd = fastdiv_inv(g.hd);
-            if (g.NT % 4) return fail(DSG_E_INVALID, "gemm: NT not divisible by the workgroup tile");
-            const dim3 grid(xcd_grid_x(g.NT / 4), g.MT + 1, 1);
-            // (bf16w2: 16 k-blocks of two-register weight + activation fragments do not fit -- two batches of 8, as in launch_gemm_w; round-5 advisor)
-            bool done = false;
-            if constexpr (!P::W2) {
-                if (pick_ch(g.KBtot) == 16) { CHK((step_launch<&k_gemm_cfg<P, 16>>(h, grid, dim3(256), g))); done = true; }
+            if (cfg_head_streams(ks.form)) {      // the last layer kept the set's form: its LayerNorm2 rows (+ twins) lie fragment-major in X0a (k_ws_cfg)
+                if constexpr (sizeof(typename P::elem) == 2 && !P::W2) {
+                    g.X = nullptr; g.ln_g = nullptr; g.ln_b = nullptr; g.A = h->X0a; g.lda = D; g.a_frag = 1;
+                    CHK(launch_ws_cfg(h, g));
+                } else {
+                    return fail(DSG_E_NOT_IMPLEMENTED, "guided pose head on the rows in X0a: bf16 only");
+                }
+            } else {
+                if (g.NT % 4) return fail(DSG_E_INVALID, "gemm: NT not divisible by the workgroup tile");
+                const dim3 grid(xcd_grid_x(g.NT / 4), g.MT + 1, 1);
+                // (bf16w2: 16 k-blocks of two-register weight + activation fragments do not fit -- two batches of 8, as in launch_gemm_w; round-5 advisor)
+                bool done = false;
+                if constexpr (!P::W2) {
+                    if (pick_ch(g.KBtot) == 16) { CHK((step_launch<&k_gemm_cfg<P, 16>>(h, grid, dim3(256), g))); done = true; }
+                }
+                if (!done && pick_ch(g.KBtot) == 12) { CHK((step_launch<&k_gemm_cfg<P, 12>>(h, grid, dim3(256), g))); done = true; }
+                if (!done) CHK((step_launch<&k_gemm_cfg<P>>(h, grid, dim3(256), g)));
             }
-            if (!done && pick_ch(g.KBtot) == 12) { CHK((step_launch<&k_gemm_cfg<P, 12>>(h, grid, dim3(256), g))); done = true; }
-            if (!done) CHK((step_launch<&k_gemm_cfg<P>>(h, grid, dim3(256), g)));
-        } else if (leaves_x0a(ks.form)) {      // the last layer left its rows normalised in X0a (cfgB == 0 here: layer_form)
+        } else if (leaves_x0a(ks.form)) {      // the last layer left its rows normalised in X0a (no guidance here)
             g.X = nullptr; g.ln_g = nullptr; g.ln_b = nullptr; g.A = h->X0a; g.lda = D; g.a_frag = 1;
             CHK((launch_gemm_w<P, PRO_DIRECT, EPI_OUT>(h, g, ks)));
         } else {

@@ -126,10 +126,15 @@ __global__ __launch_bounds__(256) void k_ln_frag(const GemmArgs g) {
 __host__ __device__ constexpr int ws_stage_bytes(int epi, int bm) {
     return epi == EPI_QKV ? 128 * (bm + 4) * 2 : (epi == EPI_OUT ? 4 * 32 * 36 * 4 : 0);
 }
-template <int EPI, int KD16, bool SW, bool ONE = false>       // SW: D[feature][token] (Q / K, linear1, pose head); !SW: D[token][feature] (V^T)
+// CFG (the pose head under classifier-free guidance, k_ws_cfg): the 64-row buffer holds 32 CONDITIONAL rows (row tiles 0 - 1) and their 32 unconditional twins
+//      (tiles 2 - 3), so the MFMA loop below is the unguided one -- the waves wm = 0 / 1, which hold the same 64 columns of the panel, form the conditional / the twin
+//      accumulator -- and the two meet in the epilogue's LDS stage
+template <int EPI, int KD16, bool SW, bool ONE = false, bool CFG = false>       // SW: D[feature][token] (Q / K, linear1, pose head); !SW: D[token][feature] (V^T)
 __device__ __forceinline__ void ws_body(const GemmArgs& g, const WsId id, char* lds) {     // ONE: one row block per workgroup (G >= MB), one buffer
     typedef PBF16 P;
     constexpr int K = 16 * KD16, KB = K / 32, BM = 64;
+    constexpr int BMO = CFG ? BM / 2 : BM;                         // rows of the output a block covers
+    static_assert(!CFG || (EPI == EPI_OUT && ONE && SW), "guidance lives in the pose head");
     constexpr int ABYTES = BM * K * 2;
     // epilogue staging (V^T transposition, pose-head tile transposition): the retired activation buffer when it is large enough
     // (K = 256), else its own region behind the two buffers (K = 128: 128 x 68 x 2 = 17408 B / 4 x 32 x 36 x 4 = 18432 B > 16384 --
@@ -137,7 +142,7 @@ __device__ __forceinline__ void ws_body(const GemmArgs& g, const WsId id, char* 
     constexpr int STAGE = ws_stage_bytes(EPI, BM);
     constexpr bool STAGE_IN_A = STAGE <= ABYTES;
     constexpr int NBUF = ONE ? 1 : 2;
-    const int G = g.ws_G, MB = (g.M + BM - 1) / BM;
+    const int G = g.ws_G, MB = (g.M + BMO - 1) / BMO;
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, lhi = lane >> 5;
 
@@ -164,12 +169,23 @@ __device__ __forceinline__ void ws_body(const GemmArgs& g, const WsId id, char* 
     if constexpr (!W_PER_BLOCK) load_w(0);
     // activation block mb -> LDS buffer (fragment-major operand: one contiguous 4 KB-tiles x KB span)
     auto issue_a = [&](int mb, int buf) {
-        const char* src = (const char*)g.A + (size_t)mb * (BM * K * 2);
+        const char* src = (const char*)g.A + (size_t)mb * (BMO * K * 2);
         char* dst = lds + buf * ABYTES;
 #pragma unroll
-        for (int c = 0; c < (BM * K * 2) / 4096; ++c) {
+        for (int c = 0; c < (BMO * K * 2) / 4096; ++c) {
             const int chunk = c * 4 + wave;                        // 1 KB per wave instruction
             glds16(src + chunk * 1024 + lane * 16, dst + chunk * 1024, lane);
+        }
+        if constexpr (CFG) {
+            // the twins lie cfg_off = cfgB ntok rows further down: a multiple of ntok, not of 16 -- the twin of a row sits in another row tile at another in-tile
+            // row, so a lane fetches the 16 bytes of ITS row (as k_clip_attn_w does for a clip's rows).  Past the last row of the batch: that row (never used)
+            const int m_last = g.M + g.cfg_off - 1;
+#pragma unroll
+            for (int c = 0; c < (BMO * K * 2) / 4096; ++c) {
+                const int chunk = c * 4 + wave, rt = chunk / KB, kb = chunk - rt * KB;      // one k-block of one twin row tile
+                const int m = min(mb * BMO + g.cfg_off + rt * 16 + (lane & 15), m_last);
+                glds16((const char*)g.A + (size_t)qk_off<P>(m, kb * P::KB + P::E * (lane >> 4), KB) * sizeof(typename P::elem), dst + (2 * KB + chunk) * 1024, lane);
+            }
         }
     };
     int cur = 0;
@@ -184,7 +200,7 @@ __device__ __forceinline__ void ws_body(const GemmArgs& g, const WsId id, char* 
     }
 #pragma unroll 1
     for (int mb = id.grp; mb < MB; mb += G) {
-        const int m0 = mb * BM;
+        const int m0 = mb * BMO;
         glds_wait();
         DSG_LDS_BARRIER();             // the block has landed for every wave; every wave is done with the other buffer
         if constexpr (ONE) DSG_TL_MARK(0);      // (pose head, one block per workgroup) the activation block is in LDS
@@ -211,7 +227,7 @@ __device__ __forceinline__ void ws_body(const GemmArgs& g, const WsId id, char* 
                 else acc[ct] = mma32(a, wf[ct][s], acc[ct]);                   // 4 consecutive tokens per lane
             }
         }
-        const int mw = m0 + 32 * wm;
+        const int mw = CFG ? m0 : m0 + 32 * wm;
         if constexpr (EPI == EPI_QKV && !SW) {
             // ---- V^T: the block goes through the retired activation buffer and out in aligned token groups (vt_store_block)
             constexpr int SP = BM + 4;                             // 136-byte feature pitch: 8-byte aligned quads
@@ -246,6 +262,34 @@ __device__ __forceinline__ void ws_body(const GemmArgs& g, const WsId id, char* 
             DSG_LDS_BARRIER();                                     // every wave is done reading the activation block
             if constexpr (ONE) DSG_TL_MARK(2);
             const int tok = lane >> 3, quad = lane & 7;
+            if constexpr (CFG) {
+                // every wave leaves BOTH its column tiles in the stage (slot 2 wave + ct); then wave (wm, wn) finishes column tile ct = wm of the column half wn on
+                // the conditional tile of wave (0, wn) and the twin tile of wave (1, wn): half the unguided epilogue per wave, no second accumulator in registers
+                float* const all = (float*)(lds + cur * ABYTES);
+                static_assert(STAGE_IN_A && 8 * 32 * TP * 4 <= ABYTES, "guided pose-head stage");
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        *(f32x4*)(all + (2 * wave + ct) * (32 * TP) + l31 * TP + 8 * q + 4 * lhi) = (f32x4){acc[ct][4 * q], acc[ct][4 * q + 1], acc[ct][4 * q + 2], acc[ct][4 * q + 3]};
+                DSG_LDS_BARRIER();
+                const float* const sc = all + (2 * wn + wm) * (32 * TP), * const su = all + (2 * (2 + wn) + wm) * (32 * TP);
+                const int n0 = id.panel * 128 + wn * 64 + wm * 32;
+                f32x4 xt[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) xt[i] = out_xt_load<P>(g, mw + tok + 8 * i, n0 + 4 * quad);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    TileOps ops;
+                    const int t = tok + 8 * i;
+                    const f32x4 v = *(const f32x4*)(sc + t * TP + 4 * quad), vu = *(const f32x4*)(su + t * TP + 4 * quad);
+                    gemm_prefetch_tile<P, EPI>(g, mw + t, n0 + 4 * quad, 0, 0, step, ops, &xt[i]);
+                    gemm_epilogue_tile<P, EPI>(g, mw + t, n0 + 4 * quad, 0, 0, 0, true, v, ops, k1, k2, k3, k4, k5, vu);
+                }
+                DSG_TL_MARK(3);
+                cur ^= 1;
+                continue;
+            }
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
 #pragma unroll
@@ -327,6 +371,29 @@ __global__ __launch_bounds__(256, KD16 > 16 ? 1 : (ONE ? 4 : 2)) void k_ws(const
     } else {
         ws_body<EPI, KD16, true, ONE>(g, id, lds);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_ws_cfg: the streaming pose head under classifier-free guidance (ROWS at the DSG+ widths: the last layer keeps Form::CLIP_W_FFN, its LayerNorm2 rows lie
+// fragment-major in X0a -- conditional rows, then their twins cfg_off rows further down).  One workgroup per (panel, block of 32 CONDITIONAL rows); see ws_body<CFG>.
+// g.M / g.B count the conditional rows / elements (as for k_gemm_cfg); the epilogue is the shared one (gemm_epilogue_tile: guidance combination, inpainting,
+// clamp, sampler update, both halves of the state).  Per conditional row the k sums are those of k_ws<EPI_OUT> on that row and on its twin.
+// ---------------------------------------------------------------------------------------------------------
+template <int KD16>
+__global__ __launch_bounds__(256, 1) void k_ws_cfg(const GemmArgs g) {
+    DSG_TL_SCOPE();
+    typedef PBF16 P;
+    static_assert(KD16 == 24 || KD16 == 32, "the DSG+ widths: K = 384 / 512");
+    __shared__ __attribute__((aligned(16))) char lds[64 * 16 * KD16 * 2];
+    preload_kernargs(g);
+    const int n_panels = g.NT >> 3;
+    const WsId id = ws_id(n_panels, g.ws_G);
+    if (!id.work) {
+        if (g.ctl && (int)blockIdx.x == ws_grid_x(n_panels, g.ws_G) && threadIdx.x == 0 && g.out_mode != OUT_FORWARD) step_advance_A<P>(g.ctl, g.st, g.n_tab);
+        return;
+    }
+    if (id.grp >= (g.M + 31) / 32) return;
+    ws_body<EPI_OUT, KD16, true, true, true>(g, id, lds);
 }
 
 // ---------------------------------------------------------------------------------------------------------

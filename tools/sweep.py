@@ -5,8 +5,9 @@ THIS process on the same GPU, same weights, same conditioning and noise, and pri
     python tools/sweep.py --spec block:1x16,stream:1x16,block:4x4,stream:4x4 --steps 100 [--reps 3] [--sampler ddpm|ddim50]
                           [--config zeggs] [--precision bf16]
 
-spec = <kernel set>:<lanes>x<batch per lane>[:uc0|uc1|uc2][:hip]      (kernel set: auto / latency / tile / block / stream;
-       uc = DSG_UC for the handles of this spec; hip = HIP launches instead of AQL packets -- what rocprofv3 can see)
+spec = <kernel set>:<lanes>x<batch per lane>[:uc0|uc1|uc2][:hip][:cfg]      (kernel set: auto / latency / tile / block / stream / rows;
+       uc = DSG_UC for the handles of this spec; hip = HIP launches instead of AQL packets -- what rocprofv3 can see;
+       cfg = classifier-free guidance: every clip brings its unconditional twin, handles of 2 x batch rows, scales 0.5 .. 2.5)
 Per spec: us per denoising step (time in which ALL clips of the spec advance one step; best and median of --reps), the
 frames/s that corresponds to for 320-frame clips of 4 x 1000 steps, which path / kernel set really ran, and the rel-L2
 distance of the samples to those of the FIRST spec with the same lanes x batch (a cross-check of the kernel sets against
@@ -23,7 +24,7 @@ import torch
 
 from diffusestylegesture_amd import config as C
 from diffusestylegesture_amd.diffusion import create_gaussian_diffusion
-from diffusestylegesture_amd.model import DSGDenoiser
+from diffusestylegesture_amd.model import ClassifierFreeSampleModel, DSGDenoiser
 from diffusestylegesture_amd.synth import synth_state_dict, synth_window_inputs
 
 p = argparse.ArgumentParser()
@@ -50,20 +51,25 @@ for spec in a.spec.split(","):
             os.environ["DSG_UC"] = o[2:]
         elif o == "hip":
             os.environ["DSG_AQL"] = "0"
-    m = DSGDenoiser(cfg, precision=a.precision, max_batch=b, device=0).set_kernel_set(kset)
+    guided = "cfg" in parts[2:]
+    m = DSGDenoiser(cfg, precision=a.precision, max_batch=2 * b if guided else b, device=0).set_kernel_set(kset)
     m.load_state_dict(sd)
     lanes = [m] + [m.clone() for _ in range(nl - 1)]
+    models = [ClassifierFreeSampleModel(ln) for ln in lanes] if guided else lanes
     shape = (b, cfg.njoints, 1, cfg.n_poses)
     ys = [{"y": {k: torch.from_numpy(v).cuda() for k, v in synth_window_inputs(cfg, b, window=1, clip0=ln * b, seed_pose_scale=0.1).items()}}
           for ln in range(nl)]
+    if guided:
+        for yy in ys:
+            yy["y"]["scale"] = np.linspace(0.5, 2.5, b).astype(np.float32)
     us = []
     for r in range(a.reps + 1):          # the first pass warms up (queues, code objects, weights in L2)
         d.manual_seed(1, 0)
         if nl > 1:
-            outs = d.p_sample_loop_multi(lanes, shape, ys, seeds=[1] * nl, stream_ids=list(range(nl)), skip_timesteps=skip, ddim=a.sampler == "ddim50")
+            outs = d.p_sample_loop_multi(models, shape, ys, seeds=[1] * nl, stream_ids=list(range(nl)), skip_timesteps=skip, ddim=a.sampler == "ddim50")
         else:
             fn = d.ddim_sample_loop if a.sampler == "ddim50" else d.p_sample_loop
-            outs = [fn(m, shape, clip_denoised=False, model_kwargs=ys[0], skip_timesteps=skip)]
+            outs = [fn(models[0], shape, clip_denoised=False, model_kwargs=ys[0], skip_timesteps=skip)]
         torch.cuda.synchronize()
         if r:
             us.append(max(1000.0 * ln.last_sample_ms()[0] / max(ln.last_sample_ms()[1], 1) for ln in lanes))
