@@ -156,6 +156,10 @@ struct dsg_handle {
     int cfgB = 0; float* cfg_scale = nullptr;
     // inpainting constraint (dsg_set_inpainting): inpB user batch elements in the state's layout [inpB][T][Jp]; 0 = off.  Allocated on first use
     int inpB = 0; float* inp32 = nullptr; unsigned char *inp_mask = nullptr, *inp_stage = nullptr;
+    // window hand-off of dsg_sample_clip (k_window_handoff): the previous window's last S frames [B][S][J], two copies used in turn (a hand-off reads
+    // one and writes the other), and the stitched clip when the caller's `out` is host memory.  Allocated on first use
+    float* clip_tail[2] = {nullptr, nullptr}; float* clip_out = nullptr; size_t clip_out_cap = 0;
+    bool clip_timing = false; double clip_ms = 0.0;      // the last sampling call was dsg_sample_clip: dsg_last_sample_ms reports the sum over its windows
     int last_path = -1;                  // submission path of the last dsg_sample: 0 HIP launches, 1 AQL packets, 2 hipGraph replay
     bool last_nofence = false;           // ... and whether its packets went without fences
     int kset_req = DSG_KSET_AUTO;        // dsg_set_kernel_set: the kernel set every step of this handle runs (AUTO: by batch, select_kernels)
@@ -860,7 +864,7 @@ static int cond_rows(dsg_handle* h, const float* style, const float* seed, const
     float* cvec = h->cvec + (size_t)row0 * D;
     float* Cf = h->Cf + (size_t)row0 * T * D;
     CHK(upload(h, c_style, style, (size_t)B * sdi * sizeof(float)));
-    if (S > 0) CHK(upload(h, c_seed, seed, (size_t)B * J * S * sizeof(float)));
+    if (S > 0 && seed != c_seed) CHK(upload(h, c_seed, seed, (size_t)B * J * S * sizeof(float)));      // (dsg_sample_clip: k_window_handoff wrote it in place)
     CHK(upload(h, c_audio, audio, (size_t)B * h->Ta * As * sizeof(float)));
     const int sdo = h->cfg.variant == 3 ? 64 : D;
     if (uncond) {       // mask_cond(force_mask=True): zeros AFTER the style linear (mdm.py:156-159, :180)
@@ -2473,55 +2477,23 @@ static int sample_run_hip(dsg_handle* h, const dsg_sample_args* a, SampleJob& jo
     return 0;
 }
 
-static int sample_finish(dsg_handle* h, float* out, void* stream, SampleJob& job) {
-    const size_t n = (size_t)job.B * h->J * h->T;
-    HP_LAP(7);                               // (the step loop itself)
-    HIPCHK(hipEventRecord(h->ev_t1, h->stream));
-    h->last_steps = job.n_run; h->timing_valid = true;
-    h->last_kset = job.c.ks.set;
-    CHK(launch_x_out(h, h->fwd_out, job.B));
-    CHK(from_dev(h, out, h->fwd_out, n));
-    CHK(order_before(h, stream));
-    HP_LAP(8);
-    return 0;
-}
-
-extern "C" int dsg_sample(dsg_handle* h, const dsg_sample_args* a, float* out, int B, void* stream) {
-    if (!h || !a || !out) return fail(DSG_E_INVALID, "dsg_sample: null argument");
-    SampleJob job;
-    CHK(sample_prepare(h, a, B, stream, job));
+// The step loops of n prepared lanes, run to their end: one lane as dsg_sample always ran it (its own AQL queue, or HIP launches / graph
+// replays), several interleaved (AQL: one queue per lane, the steps dealt round-robin by this host thread; HIP launches: step s of every
+// lane, then s + 1).  Shared by dsg_sample, dsg_sample_multi and the windows of dsg_sample_clip.
+static int run_lanes(dsg_handle** hs, int n, const dsg_sample_args* args, SampleJob* jobs) {
+    if (n == 1) {
+        dsg_handle* h = hs[0];
+        SampleJob& job = jobs[0];
 #ifndef DSG_EMU
-    if (job.aql) {
-        if (!dsg_aql::run(h->aql, job.n_run, 60.0 + 0.01 * job.n_run)) return fail(DSG_E_RUNTIME, "AQL run: " + h->aql.err);
-        job.done = job.n_run;
-        h->aql_timing = true; h->aql_ms = h->aql.last_ms;
-        h->last_path = 1; h->last_nofence = h->aql.nofence;
-    }
+        if (job.aql) {
+            if (!dsg_aql::run(h->aql, job.n_run, 60.0 + 0.01 * job.n_run)) return fail(DSG_E_RUNTIME, "AQL run: " + h->aql.err);
+            job.done = job.n_run;
+            h->aql_timing = true; h->aql_ms = h->aql.last_ms;
+            h->last_path = 1; h->last_nofence = h->aql.nofence;
+        }
 #endif
-    CHK(sample_run_hip(h, a, job));
-    return sample_finish(h, out, stream, job);
-}
-
-// n lanes (handles of ONE device, normally a handle and its clones), one independent sampling call each, advanced
-// concurrently.  With the AQL submission every lane has its own HSA queue and the host thread deals the steps round-robin (the
-// queues' dependent packet chains overlap on the GPU); with HIP launches the lanes' streams are fed step by step.  Every lane
-// runs the kernel set ITS handle selects (dsg_set_kernel_set / the batch): the call changes nothing about the arithmetic, so
-// lane i's sample is bit-identical to dsg_sample(lanes[i], &args[i], ...) on its own.
-extern "C" int dsg_sample_multi(dsg_handle** hs, int n, const dsg_sample_args* args, float** outs, int B, void* stream) {
-    if (!hs || !args || !outs || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_multi: bad argument");
-    for (int i = 0; i < n; ++i) {
-        if (!hs[i] || !outs[i]) return fail(DSG_E_INVALID, "dsg_sample_multi: null handle / output");
-        for (int j = 0; j < i; ++j) if (hs[j] == hs[i]) return fail(DSG_E_INVALID, "dsg_sample_multi: a handle appears twice");
-        if (hs[i]->cfg.device != hs[0]->cfg.device) return fail(DSG_E_INVALID, "dsg_sample_multi: lanes must live on one device");
+        return sample_run_hip(h, &args[0], job);
     }
-    if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_multi: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
-    std::vector<SampleJob> jobs(n);
-    struct LanesNow {          // how many lanes share the GPU during this call (select_kernels: block shape of k_ffn; never the arithmetic)
-        dsg_handle** hs; int n;
-        LanesNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) hs[i]->lanes_now = n; }
-        ~LanesNow() { for (int i = 0; i < n; ++i) hs[i]->lanes_now = 1; }
-    } lanes_now(hs, n);
-    for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &args[i], B, stream, jobs[i]));
     bool all_aql = true;
     for (int i = 0; i < n; ++i) all_aql = all_aql && jobs[i].aql;
 #ifndef DSG_EMU
@@ -2551,11 +2523,167 @@ extern "C" int dsg_sample_multi(dsg_handle** hs, int n, const dsg_sample_args* a
             }
         }
     }
+    for (int i = 0; i < n; ++i) CHK(sample_run_hip(hs[i], &args[i], jobs[i]));      // whatever is left (graphs, dump points); nothing after AQL
+    return 0;
+}
+
+static int sample_finish(dsg_handle* h, float* out, void* stream, SampleJob& job) {
+    const size_t n = (size_t)job.B * h->J * h->T;
+    HP_LAP(7);                               // (the step loop itself)
+    HIPCHK(hipEventRecord(h->ev_t1, h->stream));
+    h->last_steps = job.n_run; h->timing_valid = true; h->clip_timing = false;
+    h->last_kset = job.c.ks.set;
+    CHK(launch_x_out(h, h->fwd_out, job.B));
+    CHK(from_dev(h, out, h->fwd_out, n));
+    CHK(order_before(h, stream));
+    HP_LAP(8);
+    return 0;
+}
+
+extern "C" int dsg_sample(dsg_handle* h, const dsg_sample_args* a, float* out, int B, void* stream) {
+    if (!h || !a || !out) return fail(DSG_E_INVALID, "dsg_sample: null argument");
+    SampleJob job;
+    CHK(sample_prepare(h, a, B, stream, job));
+    CHK(run_lanes(&h, 1, a, &job));
+    return sample_finish(h, out, stream, job);
+}
+
+// n lanes (handles of ONE device, normally a handle and its clones), one independent sampling call each, advanced
+// concurrently.  With the AQL submission every lane has its own HSA queue and the host thread deals the steps round-robin (the
+// queues' dependent packet chains overlap on the GPU); with HIP launches the lanes' streams are fed step by step.  Every lane
+// runs the kernel set ITS handle selects (dsg_set_kernel_set / the batch): the call changes nothing about the arithmetic, so
+// lane i's sample is bit-identical to dsg_sample(lanes[i], &args[i], ...) on its own.
+extern "C" int dsg_sample_multi(dsg_handle** hs, int n, const dsg_sample_args* args, float** outs, int B, void* stream) {
+    if (!hs || !args || !outs || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_multi: bad argument");
     for (int i = 0; i < n; ++i) {
-        CHK(sample_run_hip(hs[i], &args[i], jobs[i]));      // whatever is left (graphs, dump points); nothing after AQL
-        CHK(sample_finish(hs[i], outs[i], stream, jobs[i]));
+        if (!hs[i] || !outs[i]) return fail(DSG_E_INVALID, "dsg_sample_multi: null handle / output");
+        for (int j = 0; j < i; ++j) if (hs[j] == hs[i]) return fail(DSG_E_INVALID, "dsg_sample_multi: a handle appears twice");
+        if (hs[i]->cfg.device != hs[0]->cfg.device) return fail(DSG_E_INVALID, "dsg_sample_multi: lanes must live on one device");
+    }
+    if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_multi: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
+    std::vector<SampleJob> jobs(n);
+    struct LanesNow {          // how many lanes share the GPU during this call (select_kernels: block shape of k_ffn; never the arithmetic)
+        dsg_handle** hs; int n;
+        LanesNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) hs[i]->lanes_now = n; }
+        ~LanesNow() { for (int i = 0; i < n; ++i) hs[i]->lanes_now = 1; }
+    } lanes_now(hs, n);
+    for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &args[i], B, stream, jobs[i]));
+    CHK(run_lanes(hs, n, args, jobs.data()));
+    for (int i = 0; i < n; ++i) CHK(sample_finish(hs[i], outs[i], stream, jobs[i]));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// dsg_sample_clip / dsg_sample_clip_multi: all K windows of the B clips of every lane in one call -- the window loops of
+// main/mydiffusion_zeggs/sample.py:236-296 and BEAT-TWH-main/mydiffusion_beat_twh/sample.py:98-192.  Per window: the conditioning
+// (set_window_cond, y['seed'] = the tail the previous hand-off left in c_seed), sample_prepare + the step loop exactly as dsg_sample
+// / dsg_sample_multi issue them, then k_window_handoff in place of k_x_out + the copy to the caller.  One copy of the stitched clip
+// at the end.  Bit-identical to the K calls + the host stitching of sample.py: the same kernels, draws and fp32 operations.
+// ---------------------------------------------------------------------------------------------------------
+static int launch_handoff(dsg_handle* h, float* clip_out, int B, int n_out, int c, int K, int root_shift, int keep_last_tail) {
+    HandoffArgs a;
+    a.xs32 = h->xs32; a.tail_in = h->clip_tail[(c + 1) & 1]; a.tail_out = h->clip_tail[c & 1]; a.c_seed = h->c_seed; a.clip_out = clip_out;
+    a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S; a.n_out = n_out; a.c = c;
+    a.root_shift = root_shift ? 1 : 0; a.is_first = c == 0 ? 1 : 0; a.is_last = c == K - 1 ? 1 : 0; a.keep_last_tail = keep_last_tail ? 1 : 0;
+    const size_t n = (size_t)B * h->T * (h->Jp / 4);
+    hipLaunchKernelGGL(k_window_handoff, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const float* const* seed0s, const float* const* audios,
+                       const uint8_t* mask_local, int mask_batch, const float* const* scales, const dsg_sample_args* args, int K,
+                       int root_shift, int keep_last_tail, float** outs, int B, void* stream) {
+    if (!hs || !styles || !audios || !args || !outs || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_clip: bad argument");
+    if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_clip_multi: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
+    if (K < 1) return fail(DSG_E_INVALID, "dsg_sample_clip: K < 1");
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        if (!h || !outs[i] || !styles[i] || !audios[i]) return fail(DSG_E_INVALID, "dsg_sample_clip: null handle / style / audio / output");
+        for (int j = 0; j < i; ++j) if (hs[j] == h) return fail(DSG_E_INVALID, "dsg_sample_clip_multi: a handle appears twice");
+        if (h->cfg.device != hs[0]->cfg.device) return fail(DSG_E_INVALID, "dsg_sample_clip_multi: lanes must live on one device");
+        if (h->J != hs[0]->J || h->T != hs[0]->T || h->S != hs[0]->S) return fail(DSG_E_INVALID, "dsg_sample_clip_multi: lanes of one model");
+        if (!h->finalized) return fail(DSG_E_STATE, "dsg_sample_clip before dsg_finalize_weights");
+        if (h->sched.n == 0) return fail(DSG_E_STATE, "dsg_sample_clip before dsg_set_schedule");
+        if (h->S <= 0 || 2 * h->S >= h->T) return fail(DSG_E_INVALID, "dsg_sample_clip: the window hand-off needs 0 < 2 * n_seed < n_poses");
+        if (h->inpB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip: an inpainting constraint is per window (dsg_set_inpainting(h, NULL, NULL, ...) first)");
+        const dsg_sample_args& a = args[i];
+        if (a.step_noise || a.n_dump || a.first_step || a.max_steps || a.init_noise || a.init_image)
+            return fail(DSG_E_INVALID, "dsg_sample_clip: step_noise / dump_steps / first_step / max_steps / init_noise / init_image are per window");
+        if (a.skip_timesteps < 0 || a.skip_timesteps >= h->sched.n) return fail(DSG_E_INVALID, "skip_timesteps out of range");
+        if (a.skip_timesteps != args[0].skip_timesteps || h->sched.n != hs[0]->sched.n) return fail(DSG_E_INVALID, "dsg_sample_clip_multi: one step count for every lane");
+        const int rows = (scales && scales[i]) ? 2 * B : B;
+        if (B <= 0 || rows > h->Bmax) return fail(DSG_E_INVALID, rows > B ? "classifier-free guidance needs max_batch >= 2 * batch" : "batch exceeds max_batch");
+    }
+    const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J;
+    const int n_out = keep_last_tail ? K * (T - S) : K * (T - S) - S;
+    const size_t n_clip = (size_t)B * n_out * J, n_tail = (size_t)B * J * S;
+    const int n_run = hs[0]->sched.n - args[0].skip_timesteps;
+    HIPCHK(hipSetDevice(hs[0]->cfg.device));
+    std::vector<float*> clip(n);
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        for (int k = 0; k < 2; ++k)
+            if (!h->clip_tail[k]) CHK(dalloc(h, &h->clip_tail[k], (size_t)h->Bmax * J * S));
+        if (is_device_ptr(outs[i])) clip[i] = outs[i];      // the hand-off writes the caller's tensor itself
+        else {
+            if (n_clip > h->clip_out_cap) { CHK(dalloc(h, &h->clip_out, n_clip, false)); h->clip_out_cap = n_clip; }
+            clip[i] = h->clip_out;
+        }
+        // y['seed'] of window 0: the caller's, or zeros (sample.py:241) -- in place, where the hand-off leaves the later ones
+        CHK(order_after(h, stream));
+        if (seed0s && seed0s[i]) CHK(upload(h, h->c_seed, seed0s[i], n_tail * sizeof(float)));
+        else HIPCHK(hipMemsetAsync(h->c_seed, 0, n_tail * sizeof(float), h->stream));
+        h->clip_ms = 0.0;
+    }
+    std::vector<SampleJob> jobs(n);
+    std::vector<dsg_sample_args> wargs(args, args + n);
+    struct LanesNow {          // (as in dsg_sample_multi)
+        dsg_handle** hs; int n;
+        LanesNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) hs[i]->lanes_now = n; }
+        ~LanesNow() { for (int i = 0; i < n; ++i) hs[i]->lanes_now = 1; }
+    } lanes_now(hs, n);
+    for (int c = 0; c < K; ++c) {
+        for (int i = 0; i < n; ++i) {
+            dsg_handle* h = hs[i];
+            const float* audio_c = audios[i] + (size_t)c * B * h->Ta * h->As;
+            CHK(set_window_cond(h, styles[i], h->c_seed, audio_c, mask_local, mask_batch, B, 0, scales ? scales[i] : nullptr, stream));
+            wargs[i].draw_base = args[i].draw_base + (uint32_t)c * (uint32_t)(1 + n_run);      // what K consecutive dsg_sample calls consume
+        }
+        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, jobs[i]));
+        CHK(run_lanes(hs, n, wargs.data(), jobs.data()));
+        for (int i = 0; i < n; ++i) {
+            dsg_handle* h = hs[i];
+            HIPCHK(hipEventRecord(h->ev_t1, h->stream));
+            if (h->aql_timing) h->clip_ms += h->aql_ms;
+            else {
+                float ms = 0.f;
+                HIPCHK(hipEventSynchronize(h->ev_t1));
+                HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+                h->clip_ms += ms;
+            }
+            CHK(launch_handoff(h, clip[i], B, n_out, c, K, root_shift, keep_last_tail));
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        h->last_steps = K * n_run; h->timing_valid = true; h->clip_timing = true;
+        h->last_kset = jobs[i].c.ks.set;
+        if (clip[i] != outs[i]) CHK(from_dev(h, outs[i], clip[i], n_clip));
+        CHK(order_before(h, stream));
     }
     return 0;
+}
+extern "C" int dsg_sample_clip(dsg_handle* h, const float* style, const float* seed0, const float* audio, const uint8_t* mask_local,
+                               int mask_batch, const float* scale, const dsg_sample_args* args, int K, int root_shift,
+                               int keep_last_tail, float* out, int B, void* stream) {
+    return sample_clip(&h, 1, &style, &seed0, &audio, mask_local, mask_batch, &scale, args, K, root_shift, keep_last_tail, &out, B, stream);
+}
+extern "C" int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* const* styles, const float* const* seed0s,
+                                     const float* const* audios, const uint8_t* mask_local, int mask_batch, const float* const* scales,
+                                     const dsg_sample_args* args, int K, int root_shift, int keep_last_tail, float** outs, int B,
+                                     void* stream) {
+    return sample_clip(lanes, n, styles, seed0s, audios, mask_local, mask_batch, scales, args, K, root_shift, keep_last_tail, outs, B, stream);
 }
 
 extern "C" int dsg_sync(dsg_handle* h) {
@@ -2568,7 +2696,8 @@ extern "C" int dsg_last_sample_ms(dsg_handle* h, float* ms, int* n_steps) {
     if (!h || !ms) return fail(DSG_E_INVALID, "null argument");
     if (!h->timing_valid) return fail(DSG_E_STATE, "no dsg_sample has run");
     HIPCHK(hipEventSynchronize(h->ev_t1));
-    if (h->aql_timing) *ms = (float)h->aql_ms;      // AQL path: host clock from the first doorbell to the completion signal
+    if (h->clip_timing) *ms = (float)h->clip_ms;    // dsg_sample_clip: the sum over its windows
+    else if (h->aql_timing) *ms = (float)h->aql_ms;      // AQL path: host clock from the first doorbell to the completion signal
     else HIPCHK(hipEventElapsedTime(ms, h->ev_t0, h->ev_t1));
     if (n_steps) *n_steps = h->last_steps;
     return 0;

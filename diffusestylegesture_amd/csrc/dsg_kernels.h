@@ -1658,6 +1658,59 @@ __global__ void k_x_out(const float* xs32, float* out, int B, int J, int Jp, int
         out[i] = xs32[((size_t)b * T + f) * Jp + j];
     }
 }
+// Window hand-off of a clip sampled inside the library (dsg_sample_clip): what the host loop of sample.py does between two windows
+// (main/mydiffusion_zeggs/sample.py:269-289, BEAT-TWH-main/mydiffusion_beat_twh/sample.py:150-160), on the state as it stands after
+// the step loop.  The state xs32 [B][T][Jp] is frame-major like the stitched clip [B][n_out][J], so this is a row copy with three
+// shifted channels and one blended frame: one thread per feature quad of a (clip, frame) row, one 16-byte load of it.
+//   !is_first && root_shift:  delta[j] = s[0][j] - tail[0][j],  s[f][j] -= delta[j]   (j < 3, every f; two roundings, as written on the host)
+//   !is_first:                s[0][j] = tail[0][j] * 0.5f + s[0][j] * 0.5f            (both products exact: contraction changes nothing)
+// Frames [0, T - S) go to clip row c * (T - S) + f - S (negative: not written = the first S frames of window 0); the last window also
+// writes its S closing frames when keep_last_tail.  The last S frames (after the shift) become the next window's y['seed']: tail_out
+// [B][S][J] (what the next hand-off blends with -- NOT tail_in: other threads still read that one) and c_seed [B][J][S], the layout
+// cond_rows reads.  J is odd in every product model, so a clip / tail row starts on any 4-byte boundary: a quad is stored as one 16-byte
+// store where its address allows, as four 4-byte stores elsewhere.
+struct HandoffArgs {
+    const float* xs32; const float* tail_in; float* tail_out; float* c_seed; float* clip_out;
+    int B, J, Jp, T, S, n_out, c;
+    int root_shift, is_first, is_last, keep_last_tail;
+};
+__device__ __forceinline__ void handoff_store4(float* dst, const f32x4& v, int n) {      // n = valid entries of the quad (1 .. 4)
+    if (n == 4 && ((size_t)dst & 15) == 0) { *(f32x4*)dst = v; return; }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (e < n) dst[e] = v[e];
+}
+__global__ void k_window_handoff(const HandoffArgs a) {
+    const int nq = a.Jp / 4, keep = a.T - a.S;
+    const size_t n = (size_t)a.B * a.T * nq;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int j0 = (int)(i % nq) * 4;
+        const size_t bf = i / nq;
+        const int f = (int)(bf % a.T), b = (int)(bf / a.T);
+        if (j0 >= a.J) continue;
+        const int nv = a.J - j0 < 4 ? a.J - j0 : 4;
+        f32x4 v = *(const f32x4*)(a.xs32 + bf * a.Jp + j0);
+        const float* t0 = a.tail_in + (size_t)b * a.S * a.J;      // frame 0 of the previous window's tail
+        if (!a.is_first && a.root_shift && j0 == 0) {
+            const float* s0 = a.xs32 + (size_t)b * a.T * a.Jp;
+#pragma unroll
+            for (int e = 0; e < 3; ++e)
+                if (e < nv) { const float delta = s0[e] - t0[e]; v[e] = v[e] - delta; }
+        }
+        if (!a.is_first && f == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (e < nv) v[e] = t0[j0 + e] * 0.5f + v[e] * 0.5f;
+        }
+        const int df = a.c * keep + f - a.S;
+        if ((f < keep || (a.is_last && a.keep_last_tail)) && df >= 0 && df < a.n_out)
+            handoff_store4(a.clip_out + ((size_t)b * a.n_out + df) * a.J + j0, v, nv);
+        if (f >= keep) {
+            const int sf = f - keep;
+            handoff_store4(a.tail_out + ((size_t)b * a.S + sf) * a.J + j0, v, nv);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (e < nv) a.c_seed[((size_t)b * a.J + j0 + e) * a.S + sf] = v[e];
+        }
+    }
+}
 // Self-check of the fence-free hand-off (dsg_hip.cpp: uc_selfcheck): `buf` is uncached device memory; the two kernels run as
 // dependent AQL packets WITHOUT acquire / release, 64 times over.  Writer workgroup b fills chunk b with a pattern of the
 // iteration; reader workgroup b verifies chunk b + 1 -- written on another XCD -- and counts stale words.  The iteration

@@ -318,6 +318,123 @@ class DSGDiffusion:
         self._last_model = models[0]
         return outs
 
+    # ---- a whole clip per library call (dsg_sample_clip): the window loops of sample.py inside the library -----------------
+    def sample_clip(self, model, feats, style, *, seed0=None, root_shift, keep_last_tail, ddim=False, eta=0.0, skip_timesteps=0,
+                    clip_denoised=False, scale=None, seed_last=None, mask_local="ones"):
+        """All K windows of B clips in ONE library call: per-window conditioning, step loop, seed hand-off, root shift (`root_shift`,
+        the ZEGGS loop's `smoothing`), one-frame blend and stitching on the device (k_window_handoff).  `feats`: the K per-window
+        features exactly as y['audio'] takes them, each [B, T_a, A_src] (stacked once into [K, B, T_a, A_src]); `style` [B, style_dim_in];
+        `seed0` [B, J, 1, S] = y['seed'] of window 0 (None: zeros); `scale` [B]: classifier-free guidance as y['scale'] (`model` is then
+        the ClassifierFreeSampleModel, or a DSGDenoiser with room for the twins); `seed_last`: y['seed_last'] of DiffuseStyleGesture++.
+        Returns the stitched clips [B, n_out, J] (numpy float32): n_out = K * stride - S (`keep_last_tail=False`, ZEGGS) or K * stride
+        (`True`, DSG+: last window whole, first S frames dropped).  Bit-identical to K `p_sample_loop` / `ddim_sample_loop` calls + the
+        host stitching of sample.py, and the draw counter advances as theirs does: by K * (1 + n_run)."""
+        return self.sample_clip_multi([model], [feats], [style], seed0s=None if seed0 is None else [seed0], root_shift=root_shift,
+                                      keep_last_tail=keep_last_tail, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
+                                      clip_denoised=clip_denoised, scales=None if scale is None else [scale],
+                                      seed_lasts=None if seed_last is None else [seed_last], mask_local=mask_local,
+                                      stream_ids=[self.stream_id])[0]
+
+    def sample_clip_multi(self, models, feats_per_lane, styles, *, seed0s=None, root_shift, keep_last_tail, ddim=False, eta=0.0,
+                          skip_timesteps=0, clip_denoised=False, scales=None, seed_lasts=None, mask_local="ones", seeds=None,
+                          stream_ids=None):
+        """`sample_clip` for several lanes at once (dsg_sample_clip_multi; lanes as in `p_sample_loop_multi`): lane i samples the B
+        clips of feats_per_lane[i] from the Philox stream (seeds[i], stream_ids[i]); the windows advance in lock step over the lanes.
+        Returns one [B, n_out, J] array per lane."""
+        models = list(models)
+        n = len(models)
+        if n == 0 or len(feats_per_lane) != n or len(styles) != n:
+            raise ValueError("one feature list and one style batch per lane")
+        K = len(feats_per_lane[0])
+        if K < 1 or any(len(f) != K for f in feats_per_lane):
+            raise ValueError("the same number of windows (>= 1) for every lane")
+        seeds = [self._seed] * n if seeds is None else list(seeds)
+        stream_ids = [self.stream_id + i for i in range(n)] if stream_ids is None else list(stream_ids)
+        use_torch = L.is_torch(feats_per_lane[0][0])
+        B = int(feats_per_lane[0][0].shape[0])
+        guided_any = scales is not None
+        inners = []
+        for m in models:
+            inner, guided = self._library_model(m, B)
+            if inner is None:
+                raise TypeError("sample_clip drives library denoisers (DSGDenoiser lanes)")
+            if guided and not guided_any:
+                raise KeyError("scale")
+            inners.append(inner)
+        cfg = inners[0].cfg
+        S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
+        n_run = self.num_timesteps - skip_timesteps
+        n_out = K * (T - S) - (0 if keep_last_tail else S)
+        if isinstance(mask_local, str):
+            if use_torch:
+                import torch
+                mask_local = torch.ones(1, T, dtype=torch.uint8, device=feats_per_lane[0][0].device)
+            else:
+                mask_local = np.ones((1, T), np.uint8)
+        mbuf = L.Buf(mask_local, "uint8") if mask_local is not None else L.Buf(None)
+        mb = 0 if mask_local is None else (int(mbuf.obj.shape[0]) if mbuf.obj.ndim == 2 else 1)
+        stream = L.current_stream_ptr() if use_torch else None
+        args = (L.dsg_sample_args * n)()
+        keep, outs = [mbuf], []
+        ptrs = {k: (C.c_void_p * n)() for k in ("h", "style", "seed0", "audio", "scale", "out")}
+        for i, m in enumerate(inners):
+            if m.inpainting:
+                raise ValueError("sample_clip: an inpainting constraint is per window (the host window loop takes it)")
+            m.set_schedule(self)
+            if use_torch:
+                import torch
+                audio = L.Buf(torch.stack([f.float() for f in feats_per_lane[i]]))
+            else:
+                audio = L.Buf(np.stack([np.asarray(f, np.float32) for f in feats_per_lane[i]]))
+            if tuple(audio.obj.shape) != (K, B, cfg.audio_frames, cfg.audio_src_dim):
+                raise ValueError(f"feats shape {tuple(audio.obj.shape)} != {(K, B, cfg.audio_frames, cfg.audio_src_dim)}")
+            style = L.Buf(styles[i])
+            if tuple(style.obj.shape) != (B, cfg.style_dim_in):
+                raise ValueError(f"style shape {tuple(style.obj.shape)}")
+            seed0 = L.Buf(None if seed0s is None else seed0s[i])
+            if seed0.obj is not None and tuple(seed0.obj.shape) != (B, J, 1, S):
+                raise ValueError(f"seed0 shape {tuple(seed0.obj.shape)}")
+            sc = L.Buf(None if scales is None else scales[i])
+            if sc.obj is not None:
+                if int(np.prod(sc.obj.shape)) != B:
+                    raise ValueError(f"scale must have {B} entries")
+                if m.max_batch < 2 * B:
+                    raise ValueError(f"classifier-free guidance runs the unconditional twins in the same batch: max_batch >= {2 * B}")
+            if cfg.variant == 5:
+                if seed_lasts is None or seed_lasts[i] is None:
+                    raise KeyError("seed_last")
+                last = L.Buf(seed_lasts[i])
+                if tuple(last.obj.shape) != (B, J, 1, S):
+                    raise ValueError(f"seed_last shape {tuple(last.obj.shape)}")
+                m.lib.check(m.lib.cdll.dsg_set_seed_last(m.handle, last.p, B, stream))
+                keep.append(last)
+            a = args[i]
+            a.mode, a.skip_timesteps, a.eta = (L.MODE_DDIM if ddim else L.MODE_DDPM), int(skip_timesteps), float(eta)
+            a.seed, a.stream_id, a.draw_base = int(seeds[i]) & (2 ** 64 - 1), int(stream_ids[i]), self._draw
+            a.clip_denoised = int(bool(clip_denoised))
+            if use_torch and audio.obj.is_cuda:      # device -> PINNED host memory, as sample.py's _zeggs_finish
+                import torch
+                out = torch.empty((B, n_out, J), dtype=torch.float32, pin_memory=True)
+                optr = out.data_ptr()
+                out = out.numpy()
+            else:
+                out = np.empty((B, n_out, J), np.float32)
+                optr = out.ctypes.data
+            outs.append(out)
+            keep += [audio, style, seed0, sc]
+            for k, v in (("h", m.handle), ("style", style.ptr), ("seed0", seed0.ptr), ("audio", audio.ptr), ("scale", sc.ptr), ("out", optr)):
+                ptrs[k][i] = v
+        lib = inners[0].lib
+        if n == 1:
+            lib.check(lib.cdll.dsg_sample_clip(ptrs["h"][0], ptrs["style"][0], ptrs["seed0"][0], ptrs["audio"][0], mbuf.p, mb, ptrs["scale"][0],
+                                               C.byref(args[0]), K, int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"][0], B, stream))
+        else:
+            lib.check(lib.cdll.dsg_sample_clip_multi(ptrs["h"], n, ptrs["style"], ptrs["seed0"], ptrs["audio"], mbuf.p, mb, ptrs["scale"], args, K,
+                                                     int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"], B, stream))
+        self._draw += K * (1 + n_run)
+        self._last_model = inners[0]
+        return outs
+
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
                          randomize_class=False, cond_fn_with_grad=False, dump_steps=None, const_noise=False,

@@ -9,6 +9,7 @@ HIP library.  Windows of one clip are serially dependent (window c is seeded by 
 from __future__ import annotations
 
 import argparse
+import functools
 import math
 import os
 
@@ -93,16 +94,36 @@ def _style_batch(style, B, use_torch, dev=None):
     return sty
 
 
+def _check_windows(windows, sample_fn=None):
+    """`windows=`: "host" = the window loop below, one library call per window (the default); "library" = the whole clip in one
+    library call (DSGDiffusion.sample_clip: hand-off and stitching on the device; bit-identical)."""
+    if windows not in ("host", "library"):
+        raise ValueError(f"windows must be 'host' or 'library', not {windows!r}")
+    if windows == "library" and sample_fn is not None:
+        raise ValueError("windows='library' runs the library's own loops: a custom sample_fn needs windows='host'")
+    return windows == "library"
+
+
+def _loop_fn(diffusion, ddim, eta):
+    return functools.partial(diffusion.ddim_sample_loop, eta=eta) if ddim else diffusion.p_sample_loop
+
+
 def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, skip_timesteps=0, sample_fn=None,
-                  stream_id=0, seed_pose=None, device=None):
+                  stream_id=0, seed_pose=None, device=None, *, windows="host", ddim=False, eta=0.0):
     """ZEGGS window loop (sample.py:236-296).  feats: sequence of K per-window WavLM features, each [B, T, A_src]
     (torch cuda tensors or numpy); style: one-hot list or [B, 6] array.  Returns normalised poses
-    [B, K*stride - n_seed, J] (numpy float32) -- B independent clips advance in lock step."""
+    [B, K*stride - n_seed, J] (numpy float32) -- B independent clips advance in lock step.  `ddim` / `eta`: the DDIM loop
+    instead of p_sample_loop (without a `sample_fn`); `windows`: see `_check_windows`."""
     cfg = model.cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
     B = int(feats[0].shape[0])
-    sample_fn = sample_fn or diffusion.p_sample_loop
+    if _check_windows(windows, sample_fn):
+        diffusion.manual_seed(seed, stream_id)
+        sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
+        return diffusion.sample_clip(model, list(feats), sty, seed0=seed_pose, root_shift=smoothing, keep_last_tail=False,
+                                     ddim=ddim, eta=eta, skip_timesteps=skip_timesteps)
+    sample_fn = sample_fn or _loop_fn(diffusion, ddim, eta)
     diffusion.manual_seed(seed, stream_id)          # torch.manual_seed(seed) at sample.py:212
     shape = (B, J, 1, T)
     out = []
@@ -121,7 +142,7 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
 
 
 def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456, smoothing=True, skip_timesteps=0,
-                           stream_ids=None, ddim=False, eta=0.0, kernel_set="recommended"):
+                           stream_ids=None, ddim=False, eta=0.0, kernel_set="recommended", *, windows="host"):
     """Several clips of one GPU advanced concurrently on sampling LANES ("one clip per stream", BASELINE config[3]): `lanes`
     are N DSGDenoiser lanes over one copy of the weights (`model.clone()`); lane i samples the B clips of
     feats_per_lane[i] (K per-window features [B, T, A_src]; B = 1: one clip per lane) on its own HSA queue and the library
@@ -152,6 +173,10 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
             mask = np.ones((1, T), bool)
         per_lane_style = (not L.is_torch(styles)) and np.asarray(styles).ndim == 2 and len(styles) == n and np.asarray(styles).shape[0] == n and B == 1
         stys = [_style_batch(styles[i] if per_lane_style else styles, B, use_torch, dev) for i in range(n)]
+        if _check_windows(windows):
+            return np.concatenate(diffusion.sample_clip_multi(list(lanes), [list(f) for f in feats_per_lane], stys, root_shift=smoothing,
+                                                              keep_last_tail=False, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
+                                                              seeds=[seed] * n, stream_ids=stream_ids), axis=0)
         outs = [[] for _ in range(n)]
         for c in range(K):
             ys = [{"y": _zeggs_window_y(cfg, feats_per_lane[i][c], stys[i], outs[i][-1] if outs[i] else None, None, use_torch, mask)}
@@ -222,6 +247,20 @@ def _dsgplus_stitch(out, s, S, use_torch):
     out.append(s)
 
 
+def _dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division, seed, stream_ids,
+                     skip_timesteps, ddim, eta):
+    """The DSG+ clips of every lane through DSGDiffusion.sample_clip_multi: the per-window features as `_dsgplus_window_y` builds them,
+    then crop + feature division as `_dsgplus_finish`."""
+    cfg = lanes[0].cfg
+    use_torch = L.is_torch(feats_per_lane[0][0])
+    audio = [[_dsgplus_window_y(cfg, f, c, sty, seed0s[i], None if seed_lasts is None else seed_lasts[i], use_torch, None)["audio"]
+              for c in range(len(f))] for i, f in enumerate(feats_per_lane)]
+    seqs = diffusion.sample_clip_multi(list(lanes), audio, [sty] * len(lanes), seed0s=list(seed0s), root_shift=False, keep_last_tail=True,
+                                       ddim=ddim, eta=eta, skip_timesteps=skip_timesteps, seed_lasts=seed_lasts, seeds=[seed] * len(lanes),
+                                       stream_ids=stream_ids)
+    return [np.ascontiguousarray(q[:, :real_n_frames, : cfg.njoints // feature_division], dtype=np.float32) for q in seqs]
+
+
 def _dsgplus_finish(out, S, J, real_n_frames, feature_division, use_torch):
     if use_torch:
         import torch
@@ -236,7 +275,7 @@ def _dsgplus_finish(out, S, J, real_n_frames, feature_division, use_torch):
 
 def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, seed0s, real_n_frames, seed=123456, skip_timesteps=0,
                                    stream_ids=None, seed_lasts=None, feature_division=3, ddim=False, eta=0.0,
-                                   kernel_set="recommended"):
+                                   kernel_set="recommended", *, windows="host"):
     """`generate_clips_streams` for the DSG+ window loop (BEAT-TWH sample.py:98-192; all three model names of that tree): lane i
     samples the B clips of feats_per_lane[i] (K per-window features), seeded by seed0s[i] [B, J, 1, S] (and seed_lasts[i] for
     DiffuseStyleGesture++), on its own HSA queue; the lanes' step loops are interleaved by the library.  Lane i is bit-identical
@@ -261,6 +300,9 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
         else:
             mask = np.ones((1, T), bool)
         sty = _style_batch(styles, B, use_torch, dev)
+        if _check_windows(windows):
+            return np.concatenate(_dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division,
+                                                   seed, stream_ids, skip_timesteps, ddim, eta), axis=0)
         outs = [[] for _ in range(n)]
         for c in range(K):
             ys = [{"y": _dsgplus_window_y(cfg, feats_per_lane[i], c, sty, seed0s[i] if c == 0 else outs[i][-1][..., -S:],
@@ -273,7 +315,7 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
 
 
 def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, seed=123456, skip_timesteps=0,
-                          sample_fn=None, stream_id=0, seed_last=None, feature_division=3):
+                          sample_fn=None, stream_id=0, seed_last=None, feature_division=3, *, windows="host", ddim=False, eta=0.0):
     """DSG+ window loop (BEAT-TWH sample.py:98-192), attention4: zero-padded tail, no left audio context, GT seed for
     window 0, no root shift, last window kept whole, first S frames dropped, crop, keep the first J/3 features.
     `model.cfg.variant == 3` is that tree's "DiffuseStyleGesture" (attention3 at BEAT dims): S frames of left audio context.
@@ -284,11 +326,15 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
     B = int(feats[0].shape[0])
-    sample_fn = sample_fn or diffusion.p_sample_loop
+    library = _check_windows(windows, sample_fn)
+    sample_fn = sample_fn or _loop_fn(diffusion, ddim, eta)
     diffusion.manual_seed(seed, stream_id)
     shape = (B, J, 1, T)
     out = []
     sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
+    if library:
+        return _dsgplus_library(diffusion, [model], [feats], sty, [seed0], None if seed_last is None else [seed_last], real_n_frames,
+                                feature_division, seed, [stream_id], skip_timesteps, ddim, eta)[0]
     if use_torch:
         import torch
         dev = feats[0].device
@@ -384,6 +430,8 @@ def build_parser():
     p.add_argument('--wavlm_path', default='./WavLM/WavLM-Large.pt', help='WavLM checkpoint (sample.py:33)')
     p.add_argument('--save_dir', default='sample_dir')
     p.add_argument('--timestep_respacing', default='')
+    p.add_argument('--windows', default='host', choices=['host', 'library'],
+                   help='host = one library call per window, stitched on the host (default); library = the whole clip in one library call')
     return p
 
 
@@ -423,7 +471,7 @@ def main(argv=None):
     if args.max_len:
         feats = feats[: max(1, args.max_len // (n_poses - ZEGGS.n_seed))]
     feats_t = [torch.from_numpy(f[None]).cuda(dev) for f in feats]
-    poses = generate_clip(model, diffusion, feats_t, style, seed=123456, smoothing=True)[0]
+    poses = generate_clip(model, diffusion, feats_t, style, seed=123456, smoothing=True, windows=args.windows)[0]
     stem = os.path.join(args.save_dir, os.path.splitext(name)[0])
     np.save(stem + "_poses.npy", poses)
     # de-normalise (sample.py:320-326) and write the .bvh (process_zeggs_bvh.py:219) like the reference's main()

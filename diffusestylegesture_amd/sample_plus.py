@@ -70,6 +70,8 @@ def build_parser():
                    help="`version` of the reference's yml (sample.py:309-315): v0 = poses + velocities + accelerations (njoints = 3 x motion_dim), "
                         "v2 (BEAT only) = njoints = motion_dim = 1141")
     p.add_argument('--mean_std_npz', default='', help="v2: file with `mean` and `std` [motion_dim] (the reference's gesture_BEAT_mean_v2.npy / _std_v2.npy)")
+    p.add_argument('--windows', default='host', choices=['host', 'library'],
+                   help='host = one library call per window, stitched on the host (default); library = the whole clip in one library call')
     return p
 
 
@@ -110,7 +112,7 @@ def main(argv=None):
     style = np.zeros(cfg.style_dim_in, np.float32)
     style[args.speaker] = 1.0
     seq = generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n, seed=123456, skip_timesteps=args.skip_timesteps,
-                                seed_last=seed_last, feature_division=1 if args.version == 'v2' else 3)[0]
+                                seed_last=seed_last, feature_division=1 if args.version == 'v2' else 3, windows=args.windows)[0]
     out_poses = np.multiply(seq, std) + mean                                  # sample.py:184 (no clipping of std here)
     os.makedirs(args.save_dir, exist_ok=True)
     stem = os.path.join(args.save_dir, os.path.splitext(os.path.basename(args.features_npy))[0])

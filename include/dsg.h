@@ -24,6 +24,9 @@
  *        ClassifierFreeSampleModel.forward (y['scale'], y['uncond'])   main/model/cfg_sampler.py:8-31
  *   dsg_set_inpainting
  *        y['inpainting_mask'] / y['inpainted_motion'] in p_mean_variance   main/diffusion/gaussian_diffusion.py:317-321
+ *   dsg_sample_clip / dsg_sample_clip_multi
+ *        the window loop of inference(): seed hand-off, root shift,  main/mydiffusion_zeggs/sample.py:236-296,
+ *        one-frame blend, stitching                                  BEAT-TWH-main/mydiffusion_beat_twh/sample.py:98-192
  *   dsg_clone / dsg_sample_multi / dsg_set_kernel_set / dsg_get_kernel_set / dsg_recommend_kernel_set / dsg_last_kernel_set
  *        (no reference counterpart: the reference samples one clip at a time, sample.py:418 batch_size = 1; these run
  *         several clips of one GPU concurrently over one copy of the weights -- BASELINE config[3] "one clip per stream")
@@ -208,6 +211,30 @@ int dsg_sample(dsg_handle* h, const dsg_sample_args* args, float* out, int B, vo
  * of the lanes overlap on the GPU.  args[n], outs[n]; every lane samples a batch of B.  Every lane runs the kernel set of ITS
  * handle, so lane i's result is bit-identical to dsg_sample(lanes[i], &args[i], outs[i], B, stream) issued on its own. */
 int dsg_sample_multi(dsg_handle** lanes, int n, const dsg_sample_args* args, float** outs, int B, void* stream);
+/* A whole clip in one call: the K windows of the reference's inference() loops (main/mydiffusion_zeggs/sample.py:236-296,
+ * BEAT-TWH-main/mydiffusion_beat_twh/sample.py:98-192) for B clips in lock step.  Per window the library sets the conditioning
+ * (as dsg_set_window_cond / _cfg: `scale` float[B] or NULL), runs the step loop exactly as dsg_sample does, and hands the window
+ * over on the device (k_window_handoff): window c > 0 is shifted so that its root position (features 0..2) continues the previous
+ * window's when root_shift != 0 (sample.py:277-281), its frame 0 is blended half and half with the previous window's frame T - S
+ * (the reference's `len(last_poses) == 1` quirk), frames [0, T - S) are appended to the clip, and its last S frames are window
+ * c + 1's y['seed'].  style [B, style_dim_in]; seed0 [B, J, 1, S] = y['seed'] of window 0, NULL = zeros (sample.py:241);
+ * audio [K, B, T_a, A_src] = the K per-window features exactly as dsg_set_window_cond takes them (variant 3 of the BEAT-TWH tree:
+ * the caller prepends the left context, as before); mask_local / mask_batch as dsg_set_window_cond, the same for every window.
+ * out [B, n_out, J] fp32, host or device, frame-major (NOT [B, J, 1, T]): keep_last_tail == 0 (ZEGGS) cuts the last overlap and
+ * the first S frames, n_out = K * (T - S) - S; keep_last_tail != 0 (DSG+) keeps the last window whole, n_out = K * (T - S).
+ * args: as dsg_sample; draw_base is window 0's, window c draws from draw_base + c * (1 + n_run) -- what K consecutive dsg_sample
+ * calls consume -- so the result is bit-identical to those K calls + the stitching of sample.py under the same kernel set.
+ * DSG_E_INVALID: K < 1; a handle with an inpainting constraint (it is per window); step_noise, init_noise, init_image, n_dump,
+ * first_step or max_steps in args (per-window tensors / pieces of one chain).  Variant 5 needs dsg_set_seed_last first.
+ * dsg_last_sample_ms afterwards: the sum over the K step loops, n_steps their total.  _multi: n lanes as dsg_sample_multi, one clip
+ * batch each (styles[n], audios[n], outs[n], args[n]; seed0s / scales: NULL or n entries, each nullable), the windows advance in
+ * lock step over the lanes.  Added without a version step, as dsg_set_inpainting: dsg_version() stays 330. */
+int dsg_sample_clip(dsg_handle* h, const float* style, const float* seed0, const float* audio, const uint8_t* mask_local,
+                    int mask_batch, const float* scale, const dsg_sample_args* args, int K, int root_shift, int keep_last_tail,
+                    float* out, int B, void* stream);
+int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* const* styles, const float* const* seed0s,
+                          const float* const* audios, const uint8_t* mask_local, int mask_batch, const float* const* scales,
+                          const dsg_sample_args* args, int K, int root_shift, int keep_last_tail, float** outs, int B, void* stream);
 /* Kernel set of a handle (DSG_KSET_*; sticky; clones inherit the source's at dsg_clone).  dsg_recommend_kernel_set: the set
  * measured fastest for `lanes` lanes of batch B advanced together (lanes = 1: what DSG_KSET_AUTO picks) -- several lanes share
  * the CUs and prefer the throughput-shaped sets earlier; the caller applies it to each lane.  dsg_last_kernel_set: the set the
