@@ -160,6 +160,10 @@ struct dsg_handle {
     // one and writes the other), and the stitched clip when the caller's `out` is host memory.  Allocated on first use
     float* clip_tail[2] = {nullptr, nullptr}; float* clip_out = nullptr; size_t clip_out_cap = 0;
     bool clip_timing = false; double clip_ms = 0.0;      // the last sampling call was dsg_sample_clip: dsg_last_sample_ms reports the sum over its windows
+    // clip-level inpainting constraint (dsg_set_clip_inpainting): the library's own copy in the stitched clip's coordinates [cinpB][cinp_frames][J];
+    // cinpB == 0: off.  Allocated on first use, grown when needed (cinp_cap elements).  dsg_sample_clip cuts window c's constraint out of it into
+    // inp32 / inp_mask (k_clip_inp_window); inpB stays 0 outside that call
+    int cinpB = 0, cinp_frames = 0; float* cinp_motion = nullptr; unsigned char* cinp_mask = nullptr; size_t cinp_cap = 0;
     int last_path = -1;                  // submission path of the last dsg_sample: 0 HIP launches, 1 AQL packets, 2 hipGraph replay
     bool last_nofence = false;           // ... and whether its packets went without fences
     int kset_req = DSG_KSET_AUTO;        // dsg_set_kernel_set: the kernel set every step of this handle runs (AUTO: by batch, select_kernels)
@@ -2165,6 +2169,41 @@ extern "C" int dsg_set_inpainting(dsg_handle* h, const uint8_t* mask, const floa
     return 0;
 }
 
+// The constraint of a whole clip, for dsg_sample_clip / _multi: mask uint8 / motion fp32 [B, n_frames, J] in the coordinates of the stitched
+// clip (frame-major, the layout and frame numbering of dsg_sample_clip's `out`), host or device.  The library keeps its own copy (the caller's
+// buffers are free once `stream` has passed the call) and cuts every window's constraint out of it on the device (k_clip_inp_window) into the
+// buffers of dsg_set_inpainting, which are allocated here too.  Sticky until switched off (both NULL); dsg_forward / dsg_sample / _multi ignore it.
+extern "C" int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const float* motion, int B, int n_frames, void* stream) {
+    if (!h) return fail(DSG_E_INVALID, "null handle");
+    if (!mask && !motion) { h->cinpB = 0; h->cinp_frames = 0; return 0; }
+    if (!mask || !motion) return fail(DSG_E_INVALID, "dsg_set_clip_inpainting: mask and motion go together (both NULL switches the constraint off)");
+    if (B <= 0 || B > h->Bmax) return fail(DSG_E_INVALID, "batch exceeds max_batch");
+    if (n_frames < 1) return fail(DSG_E_INVALID, "dsg_set_clip_inpainting: n_frames < 1");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    h->cinpB = 0; h->cinp_frames = 0;      // (a call that fails below leaves the constraint off, not half written)
+    const size_t n = (size_t)B * n_frames * h->J;
+    if (n > h->cinp_cap) {
+        // grown: the old copy goes back at once (nothing on the handle's stream may still read it)
+        HIPCHK(hipStreamSynchronize(h->stream));
+        void* old[2] = {h->cinp_motion, h->cinp_mask};
+        h->cinp_motion = nullptr; h->cinp_mask = nullptr; h->cinp_cap = 0;
+        for (void* p : old)
+            if (p) { h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), p), h->allocs.end()); (void)hipFree(p); }
+        CHK(dalloc(h, &h->cinp_motion, n, false));
+        CHK(dalloc(h, &h->cinp_mask, n, false));
+        h->cinp_cap = n;
+    }
+    // (each pointer on its own, as dsg_set_inpainting)
+    if (!h->inp32) CHK(dalloc(h, &h->inp32, (size_t)h->Bmax * h->T * h->Jp));
+    if (!h->inp_mask) CHK(dalloc(h, &h->inp_mask, (size_t)h->Bmax * h->T * h->Jp));
+    CHK(order_after(h, stream));
+    CHK(upload(h, h->cinp_motion, motion, n * sizeof(float)));
+    CHK(upload(h, h->cinp_mask, mask, n));
+    h->cinpB = B; h->cinp_frames = n_frames;
+    CHK(order_before(h, stream));
+    return 0;
+}
+
 extern "C" int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, float* out, int B, void* stream) {
     if (!h || !x || !t || !out) return fail(DSG_E_INVALID, "dsg_forward: null argument");
     if (!h->finalized || !h->cond_set) return fail(DSG_E_STATE, "dsg_forward before finalize / set_window_cond");
@@ -2591,6 +2630,16 @@ static int launch_handoff(dsg_handle* h, float* clip_out, int B, int n_out, int 
     return 0;
 }
 
+static int launch_clip_inp_window(dsg_handle* h, int B, int n_out, int c) {
+    ClipInpArgs a;
+    a.motion = h->cinp_motion; a.mask = h->cinp_mask; a.inp32 = h->inp32; a.inp_mask = h->inp_mask;
+    a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S; a.n_out = n_out; a.c = c;
+    const size_t n = (size_t)B * h->T * (h->Jp / 4);
+    hipLaunchKernelGGL(k_clip_inp_window, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const float* const* seed0s, const float* const* audios,
                        const uint8_t* mask_local, int mask_batch, const float* const* scales, const dsg_sample_args* args, int K,
                        int root_shift, int keep_last_tail, float** outs, int B, void* stream) {
@@ -2619,6 +2668,14 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
     const int n_out = keep_last_tail ? K * (T - S) : K * (T - S) - S;
     const size_t n_clip = (size_t)B * n_out * J, n_tail = (size_t)B * J * S;
     const int n_run = hs[0]->sched.n - args[0].skip_timesteps;
+    for (int i = 0; i < n; ++i) {          // a clip-level constraint (dsg_set_clip_inpainting) is in the coordinates of THIS call's `out`
+        const dsg_handle* h = hs[i];
+        if (h->cinpB > 0 && h->cinpB != B)
+            return fail(DSG_E_INVALID, "dsg_sample_clip: batch " + std::to_string(B) + " differs from the batch of dsg_set_clip_inpainting (" + std::to_string(h->cinpB) + ")");
+        if (h->cinpB > 0 && h->cinp_frames != n_out)
+            return fail(DSG_E_INVALID, "dsg_sample_clip: the clip has n_out = " + std::to_string(n_out) + " frames, the constraint of dsg_set_clip_inpainting n_frames = " +
+                                       std::to_string(h->cinp_frames));
+    }
     HIPCHK(hipSetDevice(hs[0]->cfg.device));
     std::vector<float*> clip(n);
     for (int i = 0; i < n; ++i) {
@@ -2643,11 +2700,21 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
         LanesNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) hs[i]->lanes_now = n; }
         ~LanesNow() { for (int i = 0; i < n; ++i) hs[i]->lanes_now = 1; }
     } lanes_now(hs, n);
+    // Lanes with a clip-level constraint: window c's slice goes into inp32 / inp_mask where the window's conditioning is set -- on the handle's
+    // stream, which sample_prepare drains before the first packet, whose acquire covers it like the conditioning; the pointers stay, only the
+    // contents change -- and the epilogue's inpainting is on (inpB: StepCtx::inpaint, GKey flag 32) for the windows of this call only: every
+    // lane came in with inpB == 0 (checked above) and leaves with it, on error returns too
+    struct ClipInpaintNow {
+        dsg_handle** hs; int n;
+        ClipInpaintNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) {}
+        ~ClipInpaintNow() { for (int i = 0; i < n; ++i) hs[i]->inpB = 0; }
+    } clip_inpaint_now(hs, n);
     for (int c = 0; c < K; ++c) {
         for (int i = 0; i < n; ++i) {
             dsg_handle* h = hs[i];
             const float* audio_c = audios[i] + (size_t)c * B * h->Ta * h->As;
             CHK(set_window_cond(h, styles[i], h->c_seed, audio_c, mask_local, mask_batch, B, 0, scales ? scales[i] : nullptr, stream));
+            if (h->cinpB > 0) { CHK(launch_clip_inp_window(h, B, n_out, c)); h->inpB = B; }
             wargs[i].draw_base = args[i].draw_base + (uint32_t)c * (uint32_t)(1 + n_run);      // what K consecutive dsg_sample calls consume
         }
         for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, jobs[i]));

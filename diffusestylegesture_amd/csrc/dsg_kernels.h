@@ -1711,6 +1711,47 @@ __global__ void k_window_handoff(const HandoffArgs a) {
         }
     }
 }
+// The constraint of one window cut out of a clip-level one (dsg_set_clip_inpainting): the inverse walk of k_window_handoff.  motion / mask
+// [B][n_out][J] are in the coordinates of the stitched clip; window c, frame f is clip row df = c * (T - S) + f - S -- the row the hand-off
+// writes frame f to, and, for the tail f >= T - S, the row window c + 1 will write (so the seed handed over honours the constraint already).
+// Outside [0, n_out) -- the first S frames of window 0, the closing S frames of the last window when they are cut -- and in the padded
+// columns J..Jp the frame is unconstrained: 0 / unmasked.  Output in the state's layout inp32 / inp_mask [B][T][Jp], what the pose-head
+// epilogue reads (k_inp_in writes the same for a window-level constraint): one thread per feature quad of a (clip, frame) row, one 16-byte
+// store and one packed mask word.  J is odd in every product model, so a clip row starts on any 4-byte boundary and the four mask bytes of
+// a quad on any byte boundary: 16-byte load where the address allows, scalars elsewhere (as handoff_store4 stores); mask bytes singly, any
+// non-zero byte becomes 1.
+struct ClipInpArgs {
+    const float* motion; const unsigned char* mask; float* inp32; unsigned char* inp_mask;
+    int B, J, Jp, T, S, n_out, c;
+};
+__device__ __forceinline__ f32x4 clip_inp_load4(const float* src, int n) {      // n = valid entries of the quad (1 .. 4); the rest 0
+    if (n == 4 && ((size_t)src & 15) == 0) return *(const f32x4*)src;
+    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (e < n) v[e] = src[e];
+    return v;
+}
+__global__ void k_clip_inp_window(const ClipInpArgs a) {
+    const int nq = a.Jp / 4, keep = a.T - a.S;
+    const size_t n = (size_t)a.B * a.T * nq;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int j0 = (int)(i % nq) * 4;
+        const size_t bf = i / nq;
+        const int f = (int)(bf % a.T), b = (int)(bf / a.T);
+        const int df = a.c * keep + f - a.S;
+        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+        unsigned mk = 0;
+        if (df >= 0 && df < a.n_out && j0 < a.J) {
+            const int nv = a.J - j0 < 4 ? a.J - j0 : 4;
+            const size_t src = ((size_t)b * a.n_out + df) * a.J + j0;
+            v = clip_inp_load4(a.motion + src, nv);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (e < nv) mk |= (a.mask[src + e] ? 1u : 0u) << (8 * e);
+        }
+        *(f32x4*)(a.inp32 + bf * a.Jp + j0) = v;
+        *(unsigned*)(a.inp_mask + bf * a.Jp + j0) = mk;
+    }
+}
 // Self-check of the fence-free hand-off (dsg_hip.cpp: uc_selfcheck): `buf` is uncached device memory; the two kernels run as
 // dependent AQL packets WITHOUT acquire / release, 64 times over.  Writer workgroup b fills chunk b with a pattern of the
 // iteration; reader workgroup b verifies chunk b + 1 -- written on another XCD -- and counts stale words.  The iteration

@@ -320,7 +320,7 @@ class DSGDiffusion:
 
     # ---- a whole clip per library call (dsg_sample_clip): the window loops of sample.py inside the library -----------------
     def sample_clip(self, model, feats, style, *, seed0=None, root_shift, keep_last_tail, ddim=False, eta=0.0, skip_timesteps=0,
-                    clip_denoised=False, scale=None, seed_last=None, mask_local="ones"):
+                    clip_denoised=False, scale=None, seed_last=None, mask_local="ones", inpainting_mask=None, inpainted_motion=None):
         """All K windows of B clips in ONE library call: per-window conditioning, step loop, seed hand-off, root shift (`root_shift`,
         the ZEGGS loop's `smoothing`), one-frame blend and stitching on the device (k_window_handoff).  `feats`: the K per-window
         features exactly as y['audio'] takes them, each [B, T_a, A_src] (stacked once into [K, B, T_a, A_src]); `style` [B, style_dim_in];
@@ -328,23 +328,36 @@ class DSGDiffusion:
         the ClassifierFreeSampleModel, or a DSGDenoiser with room for the twins); `seed_last`: y['seed_last'] of DiffuseStyleGesture++.
         Returns the stitched clips [B, n_out, J] (numpy float32): n_out = K * stride - S (`keep_last_tail=False`, ZEGGS) or K * stride
         (`True`, DSG+: last window whole, first S frames dropped).  Bit-identical to K `p_sample_loop` / `ddim_sample_loop` calls + the
-        host stitching of sample.py, and the draw counter advances as theirs does: by K * (1 + n_run)."""
+        host stitching of sample.py, and the draw counter advances as theirs does: by K * (1 + n_run).
+        `inpainting_mask` / `inpainted_motion` [B, n_out, J] (numpy or torch; both or neither): motion inpainting over the whole clip, in
+        the coordinates of the returned clip -- every window runs with the y['inpainting_mask'] / y['inpainted_motion'] that
+        `sample.window_constraint` cuts out of them, cut on the device (`DSGDenoiser.set_clip_inpainting`; set before the call, cleared
+        after it)."""
+        if (inpainting_mask is None) != (inpainted_motion is None):
+            raise ValueError("sample_clip: inpainting_mask and inpainted_motion go together")
         return self.sample_clip_multi([model], [feats], [style], seed0s=None if seed0 is None else [seed0], root_shift=root_shift,
                                       keep_last_tail=keep_last_tail, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
                                       clip_denoised=clip_denoised, scales=None if scale is None else [scale],
                                       seed_lasts=None if seed_last is None else [seed_last], mask_local=mask_local,
-                                      stream_ids=[self.stream_id])[0]
+                                      stream_ids=[self.stream_id], inpainting_masks=None if inpainting_mask is None else [inpainting_mask],
+                                      inpainted_motions=None if inpainted_motion is None else [inpainted_motion])[0]
 
     def sample_clip_multi(self, models, feats_per_lane, styles, *, seed0s=None, root_shift, keep_last_tail, ddim=False, eta=0.0,
                           skip_timesteps=0, clip_denoised=False, scales=None, seed_lasts=None, mask_local="ones", seeds=None,
-                          stream_ids=None):
+                          stream_ids=None, inpainting_masks=None, inpainted_motions=None):
         """`sample_clip` for several lanes at once (dsg_sample_clip_multi; lanes as in `p_sample_loop_multi`): lane i samples the B
         clips of feats_per_lane[i] from the Philox stream (seeds[i], stream_ids[i]); the windows advance in lock step over the lanes.
+        `inpainting_masks` / `inpainted_motions`: one [B, n_out, J] pair per lane, entries may be None (that lane runs unconstrained).
         Returns one [B, n_out, J] array per lane."""
         models = list(models)
         n = len(models)
         if n == 0 or len(feats_per_lane) != n or len(styles) != n:
             raise ValueError("one feature list and one style batch per lane")
+        if (inpainting_masks is None) != (inpainted_motions is None):
+            raise ValueError("sample_clip: inpainting_masks and inpainted_motions go together")
+        inp = [(None, None)] * n if inpainting_masks is None else list(zip(inpainting_masks, inpainted_motions))
+        if len(inp) != n or any((mk is None) != (mo is None) for mk, mo in inp):
+            raise ValueError("sample_clip: one inpainting mask and one motion per lane (or None for both)")
         K = len(feats_per_lane[0])
         if K < 1 or any(len(f) != K for f in feats_per_lane):
             raise ValueError("the same number of windows (>= 1) for every lane")
@@ -425,12 +438,24 @@ class DSGDiffusion:
             for k, v in (("h", m.handle), ("style", style.ptr), ("seed0", seed0.ptr), ("audio", audio.ptr), ("scale", sc.ptr), ("out", optr)):
                 ptrs[k][i] = v
         lib = inners[0].lib
-        if n == 1:
-            lib.check(lib.cdll.dsg_sample_clip(ptrs["h"][0], ptrs["style"][0], ptrs["seed0"][0], ptrs["audio"][0], mbuf.p, mb, ptrs["scale"][0],
-                                               C.byref(args[0]), K, int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"][0], B, stream))
-        else:
-            lib.check(lib.cdll.dsg_sample_clip_multi(ptrs["h"], n, ptrs["style"], ptrs["seed0"], ptrs["audio"], mbuf.p, mb, ptrs["scale"], args, K,
-                                                     int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"], B, stream))
+        try:
+            for m, (mk, mo) in zip(inners, inp):
+                if mk is not None:
+                    if tuple(mo.shape) != (B, n_out, J):
+                        raise ValueError(f"clip inpainted_motion shape {tuple(mo.shape)} != {(B, n_out, J)}")
+                    m.set_clip_inpainting(mk, mo, B)
+                elif m.clip_inpainting:
+                    m.set_clip_inpainting(None, None, 0)
+            if n == 1:
+                lib.check(lib.cdll.dsg_sample_clip(ptrs["h"][0], ptrs["style"][0], ptrs["seed0"][0], ptrs["audio"][0], mbuf.p, mb, ptrs["scale"][0],
+                                                   C.byref(args[0]), K, int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"][0], B, stream))
+            else:
+                lib.check(lib.cdll.dsg_sample_clip_multi(ptrs["h"], n, ptrs["style"], ptrs["seed0"], ptrs["audio"], mbuf.p, mb, ptrs["scale"], args, K,
+                                                         int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"], B, stream))
+        finally:
+            for m in inners:
+                if m.clip_inpainting:
+                    m.set_clip_inpainting(None, None, 0)
         self._draw += K * (1 + n_run)
         self._last_model = inners[0]
         return outs

@@ -15,6 +15,15 @@ from . import lib as L
 from .config import DSGConfig
 
 
+def _mask_bytes(mask):
+    """A mask as the library takes it: bool / uint8 as they are (any non-zero byte counts as set), other dtypes by `!= 0`."""
+    if L.is_torch(mask):
+        import torch
+        return mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+    a = np.asarray(mask)
+    return a if a.dtype in (np.bool_, np.uint8) else a != 0
+
+
 class DSGDenoiser:
     def __init__(self, cfg: DSGConfig, precision: str = "bf16", max_batch: int = 1, device: int = 0,
                  steps_per_graph: int = 0, library: L.DSGLibrary | None = None, latency_mode: str = "auto",
@@ -30,6 +39,7 @@ class DSGDenoiser:
         self._n_params = 0
         self._source = _clone_of          # keeps the weight owner alive as long as any lane exists
         self.inpainting = False           # this lane holds an inpainting constraint (set_inpainting)
+        self._clip_inpainting = False     # ... a clip-level one (set_clip_inpainting)
         if _clone_of is not None:
             h = C.c_void_p()
             self.lib.check(self.lib.cdll.dsg_clone(_clone_of.handle, max_batch, C.byref(h)))
@@ -159,6 +169,33 @@ class DSGDenoiser:
         stream = L.current_stream_ptr() if (L.is_torch(mask) or L.is_torch(motion)) else None
         self.lib.check(self.lib.cdll.dsg_set_inpainting(self.handle, mbuf.p, vbuf.p, batch, stream))
         self.inpainting = True
+
+    def set_clip_inpainting(self, mask, motion, batch: int):
+        """The inpainting constraint of a whole clip for `DSGDiffusion.sample_clip` (dsg_set_clip_inpainting): `mask` / `motion`
+        [batch, n_out, njoints] in the coordinates of the stitched clip that call returns; the library cuts every window's
+        y['inpainting_mask'] / y['inpainted_motion'] out of it on the device.  Sticky for this lane;
+        `set_clip_inpainting(None, None, 0)` switches it off.  The single-window loops ignore it.  `DSGDiffusion.sample_clip` sets it
+        from its own keywords and clears it afterwards (a call without them runs unconstrained, as `p_sample_loop` without the keys)."""
+        if mask is None and motion is None:
+            self.lib.check(self.lib.cdll.dsg_set_clip_inpainting(self.handle, None, None, 0, 0, None))
+            self._clip_inpainting = False
+            return
+        if mask is None or motion is None:
+            raise ValueError("clip inpainting: mask and motion go together")
+        mbuf, vbuf = L.Buf(_mask_bytes(mask), "uint8"), L.Buf(motion)
+        shape = tuple(vbuf.obj.shape)
+        if len(shape) != 3 or shape[0] != batch or shape[1] < 1 or shape[2] != self.njoints:
+            raise ValueError(f"clip inpainted_motion shape {shape} != ({batch}, n_out, {self.njoints})")
+        if tuple(mbuf.obj.shape) != shape:
+            raise ValueError(f"clip inpainting_mask shape {tuple(mbuf.obj.shape)} != {shape}")
+        stream = L.current_stream_ptr() if (L.is_torch(mask) or L.is_torch(motion)) else None
+        self.lib.check(self.lib.cdll.dsg_set_clip_inpainting(self.handle, mbuf.p, vbuf.p, batch, shape[1], stream))
+        self._clip_inpainting = True
+
+    @property
+    def clip_inpainting(self) -> bool:
+        """This lane holds a clip-level inpainting constraint (`set_clip_inpainting`)."""
+        return self._clip_inpainting
 
     def _alloc_out(self, shape, use_torch):
         if use_torch:

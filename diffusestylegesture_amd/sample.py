@@ -108,12 +108,79 @@ def _loop_fn(diffusion, ddim, eta):
     return functools.partial(diffusion.ddim_sample_loop, eta=eta) if ddim else diffusion.p_sample_loop
 
 
+def window_constraint(cfg, mask, motion, c, keep_last_tail):
+    """Window c's y['inpainting_mask'] / y['inpainted_motion'] (both [B, J, 1, T]) cut out of a clip-level constraint `mask` / `motion`
+    [B, n_out, J] given in the coordinates of the stitched clip (n_out = K * stride - S, or K * stride with `keep_last_tail`: the DSG+
+    loops).  Frame f of window c is clip row df = c * stride + f - S; for 0 <= df < n_out the window's constraint at (b, j, f) is the
+    clip's at (b, df, j), elsewhere -- the first S frames of window 0, the closing S frames of the last window when they are cut -- the
+    frame is unconstrained.  The tail of window c thus carries the constraint of the rows window c + 1 writes.  numpy or torch, as given;
+    what the library does on the device for `windows="library"` (dsg_set_clip_inpainting)."""
+    S, T, J, keep = cfg.n_seed, cfg.n_poses, cfg.njoints, cfg.n_poses - cfg.n_seed
+    if (mask is None) != (motion is None):
+        raise ValueError("inpainting_mask and inpainted_motion go together")
+    if len(motion.shape) != 3 or int(motion.shape[2]) != J or tuple(mask.shape) != tuple(motion.shape):
+        raise ValueError(f"clip constraint: mask {tuple(mask.shape)} and motion {tuple(motion.shape)} must both be [B, n_out, {J}]")
+    B, n_out = int(motion.shape[0]), int(motion.shape[1])
+    K, rest = divmod(n_out + (0 if keep_last_tail else S), keep)
+    if rest or not 0 <= c < K:
+        raise ValueError(f"clip constraint: n_out = {n_out} is not a clip of whole windows, or window {c} is outside it")
+    lo = c * keep - S                                      # clip row of window frame 0
+    f0, f1 = max(0, -lo), min(T, n_out - lo)
+    if L.is_torch(motion):
+        import torch
+        wmask = torch.zeros((B, J, 1, T), dtype=torch.bool, device=motion.device)
+        wmotion = torch.zeros((B, J, 1, T), dtype=torch.float32, device=motion.device)
+        if f1 > f0:
+            wmask[:, :, 0, f0:f1] = (torch.as_tensor(mask, device=motion.device)[:, lo + f0:lo + f1] != 0).permute(0, 2, 1)
+            wmotion[:, :, 0, f0:f1] = motion[:, lo + f0:lo + f1].float().permute(0, 2, 1)
+        return wmask, wmotion
+    wmask, wmotion = np.zeros((B, J, 1, T), bool), np.zeros((B, J, 1, T), np.float32)
+    if f1 > f0:
+        wmask[:, :, 0, f0:f1] = (np.asarray(mask)[:, lo + f0:lo + f1] != 0).transpose(0, 2, 1)
+        wmotion[:, :, 0, f0:f1] = np.asarray(motion, np.float32)[:, lo + f0:lo + f1].transpose(0, 2, 1)
+    return wmask, wmotion
+
+
+def _constrained(y, cfg, mask, motion, c, keep_last_tail):
+    """`y` of window c with the clip-level constraint's slice in it (None: `y` as it is)"""
+    if mask is None and motion is None:
+        return y
+    if mask is None or motion is None:
+        raise ValueError("inpainting_mask and inpainted_motion go together")
+    wmask, wmotion = window_constraint(cfg, mask, motion, c, keep_last_tail)
+    return dict(y, inpainting_mask=wmask, inpainted_motion=wmotion)
+
+
+def _release_window_constraint(diffusion, models):
+    """after a host window loop that put a clip-level constraint's slices into y: the lanes' sticky window-level constraint
+    (`DSGDenoiser.set_inpainting`) goes with the clip it belonged to"""
+    for model in models:
+        inner = diffusion._library_model(model)[0]
+        if inner is not None and inner.inpainting:
+            inner.set_inpainting(None, None, 0)
+
+
+def _per_lane(masks, motions, n):
+    """the per-lane lists of the multi-lane drivers: (mask, motion) per lane, (None, None) for a lane without a constraint"""
+    if masks is None and motions is None:
+        return [(None, None)] * n
+    if masks is None or motions is None or len(masks) != n or len(motions) != n:
+        raise ValueError("inpainting_mask / inpainted_motion: one entry per lane each (an entry may be None)")
+    if any((mk is None) != (mo is None) for mk, mo in zip(masks, motions)):
+        raise ValueError("inpainting_mask and inpainted_motion go together")
+    return list(zip(masks, motions))
+
+
 def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, skip_timesteps=0, sample_fn=None,
-                  stream_id=0, seed_pose=None, device=None, *, windows="host", ddim=False, eta=0.0):
+                  stream_id=0, seed_pose=None, device=None, *, windows="host", ddim=False, eta=0.0, inpainting_mask=None,
+                  inpainted_motion=None):
     """ZEGGS window loop (sample.py:236-296).  feats: sequence of K per-window WavLM features, each [B, T, A_src]
     (torch cuda tensors or numpy); style: one-hot list or [B, 6] array.  Returns normalised poses
     [B, K*stride - n_seed, J] (numpy float32) -- B independent clips advance in lock step.  `ddim` / `eta`: the DDIM loop
-    instead of p_sample_loop (without a `sample_fn`); `windows`: see `_check_windows`."""
+    instead of p_sample_loop (without a `sample_fn`); `windows`: see `_check_windows`.  `inpainting_mask` / `inpainted_motion`
+    [B, K*stride - n_seed, J] (both or neither): motion inpainting over the whole clip, in the coordinates of the returned clip --
+    every window runs with `window_constraint(...)` as its y['inpainting_mask'] / y['inpainted_motion'] (host loop), or the library
+    cuts the same on the device (`windows="library"`)."""
     cfg = model.cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
@@ -122,7 +189,8 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
         diffusion.manual_seed(seed, stream_id)
         sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
         return diffusion.sample_clip(model, list(feats), sty, seed0=seed_pose, root_shift=smoothing, keep_last_tail=False,
-                                     ddim=ddim, eta=eta, skip_timesteps=skip_timesteps)
+                                     ddim=ddim, eta=eta, skip_timesteps=skip_timesteps, inpainting_mask=inpainting_mask,
+                                     inpainted_motion=inpainted_motion)
     sample_fn = sample_fn or _loop_fn(diffusion, ddim, eta)
     diffusion.manual_seed(seed, stream_id)          # torch.manual_seed(seed) at sample.py:212
     shape = (B, J, 1, T)
@@ -135,14 +203,18 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
     sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
     for c, feat in enumerate(feats):
         y = _zeggs_window_y(cfg, feat, sty, out[-1] if out else None, seed_pose, use_torch, mask)
+        y = _constrained(y, cfg, inpainting_mask, inpainted_motion, c, False)
         s = sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=skip_timesteps,
                       init_image=None, progress=False, dump_steps=None, noise=None, const_noise=False)
         _zeggs_stitch(out, s, S, smoothing, use_torch)
+    if inpainting_mask is not None:
+        _release_window_constraint(diffusion, [model])
     return _zeggs_finish(out, S, use_torch)
 
 
 def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456, smoothing=True, skip_timesteps=0,
-                           stream_ids=None, ddim=False, eta=0.0, kernel_set="recommended", *, windows="host"):
+                           stream_ids=None, ddim=False, eta=0.0, kernel_set="recommended", *, windows="host", inpainting_mask=None,
+                           inpainted_motion=None):
     """Several clips of one GPU advanced concurrently on sampling LANES ("one clip per stream", BASELINE config[3]): `lanes`
     are N DSGDenoiser lanes over one copy of the weights (`model.clone()`); lane i samples the B clips of
     feats_per_lane[i] (K per-window features [B, T, A_src]; B = 1: one clip per lane) on its own HSA queue and the library
@@ -152,8 +224,10 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
     lanes x this batch to every lane (sticky: `DSGDenoiser.set_kernel_set`), None leaves the lanes as they are, a name forces
     that set.  The command processor serves one queue per compute pipe: up to 4 lanes overlap, more than 4 share pipes and
     block each other (measured: 4 lanes 2.7x one lane, 8 lanes slower than one) -- put the remaining clips into the lanes'
-    batches.  Returns [N * B, K*stride - n_seed, J], lane-major."""
+    batches.  `inpainting_mask` / `inpainted_motion`: per-lane lists of clip-level constraints [B, K*stride - n_seed, J] as in
+    `generate_clip` (an entry may be None: that lane runs unconstrained).  Returns [N * B, K*stride - n_seed, J], lane-major."""
     n = len(lanes)
+    inp = _per_lane(inpainting_mask, inpainted_motion, n)
     cfg = lanes[0].cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     K = len(feats_per_lane[0])
@@ -176,15 +250,18 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
         if _check_windows(windows):
             return np.concatenate(diffusion.sample_clip_multi(list(lanes), [list(f) for f in feats_per_lane], stys, root_shift=smoothing,
                                                               keep_last_tail=False, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
-                                                              seeds=[seed] * n, stream_ids=stream_ids), axis=0)
+                                                              seeds=[seed] * n, stream_ids=stream_ids, inpainting_masks=[p[0] for p in inp],
+                                                              inpainted_motions=[p[1] for p in inp]), axis=0)
         outs = [[] for _ in range(n)]
         for c in range(K):
-            ys = [{"y": _zeggs_window_y(cfg, feats_per_lane[i][c], stys[i], outs[i][-1] if outs[i] else None, None, use_torch, mask)}
-                  for i in range(n)]
+            ys = [{"y": _constrained(_zeggs_window_y(cfg, feats_per_lane[i][c], stys[i], outs[i][-1] if outs[i] else None, None, use_torch, mask),
+                                     cfg, inp[i][0], inp[i][1], c, False)} for i in range(n)]
             ss = diffusion.p_sample_loop_multi(list(lanes), shape, ys, seeds=[seed] * n, stream_ids=stream_ids,
                                                skip_timesteps=skip_timesteps, ddim=ddim, eta=eta)
             for i in range(n):
                 _zeggs_stitch(outs[i], ss[i], S, smoothing, use_torch)
+        if inpainting_mask is not None:
+            _release_window_constraint(diffusion, lanes)
     return np.concatenate([_zeggs_finish(o, S, use_torch) for o in outs], axis=0)
 
 
@@ -248,7 +325,7 @@ def _dsgplus_stitch(out, s, S, use_torch):
 
 
 def _dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division, seed, stream_ids,
-                     skip_timesteps, ddim, eta):
+                     skip_timesteps, ddim, eta, inp=None):
     """The DSG+ clips of every lane through DSGDiffusion.sample_clip_multi: the per-window features as `_dsgplus_window_y` builds them,
     then crop + feature division as `_dsgplus_finish`."""
     cfg = lanes[0].cfg
@@ -257,7 +334,8 @@ def _dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, 
               for c in range(len(f))] for i, f in enumerate(feats_per_lane)]
     seqs = diffusion.sample_clip_multi(list(lanes), audio, [sty] * len(lanes), seed0s=list(seed0s), root_shift=False, keep_last_tail=True,
                                        ddim=ddim, eta=eta, skip_timesteps=skip_timesteps, seed_lasts=seed_lasts, seeds=[seed] * len(lanes),
-                                       stream_ids=stream_ids)
+                                       stream_ids=stream_ids, inpainting_masks=None if inp is None else [p[0] for p in inp],
+                                       inpainted_motions=None if inp is None else [p[1] for p in inp])
     return [np.ascontiguousarray(q[:, :real_n_frames, : cfg.njoints // feature_division], dtype=np.float32) for q in seqs]
 
 
@@ -275,13 +353,15 @@ def _dsgplus_finish(out, S, J, real_n_frames, feature_division, use_torch):
 
 def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, seed0s, real_n_frames, seed=123456, skip_timesteps=0,
                                    stream_ids=None, seed_lasts=None, feature_division=3, ddim=False, eta=0.0,
-                                   kernel_set="recommended", *, windows="host"):
+                                   kernel_set="recommended", *, windows="host", inpainting_mask=None, inpainted_motion=None):
     """`generate_clips_streams` for the DSG+ window loop (BEAT-TWH sample.py:98-192; all three model names of that tree): lane i
     samples the B clips of feats_per_lane[i] (K per-window features), seeded by seed0s[i] [B, J, 1, S] (and seed_lasts[i] for
     DiffuseStyleGesture++), on its own HSA queue; the lanes' step loops are interleaved by the library.  Lane i is bit-identical
     to `generate_clip_dsgplus(lanes[i], ..., stream_id=stream_ids[i])` run alone on the same lane under the same kernel set.
-    Returns [N * B, real_n_frames, J // feature_division], lane-major."""
+    `inpainting_mask` / `inpainted_motion`: per-lane lists of clip-level constraints [B, K*stride, J] as in `generate_clip_dsgplus`
+    (an entry may be None).  Returns [N * B, real_n_frames, J // feature_division], lane-major."""
     n = len(lanes)
+    inp = _per_lane(inpainting_mask, inpainted_motion, n)
     cfg = lanes[0].cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     K = len(feats_per_lane[0])
@@ -302,26 +382,32 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
         sty = _style_batch(styles, B, use_torch, dev)
         if _check_windows(windows):
             return np.concatenate(_dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division,
-                                                   seed, stream_ids, skip_timesteps, ddim, eta), axis=0)
+                                                   seed, stream_ids, skip_timesteps, ddim, eta, inp), axis=0)
         outs = [[] for _ in range(n)]
         for c in range(K):
-            ys = [{"y": _dsgplus_window_y(cfg, feats_per_lane[i], c, sty, seed0s[i] if c == 0 else outs[i][-1][..., -S:],
-                                          None if seed_lasts is None else seed_lasts[i], use_torch, mask)} for i in range(n)]
+            ys = [{"y": _constrained(_dsgplus_window_y(cfg, feats_per_lane[i], c, sty, seed0s[i] if c == 0 else outs[i][-1][..., -S:],
+                                                       None if seed_lasts is None else seed_lasts[i], use_torch, mask),
+                                     cfg, inp[i][0], inp[i][1], c, True)} for i in range(n)]
             ss = diffusion.p_sample_loop_multi(list(lanes), shape, ys, seeds=[seed] * n, stream_ids=stream_ids,
                                                skip_timesteps=skip_timesteps, ddim=ddim, eta=eta)
             for i in range(n):
                 _dsgplus_stitch(outs[i], ss[i], S, use_torch)
+        if inpainting_mask is not None:
+            _release_window_constraint(diffusion, lanes)
     return np.concatenate([_dsgplus_finish(o, S, J, real_n_frames, feature_division, use_torch) for o in outs], axis=0)
 
 
 def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, seed=123456, skip_timesteps=0,
-                          sample_fn=None, stream_id=0, seed_last=None, feature_division=3, *, windows="host", ddim=False, eta=0.0):
+                          sample_fn=None, stream_id=0, seed_last=None, feature_division=3, *, windows="host", ddim=False, eta=0.0,
+                          inpainting_mask=None, inpainted_motion=None):
     """DSG+ window loop (BEAT-TWH sample.py:98-192), attention4: zero-padded tail, no left audio context, GT seed for
     window 0, no root shift, last window kept whole, first S frames dropped, crop, keep the first J/3 features.
     `model.cfg.variant == 3` is that tree's "DiffuseStyleGesture" (attention3 at BEAT dims): S frames of left audio context.
     DiffuseStyleGesture++ (attention5, model.cfg.variant == 5): `feats` are still the stride-long windows; the last S
     feature frames of every window are dropped (sample.py:104, :138) and `seed_last` [B, J, 1, S] -- the same snippet
-    for every window (sample.py:85-93) -- is passed as y['seed_last']."""
+    for every window (sample.py:85-93) -- is passed as y['seed_last'].  `inpainting_mask` / `inpainted_motion` [B, K*stride, J]
+    (both or neither): motion inpainting over the whole clip as in `generate_clip`, in the coordinates of the stitched clip: the full J
+    features, before the crop to `real_n_frames` and the feature division."""
     cfg = model.cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
@@ -334,7 +420,9 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
     sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
     if library:
         return _dsgplus_library(diffusion, [model], [feats], sty, [seed0], None if seed_last is None else [seed_last], real_n_frames,
-                                feature_division, seed, [stream_id], skip_timesteps, ddim, eta)[0]
+                                feature_division, seed, [stream_id], skip_timesteps, ddim, eta,
+                                _per_lane(None if inpainting_mask is None else [inpainting_mask],
+                                          None if inpainted_motion is None else [inpainted_motion], 1))[0]
     if use_torch:
         import torch
         dev = feats[0].device
@@ -343,9 +431,12 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
         mask = np.ones((1, T), bool)
     for c in range(len(feats)):
         y = _dsgplus_window_y(cfg, feats, c, sty, seed0 if c == 0 else out[-1][..., -S:], seed_last, use_torch, mask)
+        y = _constrained(y, cfg, inpainting_mask, inpainted_motion, c, True)
         s = sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=skip_timesteps,
                       init_image=None, progress=False, dump_steps=None, noise=None, const_noise=False)
         _dsgplus_stitch(out, s, S, use_torch)
+    if inpainting_mask is not None:
+        _release_window_constraint(diffusion, [model])
     return _dsgplus_finish(out, S, J, real_n_frames, feature_division, use_torch)
 
 

@@ -27,6 +27,9 @@
  *   dsg_sample_clip / dsg_sample_clip_multi
  *        the window loop of inference(): seed hand-off, root shift,  main/mydiffusion_zeggs/sample.py:236-296,
  *        one-frame blend, stitching                                  BEAT-TWH-main/mydiffusion_beat_twh/sample.py:98-192
+ *   dsg_set_clip_inpainting
+ *        y['inpainting_mask'] / y['inpainted_motion'] of every window of that loop, given once in the stitched clip's frame
+ *        coordinates and cut per window on the device                main/diffusion/gaussian_diffusion.py:317-321
  *   dsg_clone / dsg_sample_multi / dsg_set_kernel_set / dsg_get_kernel_set / dsg_recommend_kernel_set / dsg_last_kernel_set
  *        (no reference counterpart: the reference samples one clip at a time, sample.py:418 batch_size = 1; these run
  *         several clips of one GPU concurrently over one copy of the weights -- BASELINE config[3] "one clip per stream")
@@ -224,8 +227,9 @@ int dsg_sample_multi(dsg_handle** lanes, int n, const dsg_sample_args* args, flo
  * the first S frames, n_out = K * (T - S) - S; keep_last_tail != 0 (DSG+) keeps the last window whole, n_out = K * (T - S).
  * args: as dsg_sample; draw_base is window 0's, window c draws from draw_base + c * (1 + n_run) -- what K consecutive dsg_sample
  * calls consume -- so the result is bit-identical to those K calls + the stitching of sample.py under the same kernel set.
- * DSG_E_INVALID: K < 1; a handle with an inpainting constraint (it is per window); step_noise, init_noise, init_image, n_dump,
- * first_step or max_steps in args (per-window tensors / pieces of one chain).  Variant 5 needs dsg_set_seed_last first.
+ * DSG_E_INVALID: K < 1; a handle with a window-level inpainting constraint (dsg_set_inpainting is per window; a whole clip takes
+ * dsg_set_clip_inpainting, below); step_noise, init_noise, init_image, n_dump, first_step or max_steps in args (per-window tensors /
+ * pieces of one chain).  Variant 5 needs dsg_set_seed_last first.
  * dsg_last_sample_ms afterwards: the sum over the K step loops, n_steps their total.  _multi: n lanes as dsg_sample_multi, one clip
  * batch each (styles[n], audios[n], outs[n], args[n]; seed0s / scales: NULL or n entries, each nullable), the windows advance in
  * lock step over the lanes.  Added without a version step, as dsg_set_inpainting: dsg_version() stays 330. */
@@ -235,6 +239,29 @@ int dsg_sample_clip(dsg_handle* h, const float* style, const float* seed0, const
 int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* const* styles, const float* const* seed0s,
                           const float* const* audios, const uint8_t* mask_local, int mask_batch, const float* const* scales,
                           const dsg_sample_args* args, int K, int root_shift, int keep_last_tail, float** outs, int B, void* stream);
+/* Motion inpainting over a whole clip, for dsg_sample_clip / _multi: mask uint8 [B, n_frames, J] (non-zero = keep the given motion), motion
+ * fp32 [B, n_frames, J]; host or device; frame-major, exactly the layout and frame numbering of dsg_sample_clip's `out`.  Sticky for the
+ * handle, like dsg_set_inpainting.  The library keeps its own device copy (allocated on first use, grown when needed, freed with the
+ * handle): the caller's buffers are free once `stream` has passed the call.  mask == NULL && motion == NULL switches it off (B, n_frames
+ * ignored); exactly one NULL, B > max_batch or n_frames < 1: DSG_E_INVALID.  A dsg_clone starts without a constraint; every lane of
+ * dsg_sample_clip_multi has its own, lanes without one run as before.  dsg_forward, dsg_sample and dsg_sample_multi ignore it.
+ * dsg_sample_clip / _multi on a handle that carries it need the same B and n_frames == n_out (K * (T - S) - S without keep_last_tail,
+ * K * (T - S) with it), else DSG_E_INVALID with both numbers in the message; a window-level constraint (dsg_set_inpainting) on the handle
+ * is refused by them as before.
+ * Semantics, keep = T - S: frame f of window c is clip row df = c * keep + f - S.  For 0 <= df < n_out the window's constraint at (b, j, f)
+ * is the clip's at (b, df, j); elsewhere -- the first S frames of window 0, the closing S frames of the last window when they are cut -- the
+ * frame is unconstrained.  The tail of window c (f >= keep) therefore carries the constraint of the rows window c + 1 will write: the seed
+ * it hands over honours it already.  The constraint acts where the window-level one does: after the guidance combination, before
+ * clip_denoised and the update.  Between two step loops the library cuts the next window's slice on the device (k_clip_inp_window); the
+ * result is bit-identical to K dsg_sample calls, each after dsg_set_inpainting with that window's slice, + the stitching of sample.py,
+ * under the same kernel set and the same draws.
+ * Root shift: with root_shift != 0 the three root-position channels (features 0..2) of windows c > 0 are constrained in the window's own
+ * frame, that is BEFORE the shift -- which is what the K-call sequence does; the stitched clip then holds the constrained value moved by
+ * the window's delta.  A caller who pins the root trajectory passes root_shift = 0.  Hand-off frames: when both sides of a hand-off frame
+ * (frame T - S of window c, frame 0 of window c + 1: one clip row) are constrained, they are constrained to the same value; the
+ * half-and-half blend then returns that value exactly, and the shift delta of a constrained root channel there is 0.
+ * Added without a version step, as dsg_set_inpainting: dsg_version() stays 330. */
+int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const float* motion, int B, int n_frames, void* stream);
 /* Kernel set of a handle (DSG_KSET_*; sticky; clones inherit the source's at dsg_clone).  dsg_recommend_kernel_set: the set
  * measured fastest for `lanes` lanes of batch B advanced together (lanes = 1: what DSG_KSET_AUTO picks) -- several lanes share
  * the CUs and prefer the throughput-shaped sets earlier; the caller applies it to each lane.  dsg_last_kernel_set: the set the
