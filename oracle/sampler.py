@@ -26,6 +26,57 @@ def _f(a, i):
     return np.float32(a[i])
 
 
+def p_coefs(diff: OracleDiffusion, i):
+    """(k1, k2, k3) of DDPM step i as fp32 numbers: posterior_mean_coef1 / 2 and nz * exp(0.5 * log variance), nz = 0 at schedule index 0."""
+    t = diff.t
+    nz = np.float32(0.0 if i == 0 else 1.0)
+    sig = np.exp(np.float32(0.5) * _f(t["posterior_log_variance_clipped"], i))
+    return _f(t["posterior_mean_coef1"], i), _f(t["posterior_mean_coef2"], i), nz * sig
+
+
+def ddim_coefs(diff: OracleDiffusion, i, eta):
+    """(k1 .. k5) of DDIM step i as fp32 numbers: sqrt_recip, sqrt_recipm1, sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), nz * sigma."""
+    t = diff.t
+    eta, one = np.float32(eta), np.float32(1.0)
+    ab, abp = _f(t["alphas_cumprod"], i), _f(t["alphas_cumprod_prev"], i)
+    sigma = eta * np.sqrt((one - abp) / (one - ab)) * np.sqrt(one - ab / abp)
+    nz = np.float32(0.0 if i == 0 else 1.0)
+    return (_f(t["sqrt_recip_alphas_cumprod"], i), _f(t["sqrt_recipm1_alphas_cumprod"], i), np.sqrt(abp),
+            np.sqrt(one - abp - sigma ** 2), nz * sigma)
+
+
+def p_step(diff: OracleDiffusion, i, x0, x_t, z, clip_denoised=False, const_noise=False, dtype=np.float32, grad=None):
+    """One iteration of p_sample_loop at schedule index i, given the model's x0 (after denoised_fn): clamp, posterior mean, [cond_fn
+    shift by `grad`], noise.  dtype float32: the loop's arithmetic, bit for bit.  float64: the SAME fp32-rounded coefficients, the
+    elementwise formula evaluated in double -- the yardstick of tests/stepcheck.py."""
+    k1, k2, k3 = (dtype(k) for k in p_coefs(diff, i))
+    x0, x_t, eps = np.asarray(x0, np.float32).astype(dtype), np.asarray(x_t, np.float32).astype(dtype), np.asarray(z, np.float32).astype(dtype)
+    if clip_denoised:                               # gaussian_diffusion.py:377-379
+        x0 = np.clip(x0, dtype(-1), dtype(1))
+    mean = k1 * x0 + k2 * x_t
+    if grad is not None:                            # condition_mean, gaussian_diffusion.py:428-441 (variance = posterior_variance: FIXED_SMALL)
+        mean = mean + dtype(_f(diff.t["posterior_variance"], i)) * np.asarray(grad, np.float32).astype(dtype)
+    if const_noise:
+        eps = np.repeat(eps[[0]], x0.shape[0], 0)
+    return mean + k3 * eps
+
+
+def ddim_step(diff: OracleDiffusion, i, x0, x_t, z, eta=0.0, clip_denoised=False, dtype=np.float32, grad=None):
+    """One iteration of ddim_sample_loop at schedule index i (gaussian_diffusion.py:742-792); dtype as in p_step."""
+    k1, k2, k3, k4, k5 = (dtype(k) for k in ddim_coefs(diff, i, eta))
+    x0, x_t, z = np.asarray(x0, np.float32).astype(dtype), np.asarray(x_t, np.float32).astype(dtype), np.asarray(z, np.float32).astype(dtype)
+    if clip_denoised:
+        x0 = np.clip(x0, dtype(-1), dtype(1))
+    eps = (k1 * x_t - x0) / k2
+    if grad is not None:                            # condition_score, gaussian_diffusion.py:458-480
+        g = np.asarray(grad, np.float32).astype(dtype)
+        eps = eps - np.sqrt(dtype(1) - dtype(_f(diff.t["alphas_cumprod"], i))) * g
+        x0 = k1 * x_t - k2 * eps
+        eps = (k1 * x_t - x0) / k2
+    mean = x0 * k3 + k4 * eps
+    return (mean + k5 * z).astype(dtype)
+
+
 def p_sample_loop(diff: OracleDiffusion, model, shape, noise_fn, model_kwargs, skip_timesteps=0,
                   init_image=None, noise=None, const_noise=False, dump_steps=None, clip_denoised=False, denoised_fn=None, cond_fn=None):
     t = diff.t
@@ -43,17 +94,8 @@ def p_sample_loop(diff: OracleDiffusion, model, shape, noise_fn, model_kwargs, s
         x0 = model(img, ts, **model_kwargs).astype(np.float32)
         if denoised_fn is not None:                     # gaussian_diffusion.py:364-366
             x0 = np.asarray(denoised_fn(x0), np.float32)
-        if clip_denoised:                               # gaussian_diffusion.py:377-379
-            x0 = np.clip(x0, np.float32(-1), np.float32(1))
-        mean = _f(t["posterior_mean_coef1"], i) * x0 + _f(t["posterior_mean_coef2"], i) * img
-        if cond_fn is not None:                         # condition_mean, gaussian_diffusion.py:428-441 (variance = posterior_variance: FIXED_SMALL)
-            mean = mean + _f(t["posterior_variance"], i) * np.asarray(cond_fn(img, ts, **model_kwargs), np.float32)
-        eps = noise_fn(1 + n).astype(np.float32)
-        if const_noise:
-            eps = np.repeat(eps[[0]], shape[0], 0)
-        nz = np.float32(0.0 if i == 0 else 1.0)
-        sig = np.exp(np.float32(0.5) * _f(t["posterior_log_variance_clipped"], i))
-        img = mean + nz * sig * eps
+        grad = None if cond_fn is None else np.asarray(cond_fn(img, ts, **model_kwargs), np.float32)
+        img = p_step(diff, i, x0, img, noise_fn(1 + n), clip_denoised, const_noise, grad=grad)
         if dump_steps is not None and n in dump_steps:
             dump.append(img.copy())
     return dump if dump_steps is not None else img
@@ -70,26 +112,13 @@ def ddim_sample_loop(diff: OracleDiffusion, model, shape, noise_fn, model_kwargs
         i0 = indices[0]
         img = _f(t["sqrt_alphas_cumprod"], i0) * np.asarray(init_image, np.float32) \
             + _f(t["sqrt_one_minus_alphas_cumprod"], i0) * img
-    eta = np.float32(eta)
-    one = np.float32(1.0)
     for n, i in enumerate(indices):
         ts = np.full((shape[0],), diff.timestep_map[i], dtype=np.int64)
         x0 = model(img, ts, **model_kwargs).astype(np.float32)
         if denoised_fn is not None:
             x0 = np.asarray(denoised_fn(x0), np.float32)
-        if clip_denoised:
-            x0 = np.clip(x0, np.float32(-1), np.float32(1))
-        eps = (_f(t["sqrt_recip_alphas_cumprod"], i) * img - x0) / _f(t["sqrt_recipm1_alphas_cumprod"], i)
-        if cond_fn is not None:                         # condition_score, gaussian_diffusion.py:458-480
-            eps = eps - np.sqrt(one - _f(t["alphas_cumprod"], i)) * np.asarray(cond_fn(img, ts, **model_kwargs), np.float32)
-            x0 = _f(t["sqrt_recip_alphas_cumprod"], i) * img - _f(t["sqrt_recipm1_alphas_cumprod"], i) * eps
-            eps = (_f(t["sqrt_recip_alphas_cumprod"], i) * img - x0) / _f(t["sqrt_recipm1_alphas_cumprod"], i)
-        ab, abp = _f(t["alphas_cumprod"], i), _f(t["alphas_cumprod_prev"], i)
-        sigma = eta * np.sqrt((one - abp) / (one - ab)) * np.sqrt(one - ab / abp)
-        z = noise_fn(1 + n).astype(np.float32)
-        mean = x0 * np.sqrt(abp) + np.sqrt(one - abp - sigma ** 2) * eps
-        nz = np.float32(0.0 if i == 0 else 1.0)
-        img = (mean + nz * sigma * z).astype(np.float32)
+        grad = None if cond_fn is None else np.asarray(cond_fn(img, ts, **model_kwargs), np.float32)
+        img = ddim_step(diff, i, x0, img, noise_fn(1 + n), eta, clip_denoised, grad=grad)
     return img
 
 
