@@ -164,6 +164,11 @@ struct dsg_handle {
     // cinpB == 0: off.  Allocated on first use, grown when needed (cinp_cap elements).  dsg_sample_clip cuts window c's constraint out of it into
     // inp32 / inp_mask (k_clip_inp_window); inpB stays 0 outside that call
     int cinpB = 0, cinp_frames = 0; float* cinp_motion = nullptr; unsigned char* cinp_mask = nullptr; size_t cinp_cap = 0;
+    // clip-level init motion (dsg_set_clip_init): the library's own copy [cinitB][cinit_frames][J] in the stitched clip's coordinates; cinitB == 0:
+    // off.  Allocated on first use, grown when needed (cinit_cap elements).  Only dsg_sample_clip reads it: clip_init_c >= 0 (the window being
+    // started, for the windows of that call only) makes sample_prepare launch k_clip_x_in in place of k_x_in
+    int cinitB = 0, cinit_frames = 0; float* cinit_motion = nullptr; size_t cinit_cap = 0;
+    int clip_init_c = -1, clip_init_n_out = 0;
     int last_path = -1;                  // submission path of the last dsg_sample: 0 HIP launches, 1 AQL packets, 2 hipGraph replay
     bool last_nofence = false;           // ... and whether its packets went without fences
     int kset_req = DSG_KSET_AUTO;        // dsg_set_kernel_set: the kernel set every step of this handle runs (AUTO: by batch, select_kernels)
@@ -2092,6 +2097,20 @@ static int launch_x_in(dsg_handle* h, const float* x, const float* init, int do_
     HIPCHK(hipGetLastError());
     return 0;
 }
+// window h->clip_init_c of a clip that starts from the handle's clip-level init motion (dsg_sample_clip): cut + q_sample + state write
+static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, unsigned draw, int B, const KernelSel& ks) {
+    ClipXInArgs a;
+    a.init = h->cinit_motion; a.c_seed = h->c_seed; a.qa = qa; a.qb = qb; a.nkey = nk; a.draw = draw;
+    a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.S = h->S; a.n_out = h->clip_init_n_out; a.c = h->clip_init_c;
+    a.xs32 = h->xs32; a.xsA = is_bf16(h) ? h->xsA : nullptr;
+    a.dupB = h->cfgB; a.xs_frag = ks.xs_frag ? 1 : 0;
+    const size_t n = (size_t)B * h->T * (h->Jp / 4);
+    const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
+    if (is_bf16(h)) hipLaunchKernelGGL((k_clip_x_in<PBF16>), dim3(grid), dim3(256), 0, h->stream, a);
+    else hipLaunchKernelGGL((k_clip_x_in<PF32>), dim3(grid), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 static int launch_x_out(dsg_handle* h, float* dst_dev, int B) {
     const size_t n = (size_t)B * h->J * h->T;
     hipLaunchKernelGGL(k_x_out, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, h->xs32,
@@ -2200,6 +2219,37 @@ extern "C" int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const
     CHK(upload(h, h->cinp_motion, motion, n * sizeof(float)));
     CHK(upload(h, h->cinp_mask, mask, n));
     h->cinpB = B; h->cinp_frames = n_frames;
+    CHK(order_before(h, stream));
+    return 0;
+}
+
+// The motion a whole clip is re-denoised from, for dsg_sample_clip / _multi (init_image of every window of the loop, gaussian_diffusion.py:
+// 701-713): motion fp32 [B, n_frames, J] in the coordinates of the stitched clip, host or device.  The library keeps its own copy (the caller's
+// buffer is free once `stream` has passed the call); every window starts from q_sample of its slice (k_clip_x_in).  Sticky until switched off
+// (NULL); dsg_forward / dsg_sample / _multi ignore it.
+extern "C" int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int n_frames, void* stream) {
+    if (!h) return fail(DSG_E_INVALID, "null handle");
+    if (!motion) { h->cinitB = 0; h->cinit_frames = 0; return 0; }
+    if (B <= 0 || B > h->Bmax) return fail(DSG_E_INVALID, "batch exceeds max_batch");
+    if (n_frames < 1) return fail(DSG_E_INVALID, "dsg_set_clip_init: n_frames < 1");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    h->cinitB = 0; h->cinit_frames = 0;      // (a call that fails below leaves it off, not half written)
+    const size_t n = (size_t)B * n_frames * h->J;
+    if (n > h->cinit_cap) {
+        // grown: the old copy goes back at once (nothing on the handle's stream may still read it)
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->cinit_motion) {
+            void* old = h->cinit_motion;
+            h->cinit_motion = nullptr; h->cinit_cap = 0;
+            h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), old), h->allocs.end());
+            (void)hipFree(old);
+        }
+        CHK(dalloc(h, &h->cinit_motion, n, false));
+        h->cinit_cap = n;
+    }
+    CHK(order_after(h, stream));
+    CHK(upload(h, h->cinit_motion, motion, n * sizeof(float)));
+    h->cinitB = B; h->cinit_frames = n_frames;
     CHK(order_before(h, stream));
     return 0;
 }
@@ -2394,8 +2444,11 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     KernelSel ksel;
     CHK(select_kernels(h, rows, ksel));      // (first: the layout of the state shadow belongs to the kernel set)
     CHK(ensure_set_buffers(h, ksel));
-    CHK(launch_x_in(h, noise_d, init_d, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0],
-                    noise_d ? 0 : 1, nk, a->draw_base, B, ksel));
+    if (h->clip_init_c >= 0)      // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
+        CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, a->draw_base, B, ksel));
+    else
+        CHK(launch_x_in(h, noise_d, init_d, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0],
+                        noise_d ? 0 : 1, nk, a->draw_base, B, ksel));
     // replayed per-step noise
     const float* ext = nullptr;
     if (a->step_noise) {
@@ -2675,6 +2728,11 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
         if (h->cinpB > 0 && h->cinp_frames != n_out)
             return fail(DSG_E_INVALID, "dsg_sample_clip: the clip has n_out = " + std::to_string(n_out) + " frames, the constraint of dsg_set_clip_inpainting n_frames = " +
                                        std::to_string(h->cinp_frames));
+        if (h->cinitB > 0 && h->cinitB != B)
+            return fail(DSG_E_INVALID, "dsg_sample_clip: batch " + std::to_string(B) + " differs from the batch of dsg_set_clip_init (" + std::to_string(h->cinitB) + ")");
+        if (h->cinitB > 0 && h->cinit_frames != n_out)
+            return fail(DSG_E_INVALID, "dsg_sample_clip: the clip has n_out = " + std::to_string(n_out) + " frames, the init motion of dsg_set_clip_init n_frames = " +
+                                       std::to_string(h->cinit_frames));
     }
     HIPCHK(hipSetDevice(hs[0]->cfg.device));
     std::vector<float*> clip(n);
@@ -2709,12 +2767,20 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
         ClipInpaintNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) {}
         ~ClipInpaintNow() { for (int i = 0; i < n; ++i) hs[i]->inpB = 0; }
     } clip_inpaint_now(hs, n);
+    // Lanes with a clip-level init motion: sample_prepare starts window c from q_sample of its slice (k_clip_x_in reads c_seed for the frames in
+    // front of the clip: window 0's y['seed'], uploaded above on the same stream).  clip_init_c is -1 outside this call, on error returns too
+    struct ClipInitNow {
+        dsg_handle** hs; int n;
+        ClipInitNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) {}
+        ~ClipInitNow() { for (int i = 0; i < n; ++i) hs[i]->clip_init_c = -1; }
+    } clip_init_now(hs, n);
     for (int c = 0; c < K; ++c) {
         for (int i = 0; i < n; ++i) {
             dsg_handle* h = hs[i];
             const float* audio_c = audios[i] + (size_t)c * B * h->Ta * h->As;
             CHK(set_window_cond(h, styles[i], h->c_seed, audio_c, mask_local, mask_batch, B, 0, scales ? scales[i] : nullptr, stream));
             if (h->cinpB > 0) { CHK(launch_clip_inp_window(h, B, n_out, c)); h->inpB = B; }
+            if (h->cinitB > 0) { h->clip_init_c = c; h->clip_init_n_out = n_out; }
             wargs[i].draw_base = args[i].draw_base + (uint32_t)c * (uint32_t)(1 + n_run);      // what K consecutive dsg_sample calls consume
         }
         for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, jobs[i]));

@@ -1582,6 +1582,11 @@ struct XInArgs {
     int dupB;               // classifier-free guidance: batch element b is also written to row b + dupB (its unconditional twin)
     int xs_frag;            // xsA fragment-major (see GemmArgs::xs_frag)
 };
+// q_sample of one element (gaussian_diffusion.py:706-713): spelled ONCE for k_x_in and k_clip_x_in -- two copies of a sum of two products
+// may be contracted into FMAs differently (or not at all, once the vectorizer has paired the products), and the two kernels promise the
+// same bits for the same inputs.  The form k_x_in has always compiled to is written out: qa * init rounded on its own (it used to sit
+// behind the `init != NULL` branch, out of the contraction's reach), qb * z fused with the sum
+__device__ __forceinline__ float q_sample1(float qa, float init, float qb, float z) { return __builtin_fmaf(qb, z, qa * init); }
 template <class P>
 __global__ void k_x_in(const XInArgs a) {
     typedef typename P::elem elem;
@@ -1602,7 +1607,7 @@ __global__ void k_x_in(const XInArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (j0 + e < a.J)
-                        z[e] = (a.init ? a.qa * a.init[((size_t)b * a.J + j0 + e) * a.T + f] : 0.f) + a.qb * z[e];
+                        z[e] = q_sample1(a.qa, a.init ? a.init[((size_t)b * a.J + j0 + e) * a.T + f] : 0.f, a.qb, z[e]);
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) if (j0 + e >= a.J) z[e] = 0.f;
@@ -1750,6 +1755,54 @@ __global__ void k_clip_inp_window(const ClipInpArgs a) {
         }
         *(f32x4*)(a.inp32 + bf * a.Jp + j0) = v;
         *(unsigned*)(a.inp_mask + bf * a.Jp + j0) = mk;
+    }
+}
+// The start of one window of a clip that is re-denoised from an existing clip (dsg_set_clip_init; init_image + skip_timesteps of
+// p_sample_loop, gaussian_diffusion.py:701-713, for every window of the loop): in place of k_x_in, one launch that fuses the window cut,
+// q_sample and the write of the sampler state.  init [B][n_out][J] is in the coordinates of the stitched clip -- frame-major like the state,
+// so a feature quad is one contiguous read (k_x_in reads its [B][J][T] init with stride T) and no [B][J][T] staging tensor exists.  Window c,
+// frame f is clip row df = c * (T - S) + f - S, the walk of k_clip_inp_window.  Outside the clip: df < 0 (window 0, f < S: the frames the seed
+// poses stand for) takes y['seed'] of window 0, c_seed[b][j][f]; df >= n_out (the cut tail of the last window) holds clip row n_out - 1.
+// x = q_sample1(qa, init, qb, z), z = Philox draw `draw` at k_x_in's counter; written as k_x_in writes: xs32 [B][T][Jp] with the padded
+// columns 0, the shadow xsA in the kernel set's layout, the guidance twins.  Same inputs, same bits as k_x_in.  Loads as clip_inp_load4.
+struct ClipXInArgs {
+    const float* init; const float* c_seed;
+    float qa, qb;
+    NoiseKey nkey; unsigned draw;
+    int B, J, Jp, Jq, T, S, n_out, c;
+    float* xs32; void* xsA;
+    int dupB, xs_frag;
+};
+template <class P>
+__global__ void k_clip_x_in(const ClipXInArgs a) {
+    typedef typename P::elem elem;
+    const int nq = a.Jp / 4, keep = a.T - a.S;
+    const size_t n = (size_t)a.B * a.T * nq;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int j0 = (int)(i % nq) * 4;
+        const size_t bf = i / nq;
+        const int f = (int)(bf % a.T), b = (int)(bf / a.T);
+        f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (j0 < a.J) {
+            const int nv = a.J - j0 < 4 ? a.J - j0 : 4;
+            const int df = a.c * keep + f - a.S;
+            f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (df < 0) {                                   // (window 0 only, and there f < S)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (e < nv) v[e] = a.c_seed[((size_t)b * a.J + j0 + e) * a.S + f];
+            } else {
+                v = clip_inp_load4(a.init + ((size_t)b * a.n_out + (df < a.n_out ? df : a.n_out - 1)) * a.J + j0, nv);
+            }
+            z = philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) z[e] = e < nv ? q_sample1(a.qa, v[e], a.qb, z[e]) : 0.f;
+        }
+        *(f32x4*)(a.xs32 + ((size_t)b * a.T + f) * a.Jp + j0) = z;
+        if (a.xsA) P::store4((elem*)a.xsA + xs_off<P>(b * a.T + f, j0, a.Jp, a.xs_frag), z);
+        if (a.dupB > 0) {
+            *(f32x4*)(a.xs32 + ((size_t)(b + a.dupB) * a.T + f) * a.Jp + j0) = z;
+            if (a.xsA) P::store4((elem*)a.xsA + xs_off<P>((b + a.dupB) * a.T + f, j0, a.Jp, a.xs_frag), z);
+        }
     }
 }
 // Self-check of the fence-free hand-off (dsg_hip.cpp: uc_selfcheck): `buf` is uncached device memory; the two kernels run as

@@ -320,7 +320,8 @@ class DSGDiffusion:
 
     # ---- a whole clip per library call (dsg_sample_clip): the window loops of sample.py inside the library -----------------
     def sample_clip(self, model, feats, style, *, seed0=None, root_shift, keep_last_tail, ddim=False, eta=0.0, skip_timesteps=0,
-                    clip_denoised=False, scale=None, seed_last=None, mask_local="ones", inpainting_mask=None, inpainted_motion=None):
+                    clip_denoised=False, scale=None, seed_last=None, mask_local="ones", inpainting_mask=None, inpainted_motion=None,
+                    init_motion=None):
         """All K windows of B clips in ONE library call: per-window conditioning, step loop, seed hand-off, root shift (`root_shift`,
         the ZEGGS loop's `smoothing`), one-frame blend and stitching on the device (k_window_handoff).  `feats`: the K per-window
         features exactly as y['audio'] takes them, each [B, T_a, A_src] (stacked once into [K, B, T_a, A_src]); `style` [B, style_dim_in];
@@ -332,7 +333,11 @@ class DSGDiffusion:
         `inpainting_mask` / `inpainted_motion` [B, n_out, J] (numpy or torch; both or neither): motion inpainting over the whole clip, in
         the coordinates of the returned clip -- every window runs with the y['inpainting_mask'] / y['inpainted_motion'] that
         `sample.window_constraint` cuts out of them, cut on the device (`DSGDenoiser.set_clip_inpainting`; set before the call, cleared
-        after it)."""
+        after it).
+        `init_motion` [B, n_out, J] (numpy or torch): an existing clip to edit, in the coordinates of the returned clip -- every window
+        starts from q_sample of its slice (`sample.window_init`: the `init_image` of that window's loop) instead of pure noise, noised to
+        the first timestep `skip_timesteps` leaves; cut, noised and written as the sampler state by one kernel per window
+        (`DSGDenoiser.set_clip_init`; set before the call, cleared after it)."""
         if (inpainting_mask is None) != (inpainted_motion is None):
             raise ValueError("sample_clip: inpainting_mask and inpainted_motion go together")
         return self.sample_clip_multi([model], [feats], [style], seed0s=None if seed0 is None else [seed0], root_shift=root_shift,
@@ -340,14 +345,16 @@ class DSGDiffusion:
                                       clip_denoised=clip_denoised, scales=None if scale is None else [scale],
                                       seed_lasts=None if seed_last is None else [seed_last], mask_local=mask_local,
                                       stream_ids=[self.stream_id], inpainting_masks=None if inpainting_mask is None else [inpainting_mask],
-                                      inpainted_motions=None if inpainted_motion is None else [inpainted_motion])[0]
+                                      inpainted_motions=None if inpainted_motion is None else [inpainted_motion],
+                                      init_motions=None if init_motion is None else [init_motion])[0]
 
     def sample_clip_multi(self, models, feats_per_lane, styles, *, seed0s=None, root_shift, keep_last_tail, ddim=False, eta=0.0,
                           skip_timesteps=0, clip_denoised=False, scales=None, seed_lasts=None, mask_local="ones", seeds=None,
-                          stream_ids=None, inpainting_masks=None, inpainted_motions=None):
+                          stream_ids=None, inpainting_masks=None, inpainted_motions=None, init_motions=None):
         """`sample_clip` for several lanes at once (dsg_sample_clip_multi; lanes as in `p_sample_loop_multi`): lane i samples the B
         clips of feats_per_lane[i] from the Philox stream (seeds[i], stream_ids[i]); the windows advance in lock step over the lanes.
         `inpainting_masks` / `inpainted_motions`: one [B, n_out, J] pair per lane, entries may be None (that lane runs unconstrained).
+        `init_motions`: one [B, n_out, J] clip per lane to start from, entries may be None (that lane starts from noise).
         Returns one [B, n_out, J] array per lane."""
         models = list(models)
         n = len(models)
@@ -358,6 +365,9 @@ class DSGDiffusion:
         inp = [(None, None)] * n if inpainting_masks is None else list(zip(inpainting_masks, inpainted_motions))
         if len(inp) != n or any((mk is None) != (mo is None) for mk, mo in inp):
             raise ValueError("sample_clip: one inpainting mask and one motion per lane (or None for both)")
+        inits = [None] * n if init_motions is None else list(init_motions)
+        if len(inits) != n:
+            raise ValueError("sample_clip: one init motion per lane (or None)")
         K = len(feats_per_lane[0])
         if K < 1 or any(len(f) != K for f in feats_per_lane):
             raise ValueError("the same number of windows (>= 1) for every lane")
@@ -446,6 +456,13 @@ class DSGDiffusion:
                     m.set_clip_inpainting(mk, mo, B)
                 elif m.clip_inpainting:
                     m.set_clip_inpainting(None, None, 0)
+            for m, init in zip(inners, inits):
+                if init is not None:
+                    if tuple(init.shape) != (B, n_out, J):
+                        raise ValueError(f"clip init_motion shape {tuple(init.shape)} != {(B, n_out, J)}")
+                    m.set_clip_init(init, B)
+                elif m.clip_init:
+                    m.set_clip_init(None, 0)
             if n == 1:
                 lib.check(lib.cdll.dsg_sample_clip(ptrs["h"][0], ptrs["style"][0], ptrs["seed0"][0], ptrs["audio"][0], mbuf.p, mb, ptrs["scale"][0],
                                                    C.byref(args[0]), K, int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"][0], B, stream))
@@ -456,6 +473,8 @@ class DSGDiffusion:
             for m in inners:
                 if m.clip_inpainting:
                     m.set_clip_inpainting(None, None, 0)
+                if m.clip_init:
+                    m.set_clip_init(None, 0)
         self._draw += K * (1 + n_run)
         self._last_model = inners[0]
         return outs

@@ -55,6 +55,7 @@ SYMBOLS = {
     "dsg_sample": (_I, [_P, C.POINTER(dsg_sample_args), _P, _I, _P]),
     "dsg_sample_multi": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_sample_args), C.POINTER(_P), _I, _P]),
     "dsg_set_clip_inpainting": (_I, [_P, _P, _P, _I, _I, _P]),
+    "dsg_set_clip_init": (_I, [_P, _P, _I, _I, _P]),
     "dsg_sample_clip": (_I, [_P, _P, _P, _P, _P, _I, _P, C.POINTER(dsg_sample_args), _I, _I, _I, _P, _I, _P]),
     "dsg_sample_clip_multi": (_I, [C.POINTER(_P), _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _I, C.POINTER(_P),
                                    C.POINTER(dsg_sample_args), _I, _I, _I, C.POINTER(_P), _I, _P]),

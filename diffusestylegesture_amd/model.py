@@ -40,6 +40,7 @@ class DSGDenoiser:
         self._source = _clone_of          # keeps the weight owner alive as long as any lane exists
         self.inpainting = False           # this lane holds an inpainting constraint (set_inpainting)
         self._clip_inpainting = False     # ... a clip-level one (set_clip_inpainting)
+        self._clip_init = False           # ... a clip-level init motion (set_clip_init)
         if _clone_of is not None:
             h = C.c_void_p()
             self.lib.check(self.lib.cdll.dsg_clone(_clone_of.handle, max_batch, C.byref(h)))
@@ -196,6 +197,28 @@ class DSGDenoiser:
     def clip_inpainting(self) -> bool:
         """This lane holds a clip-level inpainting constraint (`set_clip_inpainting`)."""
         return self._clip_inpainting
+
+    def set_clip_init(self, motion, batch: int):
+        """The clip `DSGDiffusion.sample_clip` re-denoises (dsg_set_clip_init): `motion` [batch, n_out, njoints] in the coordinates of the
+        stitched clip that call returns; every window then starts from q_sample of its slice (`sample.window_init` is the rule) instead of
+        pure noise -- `init_image` + `skip_timesteps` of the window loops, for the whole clip.  Sticky for this lane;
+        `set_clip_init(None, 0)` switches it off.  The single-window loops ignore it.  `DSGDiffusion.sample_clip` sets it from its own
+        keyword and clears it afterwards."""
+        if motion is None:
+            self.lib.check(self.lib.cdll.dsg_set_clip_init(self.handle, None, 0, 0, None))
+            self._clip_init = False
+            return
+        vbuf = L.Buf(motion)
+        shape = tuple(vbuf.obj.shape)
+        if len(shape) != 3 or shape[0] != batch or shape[1] < 1 or shape[2] != self.njoints:
+            raise ValueError(f"clip init_motion shape {shape} != ({batch}, n_out, {self.njoints})")
+        self.lib.check(self.lib.cdll.dsg_set_clip_init(self.handle, vbuf.p, batch, shape[1], L.current_stream_ptr() if L.is_torch(motion) else None))
+        self._clip_init = True
+
+    @property
+    def clip_init(self) -> bool:
+        """This lane holds a clip-level init motion (`set_clip_init`)."""
+        return self._clip_init
 
     def _alloc_out(self, shape, use_torch):
         if use_torch:

@@ -141,6 +141,58 @@ def window_constraint(cfg, mask, motion, c, keep_last_tail):
     return wmask, wmotion
 
 
+def window_init(cfg, init, seed0, c, keep_last_tail):
+    """Window c's `init_image` [B, J, 1, T] cut out of a clip-level init motion `init` [B, n_out, J] given in the coordinates of the stitched
+    clip (n_out = K * stride - S, or K * stride with `keep_last_tail`: the DSG+ loops) -- the clip that is noised to the first timestep and
+    sampled back (gaussian_diffusion.py:701-713, for every window of the loop).  Frame f of window c is clip row df = c * stride + f - S;
+    for 0 <= df < n_out the window's init at (b, j, f) is the clip's at (b, df, j).  Outside the clip: df < 0 (window 0, f < S: the frames
+    the seed poses stand for) takes y['seed'] of window 0, `seed0` [B, J, 1, S] at (b, j, f), zeros without one; df >= n_out (the cut tail
+    of the last window) holds clip row n_out - 1.  numpy or torch, as `init` is given; what the library does on the device for
+    `windows="library"` (dsg_set_clip_init)."""
+    S, T, J, keep = cfg.n_seed, cfg.n_poses, cfg.njoints, cfg.n_poses - cfg.n_seed
+    if len(init.shape) != 3 or int(init.shape[2]) != J:
+        raise ValueError(f"clip init_motion: shape {tuple(init.shape)} must be [B, n_out, {J}]")
+    B, n_out = int(init.shape[0]), int(init.shape[1])
+    K, rest = divmod(n_out + (0 if keep_last_tail else S), keep)
+    if rest or K < 1 or not 0 <= c < K:
+        raise ValueError(f"clip init_motion: n_out = {n_out} is not a clip of whole windows, or window {c} is outside it")
+    if seed0 is not None and tuple(seed0.shape) != (B, J, 1, S):
+        raise ValueError(f"clip init_motion: seed0 shape {tuple(seed0.shape)} != {(B, J, 1, S)}")
+    lo = c * keep - S                                      # clip row of window frame 0
+    f0, f1 = max(0, -lo), min(T, n_out - lo)               # window frames [f0, f1) lie inside the clip (f1 > f0: 2 * S < T)
+    if L.is_torch(init):
+        import torch
+        w = torch.zeros((B, J, 1, T), dtype=torch.float32, device=init.device)
+        w[:, :, 0, f0:f1] = init[:, lo + f0:lo + f1].float().permute(0, 2, 1)
+        if f0 > 0 and seed0 is not None:
+            w[:, :, 0, :f0] = torch.as_tensor(seed0, device=init.device).float()[:, :, 0, :f0]
+        if f1 < T:
+            w[:, :, 0, f1:] = init[:, n_out - 1].float()[:, :, None]
+        return w
+    init = np.asarray(init, np.float32)
+    w = np.zeros((B, J, 1, T), np.float32)
+    w[:, :, 0, f0:f1] = init[:, lo + f0:lo + f1].transpose(0, 2, 1)
+    if f0 > 0 and seed0 is not None:
+        w[:, :, 0, :f0] = (seed0.detach().cpu().numpy() if L.is_torch(seed0) else np.asarray(seed0, np.float32))[:, :, 0, :f0]
+    if f1 < T:
+        w[:, :, 0, f1:] = init[:, n_out - 1][:, :, None]
+    return w
+
+
+def _window_init(cfg, init, seed0, c, keep_last_tail):
+    """`init_image` of window c (None without a clip-level init motion)"""
+    return None if init is None else window_init(cfg, init, seed0, c, keep_last_tail)
+
+
+def _per_lane_init(init_motion, n):
+    """the per-lane list of the multi-lane drivers: one init motion per lane, None for a lane that starts from noise"""
+    if init_motion is None:
+        return [None] * n
+    if len(init_motion) != n:
+        raise ValueError("init_motion: one entry per lane (an entry may be None)")
+    return list(init_motion)
+
+
 def _constrained(y, cfg, mask, motion, c, keep_last_tail):
     """`y` of window c with the clip-level constraint's slice in it (None: `y` as it is)"""
     if mask is None and motion is None:
@@ -173,14 +225,16 @@ def _per_lane(masks, motions, n):
 
 def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, skip_timesteps=0, sample_fn=None,
                   stream_id=0, seed_pose=None, device=None, *, windows="host", ddim=False, eta=0.0, inpainting_mask=None,
-                  inpainted_motion=None):
+                  inpainted_motion=None, init_motion=None):
     """ZEGGS window loop (sample.py:236-296).  feats: sequence of K per-window WavLM features, each [B, T, A_src]
     (torch cuda tensors or numpy); style: one-hot list or [B, 6] array.  Returns normalised poses
     [B, K*stride - n_seed, J] (numpy float32) -- B independent clips advance in lock step.  `ddim` / `eta`: the DDIM loop
     instead of p_sample_loop (without a `sample_fn`); `windows`: see `_check_windows`.  `inpainting_mask` / `inpainted_motion`
     [B, K*stride - n_seed, J] (both or neither): motion inpainting over the whole clip, in the coordinates of the returned clip --
     every window runs with `window_constraint(...)` as its y['inpainting_mask'] / y['inpainted_motion'] (host loop), or the library
-    cuts the same on the device (`windows="library"`)."""
+    cuts the same on the device (`windows="library"`).  `init_motion` [B, K*stride - n_seed, J]: an existing clip to edit, in the
+    coordinates of the returned clip -- every window is noised from `window_init(...)` as its `init_image` to the timestep
+    `skip_timesteps` leaves and sampled back (host loop), or the library cuts and noises the same on the device (`windows="library"`)."""
     cfg = model.cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
@@ -190,7 +244,7 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
         sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
         return diffusion.sample_clip(model, list(feats), sty, seed0=seed_pose, root_shift=smoothing, keep_last_tail=False,
                                      ddim=ddim, eta=eta, skip_timesteps=skip_timesteps, inpainting_mask=inpainting_mask,
-                                     inpainted_motion=inpainted_motion)
+                                     inpainted_motion=inpainted_motion, init_motion=init_motion)
     sample_fn = sample_fn or _loop_fn(diffusion, ddim, eta)
     diffusion.manual_seed(seed, stream_id)          # torch.manual_seed(seed) at sample.py:212
     shape = (B, J, 1, T)
@@ -205,7 +259,8 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
         y = _zeggs_window_y(cfg, feat, sty, out[-1] if out else None, seed_pose, use_torch, mask)
         y = _constrained(y, cfg, inpainting_mask, inpainted_motion, c, False)
         s = sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=skip_timesteps,
-                      init_image=None, progress=False, dump_steps=None, noise=None, const_noise=False)
+                      init_image=_window_init(cfg, init_motion, seed_pose, c, False), progress=False, dump_steps=None, noise=None,
+                      const_noise=False)
         _zeggs_stitch(out, s, S, smoothing, use_torch)
     if inpainting_mask is not None:
         _release_window_constraint(diffusion, [model])
@@ -214,7 +269,7 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
 
 def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456, smoothing=True, skip_timesteps=0,
                            stream_ids=None, ddim=False, eta=0.0, kernel_set="recommended", *, windows="host", inpainting_mask=None,
-                           inpainted_motion=None):
+                           inpainted_motion=None, init_motion=None):
     """Several clips of one GPU advanced concurrently on sampling LANES ("one clip per stream", BASELINE config[3]): `lanes`
     are N DSGDenoiser lanes over one copy of the weights (`model.clone()`); lane i samples the B clips of
     feats_per_lane[i] (K per-window features [B, T, A_src]; B = 1: one clip per lane) on its own HSA queue and the library
@@ -225,9 +280,11 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
     that set.  The command processor serves one queue per compute pipe: up to 4 lanes overlap, more than 4 share pipes and
     block each other (measured: 4 lanes 2.7x one lane, 8 lanes slower than one) -- put the remaining clips into the lanes'
     batches.  `inpainting_mask` / `inpainted_motion`: per-lane lists of clip-level constraints [B, K*stride - n_seed, J] as in
-    `generate_clip` (an entry may be None: that lane runs unconstrained).  Returns [N * B, K*stride - n_seed, J], lane-major."""
+    `generate_clip` (an entry may be None: that lane runs unconstrained); `init_motion`: a per-lane list of clips to edit as in
+    `generate_clip` (an entry may be None: that lane starts from noise).  Returns [N * B, K*stride - n_seed, J], lane-major."""
     n = len(lanes)
     inp = _per_lane(inpainting_mask, inpainted_motion, n)
+    inits = _per_lane_init(init_motion, n)
     cfg = lanes[0].cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     K = len(feats_per_lane[0])
@@ -251,13 +308,14 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
             return np.concatenate(diffusion.sample_clip_multi(list(lanes), [list(f) for f in feats_per_lane], stys, root_shift=smoothing,
                                                               keep_last_tail=False, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
                                                               seeds=[seed] * n, stream_ids=stream_ids, inpainting_masks=[p[0] for p in inp],
-                                                              inpainted_motions=[p[1] for p in inp]), axis=0)
+                                                              inpainted_motions=[p[1] for p in inp], init_motions=inits), axis=0)
         outs = [[] for _ in range(n)]
         for c in range(K):
             ys = [{"y": _constrained(_zeggs_window_y(cfg, feats_per_lane[i][c], stys[i], outs[i][-1] if outs[i] else None, None, use_torch, mask),
                                      cfg, inp[i][0], inp[i][1], c, False)} for i in range(n)]
             ss = diffusion.p_sample_loop_multi(list(lanes), shape, ys, seeds=[seed] * n, stream_ids=stream_ids,
-                                               skip_timesteps=skip_timesteps, ddim=ddim, eta=eta)
+                                               skip_timesteps=skip_timesteps, ddim=ddim, eta=eta,
+                                               init_images=[_window_init(cfg, inits[i], None, c, False) for i in range(n)])
             for i in range(n):
                 _zeggs_stitch(outs[i], ss[i], S, smoothing, use_torch)
         if inpainting_mask is not None:
@@ -325,7 +383,7 @@ def _dsgplus_stitch(out, s, S, use_torch):
 
 
 def _dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division, seed, stream_ids,
-                     skip_timesteps, ddim, eta, inp=None):
+                     skip_timesteps, ddim, eta, inp=None, inits=None):
     """The DSG+ clips of every lane through DSGDiffusion.sample_clip_multi: the per-window features as `_dsgplus_window_y` builds them,
     then crop + feature division as `_dsgplus_finish`."""
     cfg = lanes[0].cfg
@@ -335,7 +393,7 @@ def _dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, 
     seqs = diffusion.sample_clip_multi(list(lanes), audio, [sty] * len(lanes), seed0s=list(seed0s), root_shift=False, keep_last_tail=True,
                                        ddim=ddim, eta=eta, skip_timesteps=skip_timesteps, seed_lasts=seed_lasts, seeds=[seed] * len(lanes),
                                        stream_ids=stream_ids, inpainting_masks=None if inp is None else [p[0] for p in inp],
-                                       inpainted_motions=None if inp is None else [p[1] for p in inp])
+                                       inpainted_motions=None if inp is None else [p[1] for p in inp], init_motions=inits)
     return [np.ascontiguousarray(q[:, :real_n_frames, : cfg.njoints // feature_division], dtype=np.float32) for q in seqs]
 
 
@@ -353,15 +411,18 @@ def _dsgplus_finish(out, S, J, real_n_frames, feature_division, use_torch):
 
 def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, seed0s, real_n_frames, seed=123456, skip_timesteps=0,
                                    stream_ids=None, seed_lasts=None, feature_division=3, ddim=False, eta=0.0,
-                                   kernel_set="recommended", *, windows="host", inpainting_mask=None, inpainted_motion=None):
+                                   kernel_set="recommended", *, windows="host", inpainting_mask=None, inpainted_motion=None,
+                                   init_motion=None):
     """`generate_clips_streams` for the DSG+ window loop (BEAT-TWH sample.py:98-192; all three model names of that tree): lane i
     samples the B clips of feats_per_lane[i] (K per-window features), seeded by seed0s[i] [B, J, 1, S] (and seed_lasts[i] for
     DiffuseStyleGesture++), on its own HSA queue; the lanes' step loops are interleaved by the library.  Lane i is bit-identical
     to `generate_clip_dsgplus(lanes[i], ..., stream_id=stream_ids[i])` run alone on the same lane under the same kernel set.
     `inpainting_mask` / `inpainted_motion`: per-lane lists of clip-level constraints [B, K*stride, J] as in `generate_clip_dsgplus`
-    (an entry may be None).  Returns [N * B, real_n_frames, J // feature_division], lane-major."""
+    (an entry may be None); `init_motion`: a per-lane list of clips [B, K*stride, J] to edit (an entry may be None).  Returns
+    [N * B, real_n_frames, J // feature_division], lane-major."""
     n = len(lanes)
     inp = _per_lane(inpainting_mask, inpainted_motion, n)
+    inits = _per_lane_init(init_motion, n)
     cfg = lanes[0].cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     K = len(feats_per_lane[0])
@@ -382,14 +443,15 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
         sty = _style_batch(styles, B, use_torch, dev)
         if _check_windows(windows):
             return np.concatenate(_dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division,
-                                                   seed, stream_ids, skip_timesteps, ddim, eta, inp), axis=0)
+                                                   seed, stream_ids, skip_timesteps, ddim, eta, inp, inits), axis=0)
         outs = [[] for _ in range(n)]
         for c in range(K):
             ys = [{"y": _constrained(_dsgplus_window_y(cfg, feats_per_lane[i], c, sty, seed0s[i] if c == 0 else outs[i][-1][..., -S:],
                                                        None if seed_lasts is None else seed_lasts[i], use_torch, mask),
                                      cfg, inp[i][0], inp[i][1], c, True)} for i in range(n)]
             ss = diffusion.p_sample_loop_multi(list(lanes), shape, ys, seeds=[seed] * n, stream_ids=stream_ids,
-                                               skip_timesteps=skip_timesteps, ddim=ddim, eta=eta)
+                                               skip_timesteps=skip_timesteps, ddim=ddim, eta=eta,
+                                               init_images=[_window_init(cfg, inits[i], seed0s[i], c, True) for i in range(n)])
             for i in range(n):
                 _dsgplus_stitch(outs[i], ss[i], S, use_torch)
         if inpainting_mask is not None:
@@ -399,7 +461,7 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
 
 def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, seed=123456, skip_timesteps=0,
                           sample_fn=None, stream_id=0, seed_last=None, feature_division=3, *, windows="host", ddim=False, eta=0.0,
-                          inpainting_mask=None, inpainted_motion=None):
+                          inpainting_mask=None, inpainted_motion=None, init_motion=None):
     """DSG+ window loop (BEAT-TWH sample.py:98-192), attention4: zero-padded tail, no left audio context, GT seed for
     window 0, no root shift, last window kept whole, first S frames dropped, crop, keep the first J/3 features.
     `model.cfg.variant == 3` is that tree's "DiffuseStyleGesture" (attention3 at BEAT dims): S frames of left audio context.
@@ -407,7 +469,8 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
     feature frames of every window are dropped (sample.py:104, :138) and `seed_last` [B, J, 1, S] -- the same snippet
     for every window (sample.py:85-93) -- is passed as y['seed_last'].  `inpainting_mask` / `inpainted_motion` [B, K*stride, J]
     (both or neither): motion inpainting over the whole clip as in `generate_clip`, in the coordinates of the stitched clip: the full J
-    features, before the crop to `real_n_frames` and the feature division."""
+    features, before the crop to `real_n_frames` and the feature division.  `init_motion` [B, K*stride, J]: an existing clip to edit as in
+    `generate_clip`, in the same coordinates (the full J features, K*stride frames)."""
     cfg = model.cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
@@ -422,7 +485,8 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
         return _dsgplus_library(diffusion, [model], [feats], sty, [seed0], None if seed_last is None else [seed_last], real_n_frames,
                                 feature_division, seed, [stream_id], skip_timesteps, ddim, eta,
                                 _per_lane(None if inpainting_mask is None else [inpainting_mask],
-                                          None if inpainted_motion is None else [inpainted_motion], 1))[0]
+                                          None if inpainted_motion is None else [inpainted_motion], 1),
+                                None if init_motion is None else [init_motion])[0]
     if use_torch:
         import torch
         dev = feats[0].device
@@ -433,7 +497,8 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
         y = _dsgplus_window_y(cfg, feats, c, sty, seed0 if c == 0 else out[-1][..., -S:], seed_last, use_torch, mask)
         y = _constrained(y, cfg, inpainting_mask, inpainted_motion, c, True)
         s = sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=skip_timesteps,
-                      init_image=None, progress=False, dump_steps=None, noise=None, const_noise=False)
+                      init_image=_window_init(cfg, init_motion, seed0, c, True), progress=False, dump_steps=None, noise=None,
+                      const_noise=False)
         _dsgplus_stitch(out, s, S, use_torch)
     if inpainting_mask is not None:
         _release_window_constraint(diffusion, [model])
@@ -523,7 +588,21 @@ def build_parser():
     p.add_argument('--timestep_respacing', default='')
     p.add_argument('--windows', default='host', choices=['host', 'library'],
                    help='host = one library call per window, stitched on the host (default); library = the whole clip in one library call')
+    p.add_argument('--skip_timesteps', type=int, default=0, help='start the denoising this many timesteps below the last one')
+    p.add_argument('--init_npy', default='',
+                   help='edit an existing clip: normalised poses [n_out, J] or [1, n_out, J] (n_out = K * stride - n_seed, what --save_dir/*_poses.npy '
+                        'holds) are noised to the timestep --skip_timesteps leaves and sampled back under this run\'s style and audio')
     return p
+
+
+def load_init_npy(path, n_out, J, B=1):
+    """--init_npy: normalised poses [n_out, J] (one clip, repeated for every clip of the batch) or [B, n_out, J]"""
+    a = np.asarray(np.load(path), np.float32)
+    if a.ndim == 2:
+        a = np.repeat(a[None], B, 0)
+    if a.shape != (B, n_out, J):
+        raise SystemExit(f"--init_npy: shape {a.shape} is not [{n_out}, {J}] or [{B}, {n_out}, {J}]")
+    return np.ascontiguousarray(a)
 
 
 def main(argv=None):
@@ -562,7 +641,9 @@ def main(argv=None):
     if args.max_len:
         feats = feats[: max(1, args.max_len // (n_poses - ZEGGS.n_seed))]
     feats_t = [torch.from_numpy(f[None]).cuda(dev) for f in feats]
-    poses = generate_clip(model, diffusion, feats_t, style, seed=123456, smoothing=True, windows=args.windows)[0]
+    init = load_init_npy(args.init_npy, len(feats_t) * ZEGGS.stride - ZEGGS.n_seed, ZEGGS.njoints) if args.init_npy else None
+    poses = generate_clip(model, diffusion, feats_t, style, seed=123456, smoothing=True, skip_timesteps=args.skip_timesteps,
+                          windows=args.windows, init_motion=init)[0]
     stem = os.path.join(args.save_dir, os.path.splitext(name)[0])
     np.save(stem + "_poses.npy", poses)
     # de-normalise (sample.py:320-326) and write the .bvh (process_zeggs_bvh.py:219) like the reference's main()

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from .config import DSGPLUS_CONFIGS
-from .sample import generate_clip_dsgplus
+from .sample import generate_clip_dsgplus, load_init_npy
 
 
 def seed_features(seed_gesture, mean, std):
@@ -72,6 +72,10 @@ def build_parser():
     p.add_argument('--mean_std_npz', default='', help="v2: file with `mean` and `std` [motion_dim] (the reference's gesture_BEAT_mean_v2.npy / _std_v2.npy)")
     p.add_argument('--windows', default='host', choices=['host', 'library'],
                    help='host = one library call per window, stitched on the host (default); library = the whole clip in one library call')
+    p.add_argument('--init_npy', default='',
+                   help='edit an existing clip: normalised model features [K * stride, njoints] or [1, K * stride, njoints] (the stitched clip before '
+                        'the crop and the feature division) are noised to the timestep --skip_timesteps leaves and sampled back under this run\'s '
+                        'conditioning')
     return p
 
 
@@ -111,8 +115,10 @@ def main(argv=None):
         seed_last = torch.from_numpy(mk_seed(np.load(args.seed_last_npy))).cuda(dev)
     style = np.zeros(cfg.style_dim_in, np.float32)
     style[args.speaker] = 1.0
+    init = load_init_npy(args.init_npy, len(feats) * cfg.stride, cfg.njoints) if args.init_npy else None
     seq = generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n, seed=123456, skip_timesteps=args.skip_timesteps,
-                                seed_last=seed_last, feature_division=1 if args.version == 'v2' else 3, windows=args.windows)[0]
+                                seed_last=seed_last, feature_division=1 if args.version == 'v2' else 3, windows=args.windows,
+                                init_motion=init)[0]
     out_poses = np.multiply(seq, std) + mean                                  # sample.py:184 (no clipping of std here)
     os.makedirs(args.save_dir, exist_ok=True)
     stem = os.path.join(args.save_dir, os.path.splitext(os.path.basename(args.features_npy))[0])

@@ -30,6 +30,9 @@
  *   dsg_set_clip_inpainting
  *        y['inpainting_mask'] / y['inpainted_motion'] of every window of that loop, given once in the stitched clip's frame
  *        coordinates and cut per window on the device                main/diffusion/gaussian_diffusion.py:317-321
+ *   dsg_set_clip_init
+ *        init_image (+ skip_timesteps) of every window of that loop, given once as a clip in the stitched clip's frame
+ *        coordinates: x_t = q_sample(init_image, t, noise)            main/diffusion/gaussian_diffusion.py:701-713
  *   dsg_clone / dsg_sample_multi / dsg_set_kernel_set / dsg_get_kernel_set / dsg_recommend_kernel_set / dsg_last_kernel_set
  *        (no reference counterpart: the reference samples one clip at a time, sample.py:418 batch_size = 1; these run
  *         several clips of one GPU concurrently over one copy of the weights -- BASELINE config[3] "one clip per stream")
@@ -229,7 +232,7 @@ int dsg_sample_multi(dsg_handle** lanes, int n, const dsg_sample_args* args, flo
  * calls consume -- so the result is bit-identical to those K calls + the stitching of sample.py under the same kernel set.
  * DSG_E_INVALID: K < 1; a handle with a window-level inpainting constraint (dsg_set_inpainting is per window; a whole clip takes
  * dsg_set_clip_inpainting, below); step_noise, init_noise, init_image, n_dump, first_step or max_steps in args (per-window tensors /
- * pieces of one chain).  Variant 5 needs dsg_set_seed_last first.
+ * pieces of one chain; a whole clip to start from takes dsg_set_clip_init, below).  Variant 5 needs dsg_set_seed_last first.
  * dsg_last_sample_ms afterwards: the sum over the K step loops, n_steps their total.  _multi: n lanes as dsg_sample_multi, one clip
  * batch each (styles[n], audios[n], outs[n], args[n]; seed0s / scales: NULL or n entries, each nullable), the windows advance in
  * lock step over the lanes.  Added without a version step, as dsg_set_inpainting: dsg_version() stays 330. */
@@ -262,6 +265,29 @@ int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* const* styles,
  * half-and-half blend then returns that value exactly, and the shift delta of a constrained root channel there is 0.
  * Added without a version step, as dsg_set_inpainting: dsg_version() stays 330. */
 int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const float* motion, int B, int n_frames, void* stream);
+/* Editing an existing clip, for dsg_sample_clip / _multi: the motion every window is re-denoised from -- init_image + skip_timesteps of
+ * p_sample_loop (main/diffusion/gaussian_diffusion.py:701-713, x_t = q_sample(init_image, t, noise)) for the whole window loop.  motion fp32
+ * [B, n_frames, J], host or device; frame-major, exactly the layout and frame numbering of dsg_sample_clip's `out`.  Sticky for the handle.
+ * The library keeps its own device copy (allocated on first use, grown when needed, freed with the handle): the caller's buffer is free
+ * once `stream` has passed the call.  motion == NULL switches it off (B, n_frames ignored); B > max_batch or n_frames < 1: DSG_E_INVALID.
+ * A dsg_clone starts without one; every lane of dsg_sample_clip_multi has its own, lanes without one run as before.  dsg_forward,
+ * dsg_sample and dsg_sample_multi ignore it.
+ * dsg_sample_clip / _multi on a handle that carries it need the same B and n_frames == n_out, else DSG_E_INVALID with both numbers in the
+ * message.  Window c then starts from q_sample(slice_c, t_start, noise) with t_start = the first timestep the call runs (skip_timesteps
+ * == 0 is allowed: the last timestep, as in the reference) and noise = draw draw_base + c * (1 + n_run) -- the draw K dsg_sample calls
+ * with init_image would use; the draw accounting is unchanged.  args.init_image / init_noise stay refused.  It combines with
+ * dsg_set_clip_inpainting, with guidance (the unconditional twins receive the same start) and with DDIM.
+ * The slice, keep = T - S: frame f of window c is clip row df = c * keep + f - S; for 0 <= df < n_frames the init value at (b, j, f) is
+ * the clip's at (b, df, j).  Rows outside the clip:
+ *   df < 0          (window 0, frames f < S: the frames the seed poses stand for in training)  y['seed'] of window 0 at (b, j, f) -- the
+ *                   caller's seed0, or the zeros the call puts there without one;
+ *   df >= n_frames  (the closing S frames of the last window, without keep_last_tail only)     clip row n_frames - 1, a held pose.
+ * The cut, q_sample and the write of the sampler state are one kernel (k_clip_x_in) per window; the result is bit-identical to K dsg_sample
+ * calls, each with init_image = that window's slice as [B, J, 1, T], + the stitching of sample.py, under the same kernel set and draws.
+ * Root shift: with root_shift != 0 the slice is taken in the window's own frame, that is BEFORE the shift -- which is what the K-call
+ * sequence does: windows c > 0 start from the given root trajectory and the hand-off then moves them by the window's delta.
+ * Added without a version step, as the two inpainting setters: dsg_version() stays 330. */
+int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int n_frames, void* stream);
 /* Kernel set of a handle (DSG_KSET_*; sticky; clones inherit the source's at dsg_clone).  dsg_recommend_kernel_set: the set
  * measured fastest for `lanes` lanes of batch B advanced together (lanes = 1: what DSG_KSET_AUTO picks) -- several lanes share
  * the CUs and prefer the throughput-shaped sets earlier; the caller applies it to each lane.  dsg_last_kernel_set: the set the
