@@ -184,6 +184,10 @@ struct dsg_handle {
     int* ctr = nullptr;                  // scratch counter for diagnostics
     StepCtl* ctl = nullptr;              // device-resident step control (dsg_kernels.h: StepCtl)
     int* t_arr = nullptr; unsigned* dyn = nullptr;
+    // per-element noise streams (dsg_set_noise_streams): nkB user batch elements, 0 = off; nkeys = their keys {seed lo, seed hi, stream lo,
+    // stream hi} (nk_seeds == false: the seed words come from args->seed, per call).  dyn_host: the staging copy of `dyn`
+    // (8 + 4 * max_batch words) every sampling call uploads
+    int nkB = 0; bool nk_seeds = false; std::vector<unsigned> nkeys, dyn_host;
     int latency_mode = -1;               // dsg_config.latency_mode: -1 auto, 0 never the LATENCY set, 1 always
 #ifndef DSG_EMU
     dsg_aql::Ctx aql;                    // hand-written AQL submission of the step loop (dsg_aql.h)
@@ -217,7 +221,7 @@ struct dsg_handle {
     bool st_valid = false; int st_mode = -1, st_skip = -1; float st_eta = 0.f;      // what the device tables hold
     Sched sched;
     // graphs: key = (B, out_mode, mask batch, const_noise, steps, flags, kernel set) -> exec
-    // (flags: 1 clip_denoised, 2 guidance, 4 no mask_local, 8 k_attn_mid, 16 no noise, 32 inpainting on -- the captured pose head carries the constraint's pointers)
+    // (flags: 1 clip_denoised, 2 guidance, 4 no mask_local, 8 k_attn_mid, 16 no noise, 32 inpainting on -- the captured pose head carries the constraint's pointers, 64 keyed noise)
     // n_run is part of the key: the captured kernels carry the step-table length as an argument (n_tab); so is the kernel set
     // (a graph captured under one set must never be replayed for a call that asked for another)
     // (round-4 advisor: n_run = the steps of THIS call, n_tab = the length of the whole chain = what the captured kernels clamp their
@@ -611,7 +615,8 @@ extern "C" int dsg_create(const dsg_config* c, dsg_handle** out) {
     CHK(dalloc(h, &h->mask, (size_t)B * h->T));
     CHK(dalloc(h, &h->ctr, 8));
     CHK(dalloc(h, &h->cfg_scale, (size_t)B));
-    CHK(dalloc(h, &h->dyn, 8));
+    CHK(dalloc(h, &h->dyn, 8 + 4 * (size_t)B));      // + the key table of keyed noise (GemmArgs::dyn)
+    h->dyn_host.assign(8 + 4 * (size_t)B, 0u);
     CHK(dalloc(h, &h->t_arr, (size_t)B));
     // the xs32 master is read as a GEMM operand in fp32 mode: rows padded to a 16-row tile exist (allocated above)
     return 0;
@@ -1252,6 +1257,7 @@ extern "C" int dsg_last_kernel_set(dsg_handle* h, int* set) {
 struct StepCtx {
     int B;                  // batch rows the kernels run on (with guidance: conditional elements + their twins)
     int out_mode; bool use_ctr; const float* ext_noise; int const_noise;
+    int keyed = 0;          // per-element noise streams (dsg_set_noise_streams)
     int no_noise = 0;       // DDIM with eta = 0: no step adds noise (the pose head skips the Philox draw)
     int clip_x0 = 0;        // clip_denoised=True
     int inpaint = 0;        // the handle's inpainting constraint applies (sampling only: MDM.forward does not inpaint)
@@ -1900,7 +1906,7 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
     {   // final LayerNorm-on-read + pose head + sampler update
         GemmArgs g = gemm_pose_head(h, z, M, h->layers[h->L - 1]);
         step_ctl(h, g, ctl);
-        g.out_mode = c.out_mode; g.ext_noise = c.ext_noise; g.const_noise = c.const_noise; g.clip_x0 = c.clip_x0; g.no_noise = c.no_noise;
+        g.out_mode = c.out_mode; g.ext_noise = c.ext_noise; g.const_noise = c.const_noise; g.keyed = c.keyed; g.clip_x0 = c.clip_x0; g.no_noise = c.no_noise;
         g.xs_frag = ks.xs_frag ? 1 : 0;
         if (c.inpaint) { g.inp32 = h->inp32; g.inp_mask = h->inp_mask; }      // every pose-head form below reads the same GemmArgs
         h->fence_next = 2;     // the last packet of a step writes the state (state_fences)
@@ -2084,8 +2090,9 @@ static int run_step_p(dsg_handle* h, const StepCtx& c) {
 }
 
 static int launch_x_in(dsg_handle* h, const float* x, const float* init, int do_q, float qa, float qb, int use_philox,
-                       NoiseKey nk, unsigned draw, int B, const KernelSel& ks) {
+                       NoiseKey nk, const unsigned* keys, unsigned draw, int B, const KernelSel& ks) {
     XInArgs a;
+    a.keys = keys;
     a.dupB = h->cfgB; a.xs_frag = ks.xs_frag ? 1 : 0;
     a.x = x; a.init = init; a.do_q = do_q; a.qa = qa; a.qb = qb; a.use_philox = use_philox; a.nkey = nk; a.draw = draw;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.xs32 = h->xs32;
@@ -2098,8 +2105,9 @@ static int launch_x_in(dsg_handle* h, const float* x, const float* init, int do_
     return 0;
 }
 // window h->clip_init_c of a clip that starts from the handle's clip-level init motion (dsg_sample_clip): cut + q_sample + state write
-static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, unsigned draw, int B, const KernelSel& ks) {
+static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, const unsigned* keys, unsigned draw, int B, const KernelSel& ks) {
     ClipXInArgs a;
+    a.keys = keys;
     a.init = h->cinit_motion; a.c_seed = h->c_seed; a.qa = qa; a.qb = qb; a.nkey = nk; a.draw = draw;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.S = h->S; a.n_out = h->clip_init_n_out; a.c = h->clip_init_c;
     a.xs32 = h->xs32; a.xsA = is_bf16(h) ? h->xsA : nullptr;
@@ -2254,6 +2262,29 @@ extern "C" int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int 
     return 0;
 }
 
+// Per-element noise streams ("keyed noise") for dsg_sample / _multi / dsg_sample_clip / _multi: element b of the batch draws from
+// (seeds[b], stream_ids[b]) with the batch term of the Philox counter 0 -- draw d at (f, j) = philox4x32_10(ctr = ((f Jq + j) >> 2, d,
+// sid_b lo, sid_b hi), key = (seed_b lo, seed_b hi)) + Box-Muller, the [1, J, 1, T] tensor of its pair -- so its noise is exactly the noise it
+// gets sampled alone (B = 1) with args->seed = seeds[b], args->stream_id = stream_ids[b], whichever batch, slot and lane it rides in.  Draw
+// indices stay per call (draw_base, draw_base + 1 + i, a clip's window c from draw_base + c (1 + n_run)).  Host arrays, copied here; the
+// table reaches the device with the `dyn` block of every sampling call (sample_prepare).  Reference counterpart: none (th.randn consumes one
+// global generator, gaussian_diffusion.py:704, :542).
+extern "C" int dsg_set_noise_streams(dsg_handle* h, const uint64_t* seeds, const uint64_t* stream_ids, int B) {
+    if (!h) return fail(DSG_E_INVALID, "null handle");
+    if (!seeds && !stream_ids) { h->nkB = 0; return 0; }
+    if (B < 1 || B > h->Bmax)
+        return fail(DSG_E_INVALID, "dsg_set_noise_streams: batch " + std::to_string(B) + " outside 1 .. max_batch (" + std::to_string(h->Bmax) + ")");
+    h->nkeys.assign(4 * (size_t)B, 0u);
+    for (int b = 0; b < B; ++b) {
+        const uint64_t sd = seeds ? seeds[b] : 0, id = stream_ids ? stream_ids[b] : 0;
+        h->nkeys[4 * b] = (unsigned)(sd & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(sd >> 32);
+        h->nkeys[4 * b + 2] = (unsigned)(id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(id >> 32);
+    }
+    h->nk_seeds = seeds != nullptr;
+    h->nkB = B;
+    return 0;
+}
+
 extern "C" int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, float* out, int B, void* stream) {
     if (!h || !x || !t || !out) return fail(DSG_E_INVALID, "dsg_forward: null argument");
     if (!h->finalized || !h->cond_set) return fail(DSG_E_STATE, "dsg_forward before finalize / set_window_cond");
@@ -2281,7 +2312,7 @@ extern "C" int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, floa
     StepCtx c; c.B = rows; c.out_mode = OUT_FORWARD; c.use_ctr = false; c.ext_noise = nullptr; c.const_noise = 0;
     CHK(select_kernels(h, rows, c.ks));
     CHK(ensure_set_buffers(h, c.ks));
-    CHK(launch_x_in(h, xd, nullptr, 0, 0.f, 0.f, 0, nk, 0, B, c.ks));
+    CHK(launch_x_in(h, xd, nullptr, 0, 0.f, 0.f, 0, nk, nullptr, 0, B, c.ks));
     CHK(run_step_p(h, c));
     CHK(from_dev(h, out, h->fwd_out, n));
     CHK(order_before(h, stream));
@@ -2414,6 +2445,8 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     int rows = 0;
     CHK(rows_for(h, B, &rows));
     if (h->inpB > 0 && h->inpB != B) return fail(DSG_E_INVALID, "batch differs from the batch of dsg_set_inpainting");
+    if (h->nkB > 0 && h->nkB != B)
+        return fail(DSG_E_INVALID, "batch " + std::to_string(B) + " differs from the batch of dsg_set_noise_streams (" + std::to_string(h->nkB) + ")");
     if (a->mode != DSG_MODE_DDPM && a->mode != DSG_MODE_DDIM) return fail(DSG_E_INVALID, "mode");
     // (dump points are allowed with DDIM: ddim_sample_loop_progressive is built on them; the Python ddim_sample_loop itself
     // refuses dump_steps like the reference, gaussian_diffusion.py:913-916)
@@ -2444,11 +2477,25 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     KernelSel ksel;
     CHK(select_kernels(h, rows, ksel));      // (first: the layout of the state shadow belongs to the kernel set)
     CHK(ensure_set_buffers(h, ksel));
+    // what the loop reads from device memory instead of its arguments: the call's key, the draw index of step 0 and, with per-element noise
+    // streams, the key table (const_noise: element 0's stream for everyone) -- uploaded here because the start kernels read the table too
+    const int keyed = h->nkB > 0 ? 1 : 0;
+    {
+        unsigned* dyn = h->dyn_host.data();
+        dyn[0] = nk.k0; dyn[1] = nk.k1; dyn[2] = nk.s0; dyn[3] = nk.s1; dyn[4] = a->draw_base + 1u;
+        for (int b = 0; b < h->nkB; ++b) {
+            const unsigned* k = h->nkeys.data() + 4 * (a->const_noise ? 0 : b);
+            dyn[8 + 4 * b] = h->nk_seeds ? k[0] : nk.k0; dyn[9 + 4 * b] = h->nk_seeds ? k[1] : nk.k1;
+            dyn[10 + 4 * b] = k[2]; dyn[11 + 4 * b] = k[3];
+        }
+        HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? 8 + 4 * (size_t)h->nkB : 5) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    }
+    const unsigned* keys_d = keyed ? h->dyn + 8 : nullptr;
     if (h->clip_init_c >= 0)      // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
-        CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, a->draw_base, B, ksel));
+        CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, a->draw_base, B, ksel));
     else
         CHK(launch_x_in(h, noise_d, init_d, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0],
-                        noise_d ? 0 : 1, nk, a->draw_base, B, ksel));
+                        noise_d ? 0 : 1, nk, keys_d, a->draw_base, B, ksel));
     // replayed per-step noise
     const float* ext = nullptr;
     if (a->step_noise) {
@@ -2463,15 +2510,11 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(64), 0, h->stream, h->ctl, h->st_tmodel, first);
     HIPCHK(hipGetLastError());
     HP_LAP(1);
-    {
-        const unsigned dyn[5] = {nk.k0, nk.k1, nk.s0, nk.s1, a->draw_base + 1u};
-        HIPCHK(hipMemcpyAsync(h->dyn, dyn, sizeof(dyn), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
+    HIPCHK(hipStreamSynchronize(h->stream));      // (the upload of `dyn` above has landed)
     HP_LAP(2);
     StepCtx& c = job.c;
     c.B = rows; c.out_mode = a->mode == DSG_MODE_DDPM ? OUT_DDPM : OUT_DDIM; c.use_ctr = true; c.ext_noise = ext;
-    c.const_noise = a->const_noise; c.clip_x0 = a->clip_denoised ? 1 : 0;
+    c.const_noise = a->const_noise; c.keyed = keyed; c.clip_x0 = a->clip_denoised ? 1 : 0;
     c.no_noise = (a->mode == DSG_MODE_DDIM && a->eta == 0.f && !ext) ? 1 : 0;
     c.inpaint = h->inpB > 0 ? 1 : 0;      // (the AQL argument blocks are recorded anew below for every call: on / off needs no invalidation)
     c.ks = ksel;
@@ -2527,7 +2570,7 @@ static int sample_run_hip(dsg_handle* h, const dsg_sample_args* a, SampleJob& jo
     if (spg > 0 && n_run >= spg && job.done == 0) {
         // everything that varies between calls (step index, coefficients, noise key, conditioning) lives in device
         // memory, so one captured graph per (batch, sampler, mask batch, const_noise, steps, flags, kernel set) serves every window and clip
-        dsg_handle::GKey key = {c.B, c.out_mode, h->mb, c.const_noise, n_run, h->n_run, (c.clip_x0 ? 1 : 0) | (h->cfgB ? 2 : 0) | (h->nomask ? 4 : 0) | (c.ks.attn_in_mid ? 8 : 0) | (c.no_noise ? 16 : 0) | (c.inpaint ? 32 : 0),
+        dsg_handle::GKey key = {c.B, c.out_mode, h->mb, c.const_noise, n_run, h->n_run, (c.clip_x0 ? 1 : 0) | (h->cfgB ? 2 : 0) | (h->nomask ? 4 : 0) | (c.ks.attn_in_mid ? 8 : 0) | (c.no_noise ? 16 : 0) | (c.inpaint ? 32 : 0) | (c.keyed ? 64 : 0),
                                 c.ks.set};
         auto it = h->graphs.find(key);
         bool ok = true;
@@ -2853,17 +2896,13 @@ extern "C" int dsg_last_sample_fence_free(dsg_handle* h, int* fence_free) {
 
 // the framework's noise stream as a tensor (what the fused sampler consumes for draw index `draw`): out [B, J, 1, T], device
 // memory (written on `stream`) or host memory (generated on the device, copied back, synchronous)
-extern "C" int dsg_noise(float* out, int B, int J, int T, uint64_t seed, uint64_t stream_id, uint32_t draw, void* stream) {
-    if (!out || B <= 0 || J <= 0 || T <= 0) return fail(DSG_E_INVALID, "dsg_noise: bad argument");
-    NoiseKey nk;
-    nk.k0 = (unsigned)(seed & 0xffffffffu); nk.k1 = (unsigned)(seed >> 32);
-    nk.s0 = (unsigned)(stream_id & 0xffffffffu); nk.s1 = (unsigned)(stream_id >> 32);
+static int noise_tensor(float* out, int B, int J, int T, NoiseKey nk, const unsigned* keys, uint32_t draw, void* stream) {
     const int Jq = rup(J, 4);
     const size_t n = (size_t)B * T * (Jq / 4), bytes = (size_t)B * J * T * sizeof(float);
     const bool dev = is_device_ptr(out);
     float* dst = out;
     if (!dev) HIPCHK(hipMalloc((void**)&dst, bytes));
-    hipLaunchKernelGGL(k_noise, dim3((int)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, dst, B, J, Jq, T, nk, draw);
+    hipLaunchKernelGGL(k_noise, dim3((int)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, dst, B, J, Jq, T, nk, keys, draw);
     hipError_t e = hipGetLastError();
     if (!dev) {          // host output: the temporary is released on every path
         if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
@@ -2872,6 +2911,38 @@ extern "C" int dsg_noise(float* out, int B, int J, int T, uint64_t seed, uint64_
     }
     if (e != hipSuccess) return fail(DSG_E_RUNTIME, std::string("dsg_noise: ") + hipGetErrorString(e));
     return 0;
+}
+extern "C" int dsg_noise(float* out, int B, int J, int T, uint64_t seed, uint64_t stream_id, uint32_t draw, void* stream) {
+    if (!out || B <= 0 || J <= 0 || T <= 0) return fail(DSG_E_INVALID, "dsg_noise: bad argument");
+    NoiseKey nk;
+    nk.k0 = (unsigned)(seed & 0xffffffffu); nk.k1 = (unsigned)(seed >> 32);
+    nk.s0 = (unsigned)(stream_id & 0xffffffffu); nk.s1 = (unsigned)(stream_id >> 32);
+    return noise_tensor(out, B, J, T, nk, nullptr, draw, stream);
+}
+// dsg_noise with per-element streams: element b of out [B, J, 1, T] is draw `draw` of (seeds[b], stream_ids[b]) with the batch term of the
+// counter 0 -- bit for bit dsg_noise(B = 1, seeds[b], stream_ids[b], draw), and what the fused loops consume for that draw index on a handle
+// with dsg_set_noise_streams.  seeds / stream_ids: HOST uint64[B]; a NULL one reads as zeros
+extern "C" int dsg_noise_streams(float* out, int B, int J, int T, const uint64_t* seeds, const uint64_t* stream_ids, uint32_t draw, void* stream) {
+    if (!out || B <= 0 || J <= 0 || T <= 0) return fail(DSG_E_INVALID, "dsg_noise_streams: bad argument");
+    std::vector<unsigned> hk(4 * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const uint64_t sd = seeds ? seeds[b] : 0, id = stream_ids ? stream_ids[b] : 0;
+        hk[4 * b] = (unsigned)(sd & 0xffffffffu); hk[4 * b + 1] = (unsigned)(sd >> 32);
+        hk[4 * b + 2] = (unsigned)(id & 0xffffffffu); hk[4 * b + 3] = (unsigned)(id >> 32);
+    }
+    unsigned* keys = nullptr;
+    HIPCHK(hipMalloc((void**)&keys, hk.size() * sizeof(unsigned)));
+    hipError_t e = hipMemcpy(keys, hk.data(), hk.size() * sizeof(unsigned), hipMemcpyHostToDevice);      // (synchronous: `hk` is free after it)
+    int rc = 0;
+    if (e != hipSuccess) rc = fail(DSG_E_RUNTIME, std::string("dsg_noise_streams: ") + hipGetErrorString(e));
+    else {
+        const NoiseKey nk = {0, 0, 0, 0};
+        rc = noise_tensor(out, B, J, T, nk, keys, draw, stream);
+        // the table is released once the kernel that reads it has run (a device `out` is written on `stream`, as by dsg_noise)
+        if (rc == 0 && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(DSG_E_RUNTIME, "dsg_noise_streams: synchronize");
+    }
+    (void)hipFree(keys);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;
 
 #define DSG_FLT_MAX 3.402823466e+38f
@@ -401,6 +402,14 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // Philox4x32-10 + Box-Muller: the framework's noise stream (restated for the CPU in oracle/philox.py)
 // ---------------------------------------------------------------------------------------------------------
 struct NoiseKey { unsigned k0, k1, s0, s1; };          // seed lo/hi, stream lo/hi
+// Keyed noise (dsg_set_noise_streams): a table of one key per batch element, {seed lo, seed hi, stream lo, stream hi} x B, 16-byte aligned.
+// Element b then draws what it would draw sampled alone with its pair: ITS key and the batch term of the counter 0, i.e. draw d at
+// (f, j) = philox4x32_10(ctr = ((f Jq + j) >> 2, d, sid_b), key = seed_b) -- the [1, J, 1, T] tensor of (seed_b, sid_b).
+__device__ __forceinline__ NoiseKey noise_key_of(const unsigned* keys, int b) {
+    const u32x4 k = *(const u32x4*)(keys + 4 * b);          // one 16-byte load
+    const NoiseKey nk = {k[0], k[1], k[2], k[3]};
+    return nk;
+}
 
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
                                               unsigned k1, unsigned (&o)[4]) {
@@ -539,11 +548,13 @@ struct GemmArgs {
                             // advances the B side); null outside the sampling loop
     StepTables st;          // tables the block-0 bookkeeping reads (n_tab entries)
     int n_tab;
-    const unsigned* dyn;    // device: {seed lo, seed hi, stream lo, stream hi, draw index of step 0} -- kept out of
-                            // the kernel arguments so a captured graph is reusable across windows / clips
+    const unsigned* dyn;    // device: {seed lo, seed hi, stream lo, stream hi, draw index of step 0, -, -, -} + the key table of keyed noise
+                            // (words 8 + 4 b .. 8 + 4 b + 3: noise_key_of) -- kept out of the kernel arguments so a captured graph is
+                            // reusable across windows / clips
     const float* ext_noise; // optional [n_steps][B][J][T] replayed noise, else null
     int B;
     int const_noise;
+    int keyed;              // EPI_OUT: per-element noise streams (dsg_set_noise_streams): the key of element b from dyn + 8, batch term of the counter 0
     int ws_G;               // dsg_stream.h: row-block groups of the persistent grid (multiple of 8)
     int a_frag;             // PRO_DIRECT: A is stored fragment-major ([row tile][k-block][64 lanes][16 B], qk_off) -- hidden, attention rows
     int out_frag;           // EPI_GELU: the output goes out fragment-major (it is the next GEMM's A operand)
@@ -771,8 +782,21 @@ __device__ __forceinline__ void gemm_prefetch_tile(const GemmArgs& g, int m0, in
                         o.pz[e] = (j0 + e < g.J)
                                        ? g.ext_noise[(((size_t)step * g.B + bn) * g.J + j0 + e) * g.T + f] : 0.f;
                 } else {
-                    const NoiseKey nk = {g.dyn[0], g.dyn[1], g.dyn[2], g.dyn[3]};
-                    o.pz = philox_normal4((imul24((int)imul24(bn, g.T) + f, g.Jq) + (unsigned)j0) >> 2, g.dyn[4] + (unsigned)step, nk);
+                    // The key: the call's, dyn[0 .. 3], or with per-element streams (keyed: workgroup-uniform) the element's, from the table behind it
+                    // (noise_key_of), with the batch term of the counter 0.  Requested here with pb / pr, in front of the main loop.  Keyed, a pass
+                    // of the loop serves the lanes of ONE batch element of the wave (1 or 2 elements per 16-row tile); unkeyed there is one pass.
+                    // This form costs no kernel a spill or a wave of occupancy; selecting the key's address per lane in a straight line did
+                    // (k_ws<EPI_OUT, 16, ONE>, at its bound of 128 registers: 8 bytes of scratch)
+                    bool todo = true;
+                    do {
+                        const int bu = g.keyed ? __builtin_amdgcn_readfirstlane(bn) : 0;
+                        if (!g.keyed || bn == bu) {
+                            NoiseKey nk = {g.dyn[0], g.dyn[1], g.dyn[2], g.dyn[3]};
+                            if (g.keyed) nk = noise_key_of(g.dyn + 8, bu);
+                            o.pz = philox_normal4((imul24((int)imul24(bn, g.keyed ? 0 : g.T) + f, g.Jq) + (unsigned)j0) >> 2, g.dyn[4] + (unsigned)step, nk);
+                            todo = false;
+                        }
+                    } while (todo);
                 }
             }
         }
@@ -1577,6 +1601,7 @@ struct XInArgs {
     float qa, qb;
     int use_philox;         // draw noise 0 from the Philox stream when x == null
     NoiseKey nkey; unsigned draw;
+    const unsigned* keys;   // keyed noise: the key table (noise_key_of), else null
     int B, J, Jp, Jq, T;
     float* xs32; void* xsA;
     int dupB;               // classifier-free guidance: batch element b is also written to row b + dupB (its unconditional twin)
@@ -1601,7 +1626,8 @@ __global__ void k_x_in(const XInArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (j0 + e < a.J) z[e] = a.x[((size_t)b * a.J + j0 + e) * a.T + f];
             } else if (a.use_philox) {
-                z = philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
+                z = a.keys ? philox_normal4((unsigned)(((size_t)f * a.Jq + j0) >> 2), a.draw, noise_key_of(a.keys, b))
+                           : philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
             }
             if (a.do_q) {
 #pragma unroll
@@ -1643,13 +1669,15 @@ __global__ void k_inp_in(const float* motion, const unsigned char* mask, int B, 
 }
 // the framework's noise stream as a tensor: out [B][J][T] (the reference's [B, J, 1, T]) = draw `draw` of (seed, stream) --
 // exactly what the fused sampler epilogue consumes for that draw index (generic sampling loop, tests)
-__global__ void k_noise(float* out, int B, int J, int Jq, int T, NoiseKey key, unsigned draw) {
+// `keys` (dsg_noise_streams): element b is draw `draw` of ITS pair, the [1][J][T] tensor of that pair
+__global__ void k_noise(float* out, int B, int J, int Jq, int T, NoiseKey key, const unsigned* keys, unsigned draw) {
     const size_t n = (size_t)B * T * (Jq / 4);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int jq = (int)(i % (Jq / 4));
         const size_t bf = i / (Jq / 4);
         const int f = (int)(bf % T), b = (int)(bf / T);
-        const f32x4 z = philox_normal4((unsigned)((((size_t)b * T + f) * Jq + 4 * jq) >> 2), draw, key);
+        const f32x4 z = keys ? philox_normal4((unsigned)(((size_t)f * Jq + 4 * jq) >> 2), draw, noise_key_of(keys, b))
+                             : philox_normal4((unsigned)((((size_t)b * T + f) * Jq + 4 * jq) >> 2), draw, key);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (4 * jq + e < J) out[((size_t)b * J + 4 * jq + e) * T + f] = z[e];
@@ -1769,6 +1797,7 @@ struct ClipXInArgs {
     const float* init; const float* c_seed;
     float qa, qb;
     NoiseKey nkey; unsigned draw;
+    const unsigned* keys;   // keyed noise: the key table (noise_key_of), else null
     int B, J, Jp, Jq, T, S, n_out, c;
     float* xs32; void* xsA;
     int dupB, xs_frag;
@@ -1793,7 +1822,8 @@ __global__ void k_clip_x_in(const ClipXInArgs a) {
             } else {
                 v = clip_inp_load4(a.init + ((size_t)b * a.n_out + (df < a.n_out ? df : a.n_out - 1)) * a.J + j0, nv);
             }
-            z = philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
+            z = a.keys ? philox_normal4((unsigned)(((size_t)f * a.Jq + j0) >> 2), a.draw, noise_key_of(a.keys, b))
+                       : philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
 #pragma unroll
             for (int e = 0; e < 4; ++e) z[e] = e < nv ? q_sample1(a.qa, v[e], a.qb, z[e]) : 0.f;
         }

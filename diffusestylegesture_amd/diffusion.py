@@ -16,6 +16,8 @@ Noise: the reference consumes torch's global generator.  Here every draw comes f
 stream (Philox4x32-10, see csrc/dsg_kernels.h) addressed by (seed, stream_id, draw index).  `manual_seed(seed)`
 plays the role of `torch.manual_seed(seed)` (sample.py:212): it resets the draw counter, and each sampling call
 advances it by 1 + n_steps, so consecutive windows of a clip continue one stream exactly like the reference does.
+`clip_streams=` (every loop): one Philox stream PER BATCH ELEMENT -- element b draws what it would draw sampled alone (batch 1)
+after `manual_seed(seed_b, stream_b)`, so a clip's result does not depend on the batch, slot, lane or rank it rides in.
 """
 from __future__ import annotations
 
@@ -71,6 +73,45 @@ def space_timesteps(num_timesteps, section_counts):
 _TABLES = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod",
            "sqrt_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
            "posterior_variance", "posterior_log_variance_clipped", "posterior_mean_coef1", "posterior_mean_coef2")
+
+
+_U64 = 2 ** 64 - 1
+
+
+def _clip_streams(clip_streams, B, what="clip_streams"):
+    """`clip_streams=` as (seeds or None, stream ids): a sequence of B stream ids (every element keeps the call's seed), or of B
+    (seed, stream_id) pairs."""
+    cs = list(clip_streams)
+    if len(cs) != B:
+        raise ValueError(f"{what}: {len(cs)} entries for a batch of {B}")
+    pairs = [isinstance(c, (tuple, list)) for c in cs]
+    if any(pairs):
+        if not all(pairs) or any(len(c) != 2 for c in cs):
+            raise ValueError(f"{what}: B stream ids, or B (seed, stream_id) pairs")
+        return [int(c[0]) & _U64 for c in cs], [int(c[1]) & _U64 for c in cs]
+    return None, [int(c) & _U64 for c in cs]
+
+
+class _keyed:
+    """The lanes' per-element noise streams for ONE call (`DSGDenoiser.set_noise_streams`): set on entry, cleared on exit, as the
+    clip-level constraint of `sample_clip` is.  `per_lane`: one `clip_streams` (or None) per lane."""
+
+    def __init__(self, lanes, per_lane, B):
+        self.lanes, self.streams = list(lanes), [None if cs is None else _clip_streams(cs, B) for cs in per_lane]
+
+    def __enter__(self):
+        for m, st in zip(self.lanes, self.streams):
+            if st is not None:
+                m.set_noise_streams(*st)
+            elif m.noise_streams:
+                m.set_noise_streams(None, None)
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.lanes:
+            if m.noise_streams:
+                m.set_noise_streams(None, None)
+        return False
 
 
 class DSGDiffusion:
@@ -188,15 +229,16 @@ class DSGDiffusion:
         return a, keep, dump, use_torch
 
     def _fused(self, mode, model, guided, shape, noise, model_kwargs, skip_timesteps, init_image, dump_steps, const_noise,
-               eta, step_noise, seed, draw_base, clip_denoised, first_step=0, max_steps=0):
+               eta, step_noise, seed, draw_base, clip_denoised, first_step=0, max_steps=0, stream_id=None, clip_streams=None):
         B = int(shape[0])
         a, keep, dump, use_torch = self._prepare(mode, model, guided, shape, noise, model_kwargs, skip_timesteps, init_image,
                                                  dump_steps, const_noise, eta, step_noise, seed, draw_base, clip_denoised,
-                                                 first_step=first_step, max_steps=max_steps)
+                                                 stream_id=stream_id, first_step=first_step, max_steps=max_steps)
         n_run = self.num_timesteps - skip_timesteps
         out, out_ptr = model._alloc_out(shape, use_torch)
         lib = model.lib
-        lib.check(lib.cdll.dsg_sample(model.handle, C.byref(a), out_ptr, B, L.current_stream_ptr() if use_torch else None))
+        with _keyed([model], [clip_streams], B):
+            lib.check(lib.cdll.dsg_sample(model.handle, C.byref(a), out_ptr, B, L.current_stream_ptr() if use_torch else None))
         if draw_base is None:
             self._draw += 1 + n_run
         self._last_model = model
@@ -212,26 +254,31 @@ class DSGDiffusion:
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
                       randomize_class=False, cond_fn_with_grad=False, dump_steps=None, const_noise=False,
-                      *, step_noise=None, seed=None, draw_base=None):
+                      *, step_noise=None, seed=None, draw_base=None, clip_streams=None):
+        """`clip_streams` (every loop of this class): B stream ids, or B (seed, stream_id) pairs -- element b then draws from ITS
+        Philox stream and is, bit for bit, the batch-1 call after `manual_seed(seed_b, stream_b)` with its conditioning under the same
+        kernel set (`DSGDenoiser.set_noise_streams`; applied for this call, cleared after it)."""
         hooks = self._check_unsupported(denoised_fn, cond_fn, randomize_class, cond_fn_with_grad)
         inner, guided = (None, False) if hooks else self._library_model(model, shape[0])
         if inner is not None:
             return self._fused(L.MODE_DDPM, inner, guided, shape, noise, model_kwargs, skip_timesteps, init_image,
-                               dump_steps, const_noise, 0.0, step_noise, seed, draw_base, clip_denoised)
+                               dump_steps, const_noise, 0.0, step_noise, seed, draw_base, clip_denoised, clip_streams=clip_streams)
         return self._generic_loop(False, model, shape, noise, model_kwargs, skip_timesteps, init_image, dump_steps,
-                                  const_noise, 0.0, device, clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn)
+                                  const_noise, 0.0, device, clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                  clip_streams=clip_streams)
 
     PROGRESSIVE_CHUNK = 50      # steps per library call of the generator forms
 
     def _progressive(self, ddim, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps,
-                     init_image, randomize_class, cond_fn_with_grad, const_noise, eta):
+                     init_image, randomize_class, cond_fn_with_grad, const_noise, eta, clip_streams=None):
         """Generator form of the loops: one {"sample": x_{t-1}} per denoising step, in loop order -- LAZY like the reference's
         (gaussian_diffusion.py:673-740): the chain runs inside the library PROGRESSIVE_CHUNK steps per call (dsg_sample_args.first_step
         / max_steps: a chain in pieces, every step of the piece dumped), so the host holds one chunk of samples at a time (round-3
         advisor: the whole chain used to be materialised, 0.4 GB at ZEGGS dims and batch 1) and a caller that abandons the generator
         stops the work.  Same samples, bit for bit, as the one-call loops: draw indices are those of the whole chain, reserved HERE,
         when the generator is created (round-4 advisor: a generator body runs at the first next(), so reserving them inside it let a
-        loop started between creation and first use draw the same noise)."""
+        loop started between creation and first use draw the same noise).  The seed, the stream id and `clip_streams` are captured
+        with them: a `manual_seed()` between creation and the first next(), or between two chunks, does not touch a running chain."""
         hooks = self._check_unsupported(denoised_fn, cond_fn, randomize_class, cond_fn_with_grad)
         inner, guided = (None, False) if hooks else self._library_model(model, shape[0])
         n_run = self.num_timesteps - skip_timesteps
@@ -239,16 +286,21 @@ class DSGDiffusion:
         # (hooks / a wrapped model): noise indices are fixed here, not at the first next()
         draw0 = self._draw
         self._draw += 1 + n_run
+        if clip_streams is not None:
+            _clip_streams(clip_streams, int(shape[0]))      # (a wrong list fails here, not at the first next())
+            clip_streams = list(clip_streams)
+        owned = (self._seed & _U64, self.stream_id, clip_streams)
         return self._progressive_gen(ddim, model, inner, guided, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps,
-                                     init_image, const_noise, eta, n_run, draw0, denoised_fn, cond_fn)
+                                     init_image, const_noise, eta, n_run, draw0, denoised_fn, cond_fn, owned)
 
     def _progressive_gen(self, ddim, model, inner, guided, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps,
-                         init_image, const_noise, eta, n_run, draw0, denoised_fn=None, cond_fn=None):
+                         init_image, const_noise, eta, n_run, draw0, denoised_fn=None, cond_fn=None, owned=None):
+        seed, stream_id, clip_streams = owned if owned is not None else (self._seed & _U64, self.stream_id, None)
         if inner is None:
             # LAZY like the fused form: one step per next() (the whole chain used to run, and every step be cloned on the device -- 0.4 GB per
             # clip at ZEGGS dims -- before the first yield; an abandoned generator now stops the work)
             for o in self._generic_steps(ddim, model, shape, noise, model_kwargs, skip_timesteps, init_image, const_noise, eta, device,
-                                         clip_denoised, denoised_fn, cond_fn, draw0):
+                                         clip_denoised, denoised_fn, cond_fn, draw0, seed, stream_id, clip_streams):
                 yield {"sample": o}
             return
         mode = L.MODE_DDIM if ddim else L.MODE_DDPM
@@ -256,39 +308,43 @@ class DSGDiffusion:
         while first < n_run:
             k = min(self.PROGRESSIVE_CHUNK, n_run - first)
             outs = self._fused(mode, inner, guided, shape, x, model_kwargs, skip_timesteps, init_image if first == 0 else None,
-                               list(range(first, first + k)), const_noise, eta, None, None, draw0, clip_denoised, first_step=first, max_steps=k)
+                               list(range(first, first + k)), const_noise, eta, None, seed, draw0, clip_denoised, first_step=first, max_steps=k,
+                               stream_id=stream_id, clip_streams=clip_streams)
             for o in outs:
                 yield {"sample": o}
             x, first = outs[-1], first + k
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                   model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
-                                  randomize_class=False, cond_fn_with_grad=False, const_noise=False):
+                                  randomize_class=False, cond_fn_with_grad=False, const_noise=False, *, clip_streams=None):
         """`GaussianDiffusion.p_sample_loop_progressive` (gaussian_diffusion.py:673-740): yields a dict per step; key "sample"
         (the reference's "pred_xstart" is not produced: no caller on the path reads it)."""
         return self._progressive(False, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps,
-                                 init_image, randomize_class, cond_fn_with_grad, const_noise, 0.0)
+                                 init_image, randomize_class, cond_fn_with_grad, const_noise, 0.0, clip_streams)
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
-                                     randomize_class=False, cond_fn_with_grad=False):
+                                     randomize_class=False, cond_fn_with_grad=False, *, clip_streams=None):
         """`GaussianDiffusion.ddim_sample_loop_progressive` (gaussian_diffusion.py:938-1003)."""
         return self._progressive(True, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps,
-                                 init_image, randomize_class, cond_fn_with_grad, False, eta)
+                                 init_image, randomize_class, cond_fn_with_grad, False, eta, clip_streams)
 
     def p_sample_loop_multi(self, models, shape, model_kwargs_list, *, seeds=None, stream_ids=None, clip_denoised=False,
-                            skip_timesteps=0, init_images=None, noises=None, ddim=False, eta=0.0):
+                            skip_timesteps=0, init_images=None, noises=None, ddim=False, eta=0.0, clip_streams=None):
         """`p_sample_loop` (or `ddim_sample_loop`) for SEVERAL lanes at once -- one `DSGDenoiser` per lane (a model and its
         `clone()`s: one copy of the weights), one independent sampling problem each, advanced concurrently inside the
         library (dsg_sample_multi: every lane owns an HSA queue; "one clip per stream").  Lane i draws from the Philox stream
         (seeds[i], stream_ids[i]) at this object's current draw counter, which advances once for all lanes -- so lane i
         reproduces `manual_seed(seeds[i], stream_ids[i])` + the same sequence of single-lane calls ON THE SAME LANE bit for
         bit: every lane runs the kernel set of its own handle (`DSGDenoiser.set_kernel_set`), the call itself changes nothing
-        about the arithmetic."""
+        about the arithmetic.  `clip_streams`: one list per lane (B stream ids or B (seed, stream_id) pairs, as `p_sample_loop`
+        takes them; an entry may be None) -- the elements of that lane draw from their own streams, `stream_ids[i]` is then unused."""
         models = list(models)
         n = len(models)
         if n == 0 or len(model_kwargs_list) != n:
             raise ValueError("one model_kwargs per lane")
+        if clip_streams is not None and len(clip_streams) != n:
+            raise ValueError(f"clip_streams: {len(clip_streams)} lists for {n} lanes (one list of B streams per lane)")
         seeds = [self._seed] * n if seeds is None else list(seeds)
         stream_ids = [self.stream_id + i for i in range(n)] if stream_ids is None else list(stream_ids)
         B = int(shape[0])
@@ -313,7 +369,8 @@ class DSGDiffusion:
             outs.append(o)
             optrs[i] = p
         lib = models[0].lib
-        lib.check(lib.cdll.dsg_sample_multi(hs, n, args, optrs, B, L.current_stream_ptr() if use_torch else None))
+        with _keyed(models, [None] * n if clip_streams is None else clip_streams, B):
+            lib.check(lib.cdll.dsg_sample_multi(hs, n, args, optrs, B, L.current_stream_ptr() if use_torch else None))
         self._draw += 1 + (self.num_timesteps - skip_timesteps)
         self._last_model = models[0]
         return outs
@@ -321,7 +378,7 @@ class DSGDiffusion:
     # ---- a whole clip per library call (dsg_sample_clip): the window loops of sample.py inside the library -----------------
     def sample_clip(self, model, feats, style, *, seed0=None, root_shift, keep_last_tail, ddim=False, eta=0.0, skip_timesteps=0,
                     clip_denoised=False, scale=None, seed_last=None, mask_local="ones", inpainting_mask=None, inpainted_motion=None,
-                    init_motion=None):
+                    init_motion=None, clip_streams=None):
         """All K windows of B clips in ONE library call: per-window conditioning, step loop, seed hand-off, root shift (`root_shift`,
         the ZEGGS loop's `smoothing`), one-frame blend and stitching on the device (k_window_handoff).  `feats`: the K per-window
         features exactly as y['audio'] takes them, each [B, T_a, A_src] (stacked once into [K, B, T_a, A_src]); `style` [B, style_dim_in];
@@ -337,7 +394,9 @@ class DSGDiffusion:
         `init_motion` [B, n_out, J] (numpy or torch): an existing clip to edit, in the coordinates of the returned clip -- every window
         starts from q_sample of its slice (`sample.window_init`: the `init_image` of that window's loop) instead of pure noise, noised to
         the first timestep `skip_timesteps` leaves; cut, noised and written as the sampler state by one kernel per window
-        (`DSGDenoiser.set_clip_init`; set before the call, cleared after it)."""
+        (`DSGDenoiser.set_clip_init`; set before the call, cleared after it).
+        `clip_streams`: B stream ids or B (seed, stream_id) pairs, as `p_sample_loop` takes them -- clip b draws every window from its
+        own Philox stream and equals the clip sampled alone (`DSGDenoiser.set_noise_streams`; set before the call, cleared after it)."""
         if (inpainting_mask is None) != (inpainted_motion is None):
             raise ValueError("sample_clip: inpainting_mask and inpainted_motion go together")
         return self.sample_clip_multi([model], [feats], [style], seed0s=None if seed0 is None else [seed0], root_shift=root_shift,
@@ -346,15 +405,17 @@ class DSGDiffusion:
                                       seed_lasts=None if seed_last is None else [seed_last], mask_local=mask_local,
                                       stream_ids=[self.stream_id], inpainting_masks=None if inpainting_mask is None else [inpainting_mask],
                                       inpainted_motions=None if inpainted_motion is None else [inpainted_motion],
-                                      init_motions=None if init_motion is None else [init_motion])[0]
+                                      init_motions=None if init_motion is None else [init_motion],
+                                      clip_streams=None if clip_streams is None else [clip_streams])[0]
 
     def sample_clip_multi(self, models, feats_per_lane, styles, *, seed0s=None, root_shift, keep_last_tail, ddim=False, eta=0.0,
                           skip_timesteps=0, clip_denoised=False, scales=None, seed_lasts=None, mask_local="ones", seeds=None,
-                          stream_ids=None, inpainting_masks=None, inpainted_motions=None, init_motions=None):
+                          stream_ids=None, inpainting_masks=None, inpainted_motions=None, init_motions=None, clip_streams=None):
         """`sample_clip` for several lanes at once (dsg_sample_clip_multi; lanes as in `p_sample_loop_multi`): lane i samples the B
         clips of feats_per_lane[i] from the Philox stream (seeds[i], stream_ids[i]); the windows advance in lock step over the lanes.
         `inpainting_masks` / `inpainted_motions`: one [B, n_out, J] pair per lane, entries may be None (that lane runs unconstrained).
         `init_motions`: one [B, n_out, J] clip per lane to start from, entries may be None (that lane starts from noise).
+        `clip_streams`: one list of B streams per lane as in `p_sample_loop_multi`, entries may be None.
         Returns one [B, n_out, J] array per lane."""
         models = list(models)
         n = len(models)
@@ -368,6 +429,8 @@ class DSGDiffusion:
         inits = [None] * n if init_motions is None else list(init_motions)
         if len(inits) != n:
             raise ValueError("sample_clip: one init motion per lane (or None)")
+        if clip_streams is not None and len(clip_streams) != n:
+            raise ValueError(f"clip_streams: {len(clip_streams)} lists for {n} lanes (one list of B streams per lane)")
         K = len(feats_per_lane[0])
         if K < 1 or any(len(f) != K for f in feats_per_lane):
             raise ValueError("the same number of windows (>= 1) for every lane")
@@ -448,7 +511,9 @@ class DSGDiffusion:
             for k, v in (("h", m.handle), ("style", style.ptr), ("seed0", seed0.ptr), ("audio", audio.ptr), ("scale", sc.ptr), ("out", optr)):
                 ptrs[k][i] = v
         lib = inners[0].lib
+        keyed = _keyed(inners, [None] * n if clip_streams is None else clip_streams, B)
         try:
+            keyed.__enter__()
             for m, (mk, mo) in zip(inners, inp):
                 if mk is not None:
                     if tuple(mo.shape) != (B, n_out, J):
@@ -470,6 +535,7 @@ class DSGDiffusion:
                 lib.check(lib.cdll.dsg_sample_clip_multi(ptrs["h"], n, ptrs["style"], ptrs["seed0"], ptrs["audio"], mbuf.p, mb, ptrs["scale"], args, K,
                                                          int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"], B, stream))
         finally:
+            keyed.__exit__()
             for m in inners:
                 if m.clip_inpainting:
                     m.set_clip_inpainting(None, None, 0)
@@ -482,7 +548,7 @@ class DSGDiffusion:
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
                          randomize_class=False, cond_fn_with_grad=False, dump_steps=None, const_noise=False,
-                         *, step_noise=None, seed=None, draw_base=None):
+                         *, step_noise=None, seed=None, draw_base=None, clip_streams=None):
         if dump_steps is not None:
             raise NotImplementedError()
         if const_noise:
@@ -491,9 +557,9 @@ class DSGDiffusion:
         inner, guided = (None, False) if hooks else self._library_model(model, shape[0])
         if inner is not None:
             return self._fused(L.MODE_DDIM, inner, guided, shape, noise, model_kwargs, skip_timesteps, init_image, None,
-                               False, eta, step_noise, seed, draw_base, clip_denoised)
+                               False, eta, step_noise, seed, draw_base, clip_denoised, clip_streams=clip_streams)
         return self._generic_loop(True, model, shape, noise, model_kwargs, skip_timesteps, init_image, None, False,
-                                  eta, device, clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn)
+                                  eta, device, clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, clip_streams=clip_streams)
 
     def last_step_time_us(self):
         """GPU time per denoising step of the last fused call (HIP events inside the library)."""
@@ -514,22 +580,25 @@ class DSGDiffusion:
         return np.full((B,), np.float32(getattr(self, name)[idx]), dtype=np.float32)
 
     def _generic_loop(self, ddim, model, shape, noise, model_kwargs, skip_timesteps, init_image, dump_steps,
-                      const_noise, eta, device, clip_denoised=False, denoised_fn=None, cond_fn=None):
+                      const_noise, eta, device, clip_denoised=False, denoised_fn=None, cond_fn=None, clip_streams=None):
         """The generic loop run to its end: the last sample, or clones of the samples after the steps listed in `dump_steps`."""
         n_run = self.num_timesteps - skip_timesteps
         draw0 = self._draw
         self._draw += 1 + n_run
         img, dump = None, []
         for n, img in enumerate(self._generic_steps(ddim, model, shape, noise, model_kwargs, skip_timesteps, init_image, const_noise, eta,
-                                                    device, clip_denoised, denoised_fn, cond_fn, draw0)):
+                                                    device, clip_denoised, denoised_fn, cond_fn, draw0, self._seed & _U64, self.stream_id,
+                                                    clip_streams)):
             if dump_steps is not None and n in dump_steps:
                 dump.append(img.clone())
         return dump if dump_steps is not None else img
 
     def _generic_steps(self, ddim, model, shape, noise, model_kwargs, skip_timesteps, init_image, const_noise, eta, device,
-                       clip_denoised, denoised_fn, cond_fn, draw0):
+                       clip_denoised, denoised_fn, cond_fn, draw0, seed, stream_id, clip_streams=None):
         """Generator: x_{t-1} after every step of the loop, any callable as the denoiser; draw indices draw0 (x_T), draw0 + 1 + n (step n) --
-        reserved by the caller.  The noise is the framework's Philox stream (dsg_noise), draw for draw the one the
+        reserved by the caller, like `seed` / `stream_id` / `clip_streams`: a generator body runs at the first next(), and the chain draws
+        from the streams the object had when the loop was created.  The noise is the framework's Philox stream (dsg_noise; with
+        `clip_streams` dsg_noise_streams: every element its own stream, with `const_noise` element 0's for everyone), draw for draw the one the
         fused loop consumes -- a wrapped model keeps seed parity with the fused path and the oracle.  `denoised_fn(x0)` is applied to the
         prediction before the clamp (gaussian_diffusion.py:364-370); `cond_fn(x_t, t, **model_kwargs)` -- t the MODEL timesteps, as the wrapped
         cond_fn of SpacedDiffusion sees them (respace.py:117-129) -- shifts the DDPM mean by posterior_variance * grad (condition_mean, :428-441)
@@ -551,11 +620,21 @@ class DSGDiffusion:
         B = int(shape[0])
         per = int(np.prod(shape[1:]))
         stream = L.current_stream_ptr()
-        seed, stream_id = self._seed & (2 ** 64 - 1), self.stream_id      # (as they are when the loop / generator is created)
+        keys = None
+        if clip_streams is not None:
+            seeds, ids = _clip_streams(clip_streams, B)
+            seeds = [seed] * B if seeds is None else seeds
+            if const_noise:
+                seeds, ids = [seeds[0]] * B, [ids[0]] * B
+            keys = (np.array(seeds, dtype=np.uint64), np.array(ids, dtype=np.uint64))
 
         def z(draw):
             t = torch.empty(*shape, device=device, dtype=torch.float32)
-            lib.check(lib.cdll.dsg_noise(t.data_ptr(), B, int(shape[1]) * int(shape[2]), int(shape[3]), seed, stream_id, draw, stream))
+            if keys is not None:
+                lib.check(lib.cdll.dsg_noise_streams(t.data_ptr(), B, int(shape[1]) * int(shape[2]), int(shape[3]), keys[0].ctypes.data,
+                                                     keys[1].ctypes.data, draw, stream))
+            else:
+                lib.check(lib.cdll.dsg_noise(t.data_ptr(), B, int(shape[1]) * int(shape[2]), int(shape[3]), seed, stream_id, draw, stream))
             return t
         img = noise if noise is not None else z(draw0)      # (the x_T draw index is reserved either way, as in the fused loop)
         if skip_timesteps and init_image is None:

@@ -56,6 +56,7 @@ SYMBOLS = {
     "dsg_sample_multi": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_sample_args), C.POINTER(_P), _I, _P]),
     "dsg_set_clip_inpainting": (_I, [_P, _P, _P, _I, _I, _P]),
     "dsg_set_clip_init": (_I, [_P, _P, _I, _I, _P]),
+    "dsg_set_noise_streams": (_I, [_P, _P, _P, _I]),
     "dsg_sample_clip": (_I, [_P, _P, _P, _P, _P, _I, _P, C.POINTER(dsg_sample_args), _I, _I, _I, _P, _I, _P]),
     "dsg_sample_clip_multi": (_I, [C.POINTER(_P), _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _I, C.POINTER(_P),
                                    C.POINTER(dsg_sample_args), _I, _I, _I, C.POINTER(_P), _I, _P]),
@@ -69,6 +70,7 @@ SYMBOLS = {
     "dsg_last_sample_fence_free": (_I, [_P, C.POINTER(_I)]),
     "dsg_trim": (_I, [_I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "dsg_noise": (_I, [_P, _I, _I, _I, C.c_uint64, C.c_uint64, C.c_uint32, _P]),
+    "dsg_noise_streams": (_I, [_P, _I, _I, _I, _P, _P, C.c_uint32, _P]),
     "dsg_pose2bvh": (_I, [_P, _I, _I, _P, _P, _I, C.c_char_p]),
     "dsg_pose2bvh_channels": (_I, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "dsg_pose2bvh_batch": (_I, [_P, _I, _I, _I, _P, _P, _I, C.POINTER(C.c_char_p)]),

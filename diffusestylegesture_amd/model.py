@@ -41,6 +41,7 @@ class DSGDenoiser:
         self.inpainting = False           # this lane holds an inpainting constraint (set_inpainting)
         self._clip_inpainting = False     # ... a clip-level one (set_clip_inpainting)
         self._clip_init = False           # ... a clip-level init motion (set_clip_init)
+        self.noise_streams = None         # per-element noise streams of this lane (set_noise_streams): (seeds or None, stream ids)
         if _clone_of is not None:
             h = C.c_void_p()
             self.lib.check(self.lib.cdll.dsg_clone(_clone_of.handle, max_batch, C.byref(h)))
@@ -219,6 +220,23 @@ class DSGDenoiser:
     def clip_init(self) -> bool:
         """This lane holds a clip-level init motion (`set_clip_init`)."""
         return self._clip_init
+
+    def set_noise_streams(self, seeds, stream_ids):
+        """Per-element noise streams of this lane (dsg_set_noise_streams): element b of every sampling call draws from the Philox stream
+        (seeds[b], stream_ids[b]) -- exactly the noise it gets sampled alone, batch 1, with that pair -- instead of slot b of the call's one
+        stream.  `seeds=None`: every element keeps the call's seed; `stream_ids=None` with seeds: stream 0.  Sticky for this lane (a
+        `clone()` starts without), a sampling call then needs a batch of as many elements; `set_noise_streams(None, None)` switches it
+        off.  The loops of `DSGDiffusion` set it from their `clip_streams=` keyword and clear it afterwards."""
+        if seeds is None and stream_ids is None:
+            self.lib.check(self.lib.cdll.dsg_set_noise_streams(self.handle, None, None, 0))
+            self.noise_streams = None
+            return
+        n = len(stream_ids if seeds is None else seeds)
+        if seeds is not None and stream_ids is not None and len(stream_ids) != n:
+            raise ValueError(f"noise streams: {n} seeds, {len(stream_ids)} stream ids")
+        u64 = [None if v is None else np.array([int(x) & (2 ** 64 - 1) for x in v], dtype=np.uint64) for v in (seeds, stream_ids)]
+        self.lib.check(self.lib.cdll.dsg_set_noise_streams(self.handle, *[None if a is None else a.ctypes.data for a in u64], n))
+        self.noise_streams = tuple(None if a is None else [int(x) for x in a] for a in u64)
 
     def _alloc_out(self, shape, use_torch):
         if use_torch:

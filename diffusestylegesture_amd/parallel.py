@@ -17,6 +17,18 @@ def shard_clips(n_clips: int, rank: int, world: int) -> list[int]:
     return list(range(rank, n_clips, world))
 
 
+def shard_clip_ids(n_clips: int, rank: int, world: int, lanes: int = 1) -> list[list[int]]:
+    """The `clip_ids` of rank `rank` for `sample.generate_clips_streams(..., clip_ids=...)`: its `shard_clips` share dealt lane-major over
+    `lanes` lanes of equal batch (one list per lane; `lanes=1`: `[ids]`, whose single entry is what `sample.generate_clip` takes).  Clip c is
+    stream c on every world size and in every lanes x batch arrangement, so the gathered poses do not depend on how the clips were
+    spread; the lane-major result of the drivers is in `shard_clips` order, as `gather_poses` expects it."""
+    ids = shard_clips(n_clips, rank, world)
+    if lanes < 1 or len(ids) % lanes:
+        raise ValueError(f"{len(ids)} clips of rank {rank} do not fill {lanes} lanes of equal batch")
+    per = len(ids) // lanes
+    return [ids[i * per:(i + 1) * per] for i in range(lanes)]
+
+
 def gather_poses(local, n_clips: int, dist=None, dst: int = 0, device=None):
     """local: float32 [n_local, F, J] (numpy or torch) holding this rank's clips in shard_clips order.
     Returns [n_clips, F, J] ordered by clip index on rank `dst`, None elsewhere.  Ranks may hold different counts

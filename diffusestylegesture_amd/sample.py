@@ -108,6 +108,34 @@ def _loop_fn(diffusion, ddim, eta):
     return functools.partial(diffusion.ddim_sample_loop, eta=eta) if ddim else diffusion.p_sample_loop
 
 
+def _clip_ids(clip_ids, stream_id, B, name="stream_id"):
+    """`clip_ids=` of the single-lane drivers: B ints, clip i draws from the Philox stream (seed, clip_ids[i]) whichever slot it rides in
+    (`DSGDiffusion.p_sample_loop(clip_streams=...)`).  Returns (stream id of the call, clip_streams keywords for the loops)."""
+    if clip_ids is None:
+        return (0 if stream_id is None else stream_id), {}
+    if stream_id is not None:
+        raise ValueError(f"clip_ids and {name} exclude each other: with clip_ids every clip has its own stream")
+    ids = [int(c) for c in clip_ids]
+    if len(ids) != B:
+        raise ValueError(f"clip_ids: {len(ids)} entries for a batch of {B}")
+    return 0, {"clip_streams": ids}
+
+
+def _lane_clip_ids(clip_ids, stream_ids, n, B):
+    """`clip_ids=` of the multi-lane drivers: one list of B ints per lane.  Returns (stream ids of the lanes, clip_streams keyword)."""
+    if clip_ids is None:
+        return (list(range(n)) if stream_ids is None else list(stream_ids)), {}
+    if stream_ids is not None:
+        raise ValueError("clip_ids and stream_ids exclude each other: with clip_ids every clip has its own stream")
+    ids = [[int(c) for c in lane] for lane in clip_ids]
+    if len(ids) != n:
+        raise ValueError(f"clip_ids: {len(ids)} lists for {n} lanes")
+    for lane in ids:
+        if len(lane) != B:
+            raise ValueError(f"clip_ids: a lane's list has {len(lane)} entries for a batch of {B}")
+    return [0] * n, {"clip_streams": ids}
+
+
 def window_constraint(cfg, mask, motion, c, keep_last_tail):
     """Window c's y['inpainting_mask'] / y['inpainted_motion'] (both [B, J, 1, T]) cut out of a clip-level constraint `mask` / `motion`
     [B, n_out, J] given in the coordinates of the stitched clip (n_out = K * stride - S, or K * stride with `keep_last_tail`: the DSG+
@@ -224,8 +252,8 @@ def _per_lane(masks, motions, n):
 
 
 def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, skip_timesteps=0, sample_fn=None,
-                  stream_id=0, seed_pose=None, device=None, *, windows="host", ddim=False, eta=0.0, inpainting_mask=None,
-                  inpainted_motion=None, init_motion=None):
+                  stream_id=None, seed_pose=None, device=None, *, windows="host", ddim=False, eta=0.0, inpainting_mask=None,
+                  inpainted_motion=None, init_motion=None, clip_ids=None):
     """ZEGGS window loop (sample.py:236-296).  feats: sequence of K per-window WavLM features, each [B, T, A_src]
     (torch cuda tensors or numpy); style: one-hot list or [B, 6] array.  Returns normalised poses
     [B, K*stride - n_seed, J] (numpy float32) -- B independent clips advance in lock step.  `ddim` / `eta`: the DDIM loop
@@ -234,17 +262,20 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
     every window runs with `window_constraint(...)` as its y['inpainting_mask'] / y['inpainted_motion'] (host loop), or the library
     cuts the same on the device (`windows="library"`).  `init_motion` [B, K*stride - n_seed, J]: an existing clip to edit, in the
     coordinates of the returned clip -- every window is noised from `window_init(...)` as its `init_image` to the timestep
-    `skip_timesteps` leaves and sampled back (host loop), or the library cuts and noises the same on the device (`windows="library"`)."""
+    `skip_timesteps` leaves and sampled back (host loop), or the library cuts and noises the same on the device (`windows="library"`).
+    `stream_id` (default 0): the Philox stream of the call, shared by the B clips (slot b of it).  `clip_ids` (B ints, instead of
+    `stream_id`): clip i draws from the stream (seed, clip_ids[i]) -- the same motion in any batch, slot, lane or rank."""
     cfg = model.cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
     B = int(feats[0].shape[0])
+    stream_id, keyed = _clip_ids(clip_ids, stream_id, B)
     if _check_windows(windows, sample_fn):
         diffusion.manual_seed(seed, stream_id)
         sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
         return diffusion.sample_clip(model, list(feats), sty, seed0=seed_pose, root_shift=smoothing, keep_last_tail=False,
                                      ddim=ddim, eta=eta, skip_timesteps=skip_timesteps, inpainting_mask=inpainting_mask,
-                                     inpainted_motion=inpainted_motion, init_motion=init_motion)
+                                     inpainted_motion=inpainted_motion, init_motion=init_motion, **keyed)
     sample_fn = sample_fn or _loop_fn(diffusion, ddim, eta)
     diffusion.manual_seed(seed, stream_id)          # torch.manual_seed(seed) at sample.py:212
     shape = (B, J, 1, T)
@@ -260,7 +291,7 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
         y = _constrained(y, cfg, inpainting_mask, inpainted_motion, c, False)
         s = sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=skip_timesteps,
                       init_image=_window_init(cfg, init_motion, seed_pose, c, False), progress=False, dump_steps=None, noise=None,
-                      const_noise=False)
+                      const_noise=False, **keyed)
         _zeggs_stitch(out, s, S, smoothing, use_torch)
     if inpainting_mask is not None:
         _release_window_constraint(diffusion, [model])
@@ -269,7 +300,7 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
 
 def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456, smoothing=True, skip_timesteps=0,
                            stream_ids=None, ddim=False, eta=0.0, kernel_set="recommended", *, windows="host", inpainting_mask=None,
-                           inpainted_motion=None, init_motion=None):
+                           inpainted_motion=None, init_motion=None, clip_ids=None):
     """Several clips of one GPU advanced concurrently on sampling LANES ("one clip per stream", BASELINE config[3]): `lanes`
     are N DSGDenoiser lanes over one copy of the weights (`model.clone()`); lane i samples the B clips of
     feats_per_lane[i] (K per-window features [B, T, A_src]; B = 1: one clip per lane) on its own HSA queue and the library
@@ -281,7 +312,9 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
     block each other (measured: 4 lanes 2.7x one lane, 8 lanes slower than one) -- put the remaining clips into the lanes'
     batches.  `inpainting_mask` / `inpainted_motion`: per-lane lists of clip-level constraints [B, K*stride - n_seed, J] as in
     `generate_clip` (an entry may be None: that lane runs unconstrained); `init_motion`: a per-lane list of clips to edit as in
-    `generate_clip` (an entry may be None: that lane starts from noise).  Returns [N * B, K*stride - n_seed, J], lane-major."""
+    `generate_clip` (an entry may be None: that lane starts from noise).  `clip_ids` (instead of `stream_ids`): one list of B ints per
+    lane, the clip in lane i, slot b draws from the stream (seed, clip_ids[i][b]) -- any arrangement of the same clips over lanes and
+    batches gives the same motion per clip under one kernel set.  Returns [N * B, K*stride - n_seed, J], lane-major."""
     n = len(lanes)
     inp = _per_lane(inpainting_mask, inpainted_motion, n)
     inits = _per_lane_init(init_motion, n)
@@ -292,7 +325,7 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
         raise ValueError("one feature list per lane, the same number of windows each")
     use_torch = L.is_torch(feats_per_lane[0][0])
     B = int(feats_per_lane[0][0].shape[0])
-    stream_ids = list(range(n)) if stream_ids is None else list(stream_ids)
+    stream_ids, keyed = _lane_clip_ids(clip_ids, stream_ids, n, B)
     with _lane_kernel_sets(lanes, B, kernel_set):
         diffusion.manual_seed(seed, 0)
         shape = (B, J, 1, T)
@@ -308,14 +341,14 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
             return np.concatenate(diffusion.sample_clip_multi(list(lanes), [list(f) for f in feats_per_lane], stys, root_shift=smoothing,
                                                               keep_last_tail=False, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
                                                               seeds=[seed] * n, stream_ids=stream_ids, inpainting_masks=[p[0] for p in inp],
-                                                              inpainted_motions=[p[1] for p in inp], init_motions=inits), axis=0)
+                                                              inpainted_motions=[p[1] for p in inp], init_motions=inits, **keyed), axis=0)
         outs = [[] for _ in range(n)]
         for c in range(K):
             ys = [{"y": _constrained(_zeggs_window_y(cfg, feats_per_lane[i][c], stys[i], outs[i][-1] if outs[i] else None, None, use_torch, mask),
                                      cfg, inp[i][0], inp[i][1], c, False)} for i in range(n)]
             ss = diffusion.p_sample_loop_multi(list(lanes), shape, ys, seeds=[seed] * n, stream_ids=stream_ids,
                                                skip_timesteps=skip_timesteps, ddim=ddim, eta=eta,
-                                               init_images=[_window_init(cfg, inits[i], None, c, False) for i in range(n)])
+                                               init_images=[_window_init(cfg, inits[i], None, c, False) for i in range(n)], **keyed)
             for i in range(n):
                 _zeggs_stitch(outs[i], ss[i], S, smoothing, use_torch)
         if inpainting_mask is not None:
@@ -383,7 +416,7 @@ def _dsgplus_stitch(out, s, S, use_torch):
 
 
 def _dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division, seed, stream_ids,
-                     skip_timesteps, ddim, eta, inp=None, inits=None):
+                     skip_timesteps, ddim, eta, inp=None, inits=None, keyed=None):
     """The DSG+ clips of every lane through DSGDiffusion.sample_clip_multi: the per-window features as `_dsgplus_window_y` builds them,
     then crop + feature division as `_dsgplus_finish`."""
     cfg = lanes[0].cfg
@@ -393,7 +426,7 @@ def _dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, 
     seqs = diffusion.sample_clip_multi(list(lanes), audio, [sty] * len(lanes), seed0s=list(seed0s), root_shift=False, keep_last_tail=True,
                                        ddim=ddim, eta=eta, skip_timesteps=skip_timesteps, seed_lasts=seed_lasts, seeds=[seed] * len(lanes),
                                        stream_ids=stream_ids, inpainting_masks=None if inp is None else [p[0] for p in inp],
-                                       inpainted_motions=None if inp is None else [p[1] for p in inp], init_motions=inits)
+                                       inpainted_motions=None if inp is None else [p[1] for p in inp], init_motions=inits, **(keyed or {}))
     return [np.ascontiguousarray(q[:, :real_n_frames, : cfg.njoints // feature_division], dtype=np.float32) for q in seqs]
 
 
@@ -412,13 +445,14 @@ def _dsgplus_finish(out, S, J, real_n_frames, feature_division, use_torch):
 def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, seed0s, real_n_frames, seed=123456, skip_timesteps=0,
                                    stream_ids=None, seed_lasts=None, feature_division=3, ddim=False, eta=0.0,
                                    kernel_set="recommended", *, windows="host", inpainting_mask=None, inpainted_motion=None,
-                                   init_motion=None):
+                                   init_motion=None, clip_ids=None):
     """`generate_clips_streams` for the DSG+ window loop (BEAT-TWH sample.py:98-192; all three model names of that tree): lane i
     samples the B clips of feats_per_lane[i] (K per-window features), seeded by seed0s[i] [B, J, 1, S] (and seed_lasts[i] for
     DiffuseStyleGesture++), on its own HSA queue; the lanes' step loops are interleaved by the library.  Lane i is bit-identical
     to `generate_clip_dsgplus(lanes[i], ..., stream_id=stream_ids[i])` run alone on the same lane under the same kernel set.
     `inpainting_mask` / `inpainted_motion`: per-lane lists of clip-level constraints [B, K*stride, J] as in `generate_clip_dsgplus`
-    (an entry may be None); `init_motion`: a per-lane list of clips [B, K*stride, J] to edit (an entry may be None).  Returns
+    (an entry may be None); `init_motion`: a per-lane list of clips [B, K*stride, J] to edit (an entry may be None); `clip_ids`: one list
+    of B ints per lane instead of `stream_ids`, every clip its own stream as in `generate_clips_streams`.  Returns
     [N * B, real_n_frames, J // feature_division], lane-major."""
     n = len(lanes)
     inp = _per_lane(inpainting_mask, inpainted_motion, n)
@@ -430,7 +464,7 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
         raise ValueError("one feature list and one seed clip per lane, the same number of windows each")
     use_torch = L.is_torch(feats_per_lane[0][0])
     B = int(feats_per_lane[0][0].shape[0])
-    stream_ids = list(range(n)) if stream_ids is None else list(stream_ids)
+    stream_ids, keyed = _lane_clip_ids(clip_ids, stream_ids, n, B)
     with _lane_kernel_sets(lanes, B, kernel_set):
         diffusion.manual_seed(seed, 0)
         shape = (B, J, 1, T)
@@ -443,7 +477,7 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
         sty = _style_batch(styles, B, use_torch, dev)
         if _check_windows(windows):
             return np.concatenate(_dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division,
-                                                   seed, stream_ids, skip_timesteps, ddim, eta, inp, inits), axis=0)
+                                                   seed, stream_ids, skip_timesteps, ddim, eta, inp, inits, keyed), axis=0)
         outs = [[] for _ in range(n)]
         for c in range(K):
             ys = [{"y": _constrained(_dsgplus_window_y(cfg, feats_per_lane[i], c, sty, seed0s[i] if c == 0 else outs[i][-1][..., -S:],
@@ -451,7 +485,7 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
                                      cfg, inp[i][0], inp[i][1], c, True)} for i in range(n)]
             ss = diffusion.p_sample_loop_multi(list(lanes), shape, ys, seeds=[seed] * n, stream_ids=stream_ids,
                                                skip_timesteps=skip_timesteps, ddim=ddim, eta=eta,
-                                               init_images=[_window_init(cfg, inits[i], seed0s[i], c, True) for i in range(n)])
+                                               init_images=[_window_init(cfg, inits[i], seed0s[i], c, True) for i in range(n)], **keyed)
             for i in range(n):
                 _dsgplus_stitch(outs[i], ss[i], S, use_torch)
         if inpainting_mask is not None:
@@ -460,8 +494,8 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
 
 
 def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, seed=123456, skip_timesteps=0,
-                          sample_fn=None, stream_id=0, seed_last=None, feature_division=3, *, windows="host", ddim=False, eta=0.0,
-                          inpainting_mask=None, inpainted_motion=None, init_motion=None):
+                          sample_fn=None, stream_id=None, seed_last=None, feature_division=3, *, windows="host", ddim=False, eta=0.0,
+                          inpainting_mask=None, inpainted_motion=None, init_motion=None, clip_ids=None):
     """DSG+ window loop (BEAT-TWH sample.py:98-192), attention4: zero-padded tail, no left audio context, GT seed for
     window 0, no root shift, last window kept whole, first S frames dropped, crop, keep the first J/3 features.
     `model.cfg.variant == 3` is that tree's "DiffuseStyleGesture" (attention3 at BEAT dims): S frames of left audio context.
@@ -470,11 +504,13 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
     for every window (sample.py:85-93) -- is passed as y['seed_last'].  `inpainting_mask` / `inpainted_motion` [B, K*stride, J]
     (both or neither): motion inpainting over the whole clip as in `generate_clip`, in the coordinates of the stitched clip: the full J
     features, before the crop to `real_n_frames` and the feature division.  `init_motion` [B, K*stride, J]: an existing clip to edit as in
-    `generate_clip`, in the same coordinates (the full J features, K*stride frames)."""
+    `generate_clip`, in the same coordinates (the full J features, K*stride frames).  `stream_id` (default 0) / `clip_ids` (B ints: every
+    clip its own Philox stream (seed, clip_ids[i])) as in `generate_clip`."""
     cfg = model.cfg
     S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
     B = int(feats[0].shape[0])
+    stream_id, keyed = _clip_ids(clip_ids, stream_id, B)
     library = _check_windows(windows, sample_fn)
     sample_fn = sample_fn or _loop_fn(diffusion, ddim, eta)
     diffusion.manual_seed(seed, stream_id)
@@ -486,7 +522,8 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
                                 feature_division, seed, [stream_id], skip_timesteps, ddim, eta,
                                 _per_lane(None if inpainting_mask is None else [inpainting_mask],
                                           None if inpainted_motion is None else [inpainted_motion], 1),
-                                None if init_motion is None else [init_motion])[0]
+                                None if init_motion is None else [init_motion],
+                                {"clip_streams": [keyed["clip_streams"]]} if keyed else None)[0]
     if use_torch:
         import torch
         dev = feats[0].device
@@ -498,7 +535,7 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
         y = _constrained(y, cfg, inpainting_mask, inpainted_motion, c, True)
         s = sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=skip_timesteps,
                       init_image=_window_init(cfg, init_motion, seed0, c, True), progress=False, dump_steps=None, noise=None,
-                      const_noise=False)
+                      const_noise=False, **keyed)
         _dsgplus_stitch(out, s, S, use_torch)
     if inpainting_mask is not None:
         _release_window_constraint(diffusion, [model])

@@ -288,6 +288,21 @@ int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const float* mot
  * sequence does: windows c > 0 start from the given root trajectory and the hand-off then moves them by the window's delta.
  * Added without a version step, as the two inpainting setters: dsg_version() stays 330. */
 int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int n_frames, void* stream);
+/* Per-element noise streams ("keyed noise") for dsg_sample / _multi / dsg_sample_clip / _multi.  seeds, stream_ids: HOST uint64[B], copied by
+ * the call.  While set, element b of the batch draws from its own pair (seed_b, sid_b): draw d at frame f, feature j is
+ *   philox4x32_10(ctr = ((f * Jq + j) >> 2, d, sid_b lo, sid_b hi), key = (seed_b lo, seed_b hi)) + Box-Muller,   Jq = J rounded up to 4,
+ * that is the [1, J, 1, T] tensor of (seed_b, sid_b): the batch term of the counter is 0 and the key is per element.  An element's noise is
+ * therefore exactly the noise it gets sampled alone (B = 1, args->seed = seed_b, args->stream_id = sid_b), whichever batch, slot, lane or rank
+ * it rides in.  Draw indices stay per call: draw_base for x_T / the q_sample noise, draw_base + 1 + i for step i, window c of a clip call from
+ * draw_base + c * (1 + n_run).
+ * seeds == NULL: every element uses args->seed.  stream_ids == NULL with seeds: stream id 0 for every element.  stream_ids == NULL && seeds ==
+ * NULL: off (B ignored).  B < 1 or B > max_batch: DSG_E_INVALID.  Sticky; a dsg_clone starts without; every lane has its own.  While set,
+ * args->stream_id is ignored and a sampling call needs the same B (else DSG_E_INVALID with both numbers).  With guidance B is the user batch
+ * and the unconditional twins follow their element.  const_noise: element 0's stream for everyone.  step_noise / init_noise replace the draws
+ * exactly as they do without.  A chain run in pieces (first_step / max_steps) uses the same streams in every piece.  Without this call every
+ * draw is what it always was.  Reference counterpart: none (th.randn consumes one global generator, gaussian_diffusion.py:704, :542).
+ * Added without a version step, as dsg_set_inpainting and dsg_set_clip_init: dsg_version() stays 330. */
+int dsg_set_noise_streams(dsg_handle* h, const uint64_t* seeds, const uint64_t* stream_ids, int B);
 /* Kernel set of a handle (DSG_KSET_*; sticky; clones inherit the source's at dsg_clone).  dsg_recommend_kernel_set: the set
  * measured fastest for `lanes` lanes of batch B advanced together (lanes = 1: what DSG_KSET_AUTO picks) -- several lanes share
  * the CUs and prefer the throughput-shaped sets earlier; the caller applies it to each lane.  dsg_last_kernel_set: the set the
@@ -322,6 +337,11 @@ int dsg_trim(int device, long long* bytes_released, long long* bytes_held);
  * noise the fused sampler uses for that draw index (x_T is draw_base, step i is draw_base + 1 + i).  Stands in for
  * th.randn / th.randn_like of gaussian_diffusion.py:704, :542 in the generic loop. */
 int dsg_noise(float* out, int B, int J, int T, uint64_t seed, uint64_t stream_id, uint32_t draw, void* stream);
+/* dsg_noise with per-element streams: out [B, J, 1, T] (device, or host), element b = draw `draw` of (seeds[b], stream_ids[b]) by the definition
+ * of dsg_set_noise_streams -- bit for bit dsg_noise(B = 1, seeds[b], stream_ids[b], draw), and what the fused loops of a handle with those
+ * streams consume for that draw index.  seeds, stream_ids: HOST uint64[B]; a NULL array reads as zeros.  Reference counterpart: none (th.randn
+ * consumes one global generator, gaussian_diffusion.py:704, :542). */
+int dsg_noise_streams(float* out, int B, int J, int T, const uint64_t* seeds, const uint64_t* stream_ids, uint32_t draw, void* stream);
 
 /* ZEGGS pose vectors -> BVH (pose2bvh of main/process/process_zeggs_bvh.py:219-275 and what it calls; host code, no GPU).
  * poses: host [frames, 1141], dtype 0 = float32, 1 = float64.  mean / std (float64[1141], both or neither): the sampler's
