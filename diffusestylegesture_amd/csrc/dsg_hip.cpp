@@ -186,8 +186,15 @@ struct dsg_handle {
     int* t_arr = nullptr; unsigned* dyn = nullptr;
     // per-element noise streams (dsg_set_noise_streams): nkB user batch elements, 0 = off; nkeys = their keys {seed lo, seed hi, stream lo,
     // stream hi} (nk_seeds == false: the seed words come from args->seed, per call).  dyn_host: the staging copy of `dyn`
-    // (8 + 4 * max_batch words) every sampling call uploads
+    // (8 + 5 * max_batch words: + the draw offsets) every sampling call uploads
     int nkB = 0; bool nk_seeds = false; std::vector<unsigned> nkeys, dyn_host;
+    // per-element draw offsets of keyed noise (GemmArgs::draw_off; words 8 + 4 max_batch .. of `dyn`): dsg_sample_clip_queue sets them per round
+    // (draw_offs_on, for the rounds of that call only); every other keyed call uploads zeros
+    bool draw_offs_on = false; std::vector<unsigned> draw_offs;
+    // dsg_sample_clip_queue: the round's per-slot style / audio gathered on the device, the hand-off table (k_window_handoff_q) and the host
+    // copies of what is uploaded per round (they outlive the copies).  Allocated on first use
+    float *q_style = nullptr, *q_audio = nullptr; HandoffSlot* q_slots = nullptr;
+    std::vector<HandoffSlot> q_slots_host; std::vector<float> q_scale_host;
     int latency_mode = -1;               // dsg_config.latency_mode: -1 auto, 0 never the LATENCY set, 1 always
 #ifndef DSG_EMU
     dsg_aql::Ctx aql;                    // hand-written AQL submission of the step loop (dsg_aql.h)
@@ -615,8 +622,8 @@ extern "C" int dsg_create(const dsg_config* c, dsg_handle** out) {
     CHK(dalloc(h, &h->mask, (size_t)B * h->T));
     CHK(dalloc(h, &h->ctr, 8));
     CHK(dalloc(h, &h->cfg_scale, (size_t)B));
-    CHK(dalloc(h, &h->dyn, 8 + 4 * (size_t)B));      // + the key table of keyed noise (GemmArgs::dyn)
-    h->dyn_host.assign(8 + 4 * (size_t)B, 0u);
+    CHK(dalloc(h, &h->dyn, 8 + 5 * (size_t)B));      // + the key table of keyed noise (GemmArgs::dyn) + its draw offsets (GemmArgs::draw_off)
+    h->dyn_host.assign(8 + 5 * (size_t)B, 0u);
     CHK(dalloc(h, &h->t_arr, (size_t)B));
     // the xs32 master is read as a GEMM operand in fp32 mode: rows padded to a 16-row tile exist (allocated above)
     return 0;
@@ -1600,7 +1607,7 @@ static GemmArgs gemm_linear2(const dsg_handle* h, const GemmArgs& z, int M, cons
 static GemmArgs gemm_pose_head(const dsg_handle* h, const GemmArgs& z, int M, const Layer& last) {
     GemmArgs g = gemm_of(h, z, M, h->Jp, h->D, h->Wp_out, h->b_out);
     g.X = h->pre2; g.ln_g = last.g2; g.ln_b = last.be2;
-    g.xs32 = h->xs32; g.xsA = is_bf16(h) ? h->xsA : nullptr; g.fwd_out = h->fwd_out; g.dyn = h->dyn;
+    g.xs32 = h->xs32; g.xsA = is_bf16(h) ? h->xsA : nullptr; g.fwd_out = h->fwd_out; g.dyn = h->dyn; g.draw_off = h->dyn + 8 + 4 * (size_t)h->Bmax;
     return g;
 }
 // the step control of the two GEMMs that read / advance it (k_in, pose head)
@@ -2090,9 +2097,9 @@ static int run_step_p(dsg_handle* h, const StepCtx& c) {
 }
 
 static int launch_x_in(dsg_handle* h, const float* x, const float* init, int do_q, float qa, float qb, int use_philox,
-                       NoiseKey nk, const unsigned* keys, unsigned draw, int B, const KernelSel& ks) {
+                       NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B, const KernelSel& ks) {
     XInArgs a;
-    a.keys = keys;
+    a.keys = keys; a.offs = offs;
     a.dupB = h->cfgB; a.xs_frag = ks.xs_frag ? 1 : 0;
     a.x = x; a.init = init; a.do_q = do_q; a.qa = qa; a.qb = qb; a.use_philox = use_philox; a.nkey = nk; a.draw = draw;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.xs32 = h->xs32;
@@ -2105,9 +2112,10 @@ static int launch_x_in(dsg_handle* h, const float* x, const float* init, int do_
     return 0;
 }
 // window h->clip_init_c of a clip that starts from the handle's clip-level init motion (dsg_sample_clip): cut + q_sample + state write
-static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, const unsigned* keys, unsigned draw, int B, const KernelSel& ks) {
+static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B,
+                            const KernelSel& ks) {
     ClipXInArgs a;
-    a.keys = keys;
+    a.keys = keys; a.offs = offs;
     a.init = h->cinit_motion; a.c_seed = h->c_seed; a.qa = qa; a.qb = qb; a.nkey = nk; a.draw = draw;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.S = h->S; a.n_out = h->clip_init_n_out; a.c = h->clip_init_c;
     a.xs32 = h->xs32; a.xsA = is_bf16(h) ? h->xsA : nullptr;
@@ -2312,7 +2320,7 @@ extern "C" int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, floa
     StepCtx c; c.B = rows; c.out_mode = OUT_FORWARD; c.use_ctr = false; c.ext_noise = nullptr; c.const_noise = 0;
     CHK(select_kernels(h, rows, c.ks));
     CHK(ensure_set_buffers(h, c.ks));
-    CHK(launch_x_in(h, xd, nullptr, 0, 0.f, 0.f, 0, nk, nullptr, 0, B, c.ks));
+    CHK(launch_x_in(h, xd, nullptr, 0, 0.f, 0.f, 0, nk, nullptr, nullptr, 0, B, c.ks));
     CHK(run_step_p(h, c));
     CHK(from_dev(h, out, h->fwd_out, n));
     CHK(order_before(h, stream));
@@ -2488,14 +2496,19 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
             dyn[8 + 4 * b] = h->nk_seeds ? k[0] : nk.k0; dyn[9 + 4 * b] = h->nk_seeds ? k[1] : nk.k1;
             dyn[10 + 4 * b] = k[2]; dyn[11 + 4 * b] = k[3];
         }
-        HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? 8 + 4 * (size_t)h->nkB : 5) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+        // the draw offsets behind the table: the queue's (dsg_sample_clip_queue, per round), zeros in every other keyed call -- written with
+        // every keyed upload, so that nothing of a queue call can outlive it on the device
+        const size_t off0 = 8 + 4 * (size_t)h->Bmax;
+        for (int b = 0; b < h->nkB; ++b) dyn[off0 + b] = h->draw_offs_on ? h->draw_offs[b] : 0u;
+        HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? off0 + (size_t)h->nkB : 5) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
     }
     const unsigned* keys_d = keyed ? h->dyn + 8 : nullptr;
+    const unsigned* offs_d = keyed ? h->dyn + 8 + 4 * (size_t)h->Bmax : nullptr;
     if (h->clip_init_c >= 0)      // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
-        CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, a->draw_base, B, ksel));
+        CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
     else
         CHK(launch_x_in(h, noise_d, init_d, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0],
-                        noise_d ? 0 : 1, nk, keys_d, a->draw_base, B, ksel));
+                        noise_d ? 0 : 1, nk, keys_d, offs_d, a->draw_base, B, ksel));
     // replayed per-step noise
     const float* ext = nullptr;
     if (a->step_noise) {
@@ -2860,6 +2873,200 @@ extern "C" int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* con
                                      const dsg_sample_args* args, int K, int root_shift, int keep_last_tail, float** outs, int B,
                                      void* stream) {
     return sample_clip(lanes, n, styles, seed0s, audios, mask_local, mask_batch, scales, args, K, root_shift, keep_last_tail, outs, B, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// dsg_sample_clip_queue: clips of different lengths over one batch of slots.  The plan (dsg_clip_queue_plan) gives every clip a slot and a
+// first round; a round is one iteration of sample_clip's window loop for every lane at the constant batch B, with per-slot conditioning,
+// per-slot Philox keys and draw offsets (a slot on window c of its clip draws what dsg_sample_clip draws for window c of that clip alone),
+// and the per-slot hand-off (k_window_handoff_q).  A slot without a clip in a round is dead: it runs on whatever conditioning it holds --
+// rows are independent -- and writes nothing.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int dsg_clip_queue_plan(const int32_t* K, int n_jobs, int n_slots, int32_t* slot, int32_t* first_round, int32_t* n_rounds) {
+    if (!K || !slot || !first_round || !n_rounds) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: null argument");
+    if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: n_jobs < 1");
+    if (n_slots < 1) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: n_slots < 1");
+    for (int j = 0; j < n_jobs; ++j)
+        if (K[j] < 1) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: job " + std::to_string(j) + " has K < 1");
+    std::vector<int> order(n_jobs);
+    for (int j = 0; j < n_jobs; ++j) order[j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return K[a] > K[b]; });      // longest first, ties by lower index
+    std::vector<int64_t> load(n_slots, 0);
+    int64_t most = 0;
+    for (int j : order) {
+        int best = 0;
+        for (int s = 1; s < n_slots; ++s) if (load[s] < load[best]) best = s;      // least load so far, ties: lowest slot
+        if (load[best] + K[j] > 0x7fffffff) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: more than 2^31 - 1 rounds");
+        slot[j] = best; first_round[j] = (int32_t)load[best];
+        load[best] += K[j];
+        most = std::max(most, load[best]);
+    }
+    *n_rounds = (int32_t)most;
+    return 0;
+}
+
+static int launch_handoff_q(dsg_handle* h, int B, int round, int root_shift, int keep_last_tail) {
+    HandoffQArgs a;
+    a.xs32 = h->xs32; a.tail_in = h->clip_tail[(round + 1) & 1]; a.tail_out = h->clip_tail[round & 1]; a.c_seed = h->c_seed; a.slots = h->q_slots;
+    a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S;
+    a.root_shift = root_shift ? 1 : 0; a.keep_last_tail = keep_last_tail ? 1 : 0;
+    const size_t n = (size_t)B * h->T * (h->Jp / 4);
+    hipLaunchKernelGGL(k_window_handoff_q, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job* jobs, int n_jobs, int B, const uint8_t* mask_local, int guided,
+                                     const dsg_sample_args* args, int root_shift, int keep_last_tail, void* stream) {
+    if (!hs || !jobs || !args || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: bad argument");
+    if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
+    if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: n_jobs < 1");
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        if (!h) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: null handle");
+        for (int j = 0; j < i; ++j) if (hs[j] == h) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: a handle appears twice");
+        if (!h->finalized) return fail(DSG_E_STATE, "dsg_sample_clip_queue before dsg_finalize_weights");
+        if (h->sched.n == 0) return fail(DSG_E_STATE, "dsg_sample_clip_queue before dsg_set_schedule");
+        if (h->cfg.device != hs[0]->cfg.device) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: lanes must live on one device");
+        if (h->J != hs[0]->J || h->T != hs[0]->T || h->S != hs[0]->S || h->Ta != hs[0]->Ta || h->As != hs[0]->As ||
+            h->cfg.style_dim_in != hs[0]->cfg.style_dim_in || h->cfg.variant != hs[0]->cfg.variant)
+            return fail(DSG_E_INVALID, "dsg_sample_clip_queue: lanes of one model");
+        if (h->sched.n != hs[0]->sched.n) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: one step count for every lane");
+        if (h->S <= 0 || 2 * h->S >= h->T) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the window hand-off needs 0 < 2 * n_seed < n_poses");
+        const int rows = guided ? 2 * B : B;
+        if (B < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: B < 1");
+        if (rows > h->Bmax) return fail(DSG_E_INVALID, guided ? "dsg_sample_clip_queue: classifier-free guidance needs max_batch >= 2 * B" : "dsg_sample_clip_queue: B exceeds max_batch");
+        if (h->nkB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries noise streams (dsg_set_noise_streams(h, NULL, NULL, 0) first): every job brings its own pair");
+        if (h->inpB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries a window-level inpainting constraint (dsg_set_inpainting(h, NULL, NULL, ...) first)");
+        if (h->cinpB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries a clip-level inpainting constraint (dsg_set_clip_inpainting(h, NULL, NULL, ...) first): per-clip inpainting through the queue is not implemented");
+        if (h->cinitB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries a clip-level init motion (dsg_set_clip_init(h, NULL, ...) first): per-clip editing through the queue is not implemented");
+    }
+    if (args->step_noise || args->init_noise || args->init_image || args->n_dump || args->first_step || args->max_steps || args->const_noise)
+        return fail(DSG_E_INVALID, "dsg_sample_clip_queue: step_noise / init_noise / init_image / dump_steps / first_step / max_steps / const_noise are not for a queue of clips");
+    if (args->mode != DSG_MODE_DDPM && args->mode != DSG_MODE_DDIM) return fail(DSG_E_INVALID, "mode");
+    if (args->skip_timesteps < 0 || args->skip_timesteps >= hs[0]->sched.n) return fail(DSG_E_INVALID, "skip_timesteps out of range");
+    const int variant5 = hs[0]->cfg.variant == 5;
+    for (int j = 0; j < n_jobs; ++j) {
+        const dsg_clip_job& q = jobs[j];
+        if (q.K < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has K < 1");
+        if (!q.style || !q.audio || !q.out) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has a null style / audio / out");
+        if (variant5 && !q.seed_last) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: variant 5 needs seed_last for every job (job " + std::to_string(j) + " has none)");
+    }
+    const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J, Ta = hs[0]->Ta, As = hs[0]->As, sdi = hs[0]->cfg.style_dim_in;
+    const int n_slots = n * B, keep = T - S;
+    const int n_run = hs[0]->sched.n - args->skip_timesteps;
+    std::vector<int32_t> Ks(n_jobs), slot(n_jobs), first(n_jobs);
+    for (int j = 0; j < n_jobs; ++j) Ks[j] = jobs[j].K;
+    int32_t n_rounds = 0;
+    CHK(dsg_clip_queue_plan(Ks.data(), n_jobs, n_slots, slot.data(), first.data(), &n_rounds));
+    std::vector<int> sched((size_t)n_rounds * n_slots, -1);      // [round][slot] -> job, -1: dead
+    for (int j = 0; j < n_jobs; ++j)
+        for (int c = 0; c < Ks[j]; ++c) sched[(size_t)(first[j] + c) * n_slots + slot[j]] = j;
+    HIPCHK(hipSetDevice(hs[0]->cfg.device));
+    // the clips: the caller's tensor where it is device memory, else a piece of ONE device buffer (lane 0's) and one copy per job at the end
+    std::vector<float*> clip(n_jobs);
+    std::vector<size_t> n_clip(n_jobs);
+    {
+        size_t need = 0;
+        for (int j = 0; j < n_jobs; ++j) {
+            n_clip[j] = ((size_t)Ks[j] * keep - (keep_last_tail ? 0 : S)) * J;
+            if (!is_device_ptr(jobs[j].out)) need += n_clip[j];
+        }
+        dsg_handle* h0 = hs[0];
+        if (need > h0->clip_out_cap) { CHK(dalloc(h0, &h0->clip_out, need, false)); h0->clip_out_cap = need; }
+        size_t at = 0;
+        for (int j = 0; j < n_jobs; ++j) {
+            if (is_device_ptr(jobs[j].out)) clip[j] = jobs[j].out;
+            else { clip[j] = h0->clip_out + at; at += n_clip[j]; }
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        for (int k = 0; k < 2; ++k)
+            if (!h->clip_tail[k]) CHK(dalloc(h, &h->clip_tail[k], (size_t)h->Bmax * J * S));
+        if (!h->q_style) CHK(dalloc(h, &h->q_style, (size_t)h->Bmax * sdi));
+        if (!h->q_audio) CHK(dalloc(h, &h->q_audio, (size_t)h->Bmax * Ta * As));
+        if (!h->q_slots) CHK(dalloc(h, &h->q_slots, (size_t)h->Bmax));
+        h->q_slots_host.assign(B, HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0});
+        h->q_scale_host.assign(B, 1.f);
+        h->draw_offs.assign(B, 0u);
+        CHK(order_after(h, stream));
+    }
+    // What the call sets on a lane for its rounds -- the keyed table and its draw offsets, lanes_now, (variant 5) the batch of seed_last -- is
+    // put back on every return path.  Every lane came in unkeyed (checked above).  Variant 5: the rows of c_seed_last now hold the jobs' snippets,
+    // so the lane asks for dsg_set_seed_last again, as a fresh handle does
+    struct QueueNow {
+        dsg_handle** hs; int n; bool seed_last_written = false;
+        QueueNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) { hs[i]->lanes_now = n; hs[i]->clip_ms = 0.0; } }
+        ~QueueNow() {
+            for (int i = 0; i < n; ++i) {
+                dsg_handle* h = hs[i];
+                h->lanes_now = 1; h->nkB = 0; h->nk_seeds = false; h->nkeys.clear(); h->draw_offs_on = false;
+                if (seed_last_written) h->seed_last_B = 0;
+            }
+        }
+    } queue_now(hs, n);
+    std::vector<SampleJob> sjobs(n);
+    std::vector<dsg_sample_args> wargs(n, *args);      // (draw_base is args->draw_base for every clip: the windows are told apart by the offsets)
+    const size_t n_tail = (size_t)J * S;
+    for (int r = 0; r < n_rounds; ++r) {
+        for (int i = 0; i < n; ++i) {
+            dsg_handle* h = hs[i];
+            h->nkeys.assign(4 * (size_t)B, 0u);
+            for (int b = 0; b < B; ++b) {
+                const int j = sched[(size_t)r * n_slots + (size_t)b * n + i];      // global slot s: lane s % n, position s / n
+                HandoffSlot& hq = h->q_slots_host[b];
+                h->draw_offs[b] = 0u;
+                if (j < 0) { hq = HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0}; continue; }
+                const dsg_clip_job& q = jobs[j];
+                const int c = r - first[j];
+                CHK(upload(h, h->q_style + (size_t)b * sdi, q.style, (size_t)sdi * sizeof(float)));
+                CHK(upload(h, h->q_audio + (size_t)b * Ta * As, q.audio + (size_t)c * Ta * As, (size_t)Ta * As * sizeof(float)));
+                h->q_scale_host[b] = q.scale;
+                if (c == 0) {
+                    if (q.seed0) CHK(upload(h, h->c_seed + b * n_tail, q.seed0, n_tail * sizeof(float)));
+                    else HIPCHK(hipMemsetAsync(h->c_seed + b * n_tail, 0, n_tail * sizeof(float), h->stream));
+                    if (variant5) {
+                        queue_now.seed_last_written = true;
+                        CHK(upload(h, h->c_seed_last + b * n_tail, q.seed_last, n_tail * sizeof(float)));
+                    }
+                }
+                h->nkeys[4 * b] = (unsigned)(q.seed & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(q.seed >> 32);
+                h->nkeys[4 * b + 2] = (unsigned)(q.stream_id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(q.stream_id >> 32);
+                h->draw_offs[b] = (uint32_t)c * (uint32_t)(1 + n_run);      // what dsg_sample_clip alone consumes before window c
+                hq = HandoffSlot{clip[j], (int)(n_clip[j] / J), c, (c == 0 ? HQ_FIRST : 0) | (c == Ks[j] - 1 ? HQ_LAST : 0), 0};
+            }
+            h->nkB = B; h->nk_seeds = true; h->draw_offs_on = true;
+            if (variant5) h->seed_last_B = B;
+            // the round's hand-off table, uploaded here: behind the previous round's hand-off on the stream, and in front of the point where
+            // sample_prepare drains the stream -- so the host copy is free to change in the next round
+            HIPCHK(hipMemcpyAsync(h->q_slots, h->q_slots_host.data(), (size_t)B * sizeof(HandoffSlot), hipMemcpyHostToDevice, h->stream));
+            CHK(set_window_cond(h, h->q_style, h->c_seed, h->q_audio, mask_local, 1, B, 0, guided ? h->q_scale_host.data() : nullptr, stream));
+        }
+        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, sjobs[i]));
+        CHK(run_lanes(hs, n, wargs.data(), sjobs.data()));
+        for (int i = 0; i < n; ++i) {
+            dsg_handle* h = hs[i];
+            HIPCHK(hipEventRecord(h->ev_t1, h->stream));
+            if (h->aql_timing) h->clip_ms += h->aql_ms;
+            else {
+                float ms = 0.f;
+                HIPCHK(hipEventSynchronize(h->ev_t1));
+                HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+                h->clip_ms += ms;
+            }
+            CHK(launch_handoff_q(h, B, r, root_shift, keep_last_tail));
+        }
+    }
+    for (int j = 0; j < n_jobs; ++j)
+        if (clip[j] != jobs[j].out) CHK(from_dev(hs[slot[j] % n], jobs[j].out, clip[j], n_clip[j]));      // (on the stream of the lane that wrote it)
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        h->last_steps = n_rounds * n_run; h->timing_valid = true; h->clip_timing = true;
+        h->last_kset = sjobs[i].c.ks.set;
+        CHK(order_before(h, stream));
+    }
+    return 0;
 }
 
 extern "C" int dsg_sync(dsg_handle* h) {

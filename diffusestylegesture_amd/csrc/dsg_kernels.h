@@ -555,6 +555,8 @@ struct GemmArgs {
     int B;
     int const_noise;
     int keyed;              // EPI_OUT: per-element noise streams (dsg_set_noise_streams): the key of element b from dyn + 8, batch term of the counter 0
+    const unsigned* draw_off;   // keyed: uint32 [B] behind the key table (dyn + 8 + 4 max_batch: it does not move with the batch), element b's draw index is
+                            // dyn[4] + step + draw_off[b] (wraps) -- 0 everywhere but in dsg_sample_clip_queue, whose slots stand on different windows
     int ws_G;               // dsg_stream.h: row-block groups of the persistent grid (multiple of 8)
     int a_frag;             // PRO_DIRECT: A is stored fragment-major ([row tile][k-block][64 lanes][16 B], qk_off) -- hidden, attention rows
     int out_frag;           // EPI_GELU: the output goes out fragment-major (it is the next GEMM's A operand)
@@ -786,14 +788,16 @@ __device__ __forceinline__ void gemm_prefetch_tile(const GemmArgs& g, int m0, in
                     // (noise_key_of), with the batch term of the counter 0.  Requested here with pb / pr, in front of the main loop.  Keyed, a pass
                     // of the loop serves the lanes of ONE batch element of the wave (1 or 2 elements per 16-row tile); unkeyed there is one pass.
                     // This form costs no kernel a spill or a wave of occupancy; selecting the key's address per lane in a straight line did
-                    // (k_ws<EPI_OUT, 16, ONE>, at its bound of 128 registers: 8 bytes of scratch)
+                    // (k_ws<EPI_OUT, 16, ONE>, at its bound of 128 registers: 8 bytes of scratch).  The element's draw offset (GemmArgs::draw_off) is
+                    // read at the same point, one more workgroup-uniform word beside the key
                     bool todo = true;
                     do {
                         const int bu = g.keyed ? __builtin_amdgcn_readfirstlane(bn) : 0;
                         if (!g.keyed || bn == bu) {
                             NoiseKey nk = {g.dyn[0], g.dyn[1], g.dyn[2], g.dyn[3]};
-                            if (g.keyed) nk = noise_key_of(g.dyn + 8, bu);
-                            o.pz = philox_normal4((imul24((int)imul24(bn, g.keyed ? 0 : g.T) + f, g.Jq) + (unsigned)j0) >> 2, g.dyn[4] + (unsigned)step, nk);
+                            unsigned off = 0u;
+                            if (g.keyed) { nk = noise_key_of(g.dyn + 8, bu); off = g.draw_off[bu]; }
+                            o.pz = philox_normal4((imul24((int)imul24(bn, g.keyed ? 0 : g.T) + f, g.Jq) + (unsigned)j0) >> 2, g.dyn[4] + (unsigned)step + off, nk);
                             todo = false;
                         }
                     } while (todo);
@@ -1602,6 +1606,7 @@ struct XInArgs {
     int use_philox;         // draw noise 0 from the Philox stream when x == null
     NoiseKey nkey; unsigned draw;
     const unsigned* keys;   // keyed noise: the key table (noise_key_of), else null
+    const unsigned* offs;   // keyed noise: per-element draw offsets (GemmArgs::draw_off), element b draws `draw + offs[b]`; null: 0
     int B, J, Jp, Jq, T;
     float* xs32; void* xsA;
     int dupB;               // classifier-free guidance: batch element b is also written to row b + dupB (its unconditional twin)
@@ -1626,7 +1631,7 @@ __global__ void k_x_in(const XInArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (j0 + e < a.J) z[e] = a.x[((size_t)b * a.J + j0 + e) * a.T + f];
             } else if (a.use_philox) {
-                z = a.keys ? philox_normal4((unsigned)(((size_t)f * a.Jq + j0) >> 2), a.draw, noise_key_of(a.keys, b))
+                z = a.keys ? philox_normal4((unsigned)(((size_t)f * a.Jq + j0) >> 2), a.draw + (a.offs ? a.offs[b] : 0u), noise_key_of(a.keys, b))
                            : philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
             }
             if (a.do_q) {
@@ -1712,36 +1717,68 @@ __device__ __forceinline__ void handoff_store4(float* dst, const f32x4& v, int n
 #pragma unroll
     for (int e = 0; e < 4; ++e) if (e < n) dst[e] = v[e];
 }
+// One feature quad of a (slot, frame) row of the hand-off: spelled ONCE for k_window_handoff and k_window_handoff_q, which promise the same
+// bits (as q_sample1 for the two start kernels).  i = ((b * T + f) * Jp / 4 + quad); clip_out = the [n_out][J] clip of THIS slot
+__device__ __forceinline__ void handoff_row(const float* xs32, const float* tail_in, float* tail_out, float* c_seed, float* clip_out, size_t i,
+                                            int J, int Jp, int T, int S, int n_out, int c, int root_shift, int is_first, int is_last,
+                                            int keep_last_tail) {
+    const int nq = Jp / 4, keep = T - S;
+    const int j0 = (int)(i % nq) * 4;
+    const size_t bf = i / nq;
+    const int f = (int)(bf % T), b = (int)(bf / T);
+    if (j0 >= J) return;
+    const int nv = J - j0 < 4 ? J - j0 : 4;
+    f32x4 v = *(const f32x4*)(xs32 + bf * Jp + j0);
+    const float* t0 = tail_in + (size_t)b * S * J;      // frame 0 of the previous window's tail
+    if (!is_first && root_shift && j0 == 0) {
+        const float* s0 = xs32 + (size_t)b * T * Jp;
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+            if (e < nv) { const float delta = s0[e] - t0[e]; v[e] = v[e] - delta; }
+    }
+    if (!is_first && f == 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (e < nv) v[e] = t0[j0 + e] * 0.5f + v[e] * 0.5f;
+    }
+    const int df = c * keep + f - S;
+    if ((f < keep || (is_last && keep_last_tail)) && df >= 0 && df < n_out)
+        handoff_store4(clip_out + (size_t)df * J + j0, v, nv);
+    if (f >= keep) {
+        const int sf = f - keep;
+        handoff_store4(tail_out + ((size_t)b * S + sf) * J + j0, v, nv);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (e < nv) c_seed[((size_t)b * J + j0 + e) * S + sf] = v[e];
+    }
+}
 __global__ void k_window_handoff(const HandoffArgs a) {
-    const int nq = a.Jp / 4, keep = a.T - a.S;
-    const size_t n = (size_t)a.B * a.T * nq;
+    const size_t per = (size_t)a.T * (a.Jp / 4), n = (size_t)a.B * per;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        handoff_row(a.xs32, a.tail_in, a.tail_out, a.c_seed, a.clip_out + (i / per) * (size_t)a.n_out * a.J, i, a.J, a.Jp, a.T, a.S, a.n_out, a.c,
+                    a.root_shift, a.is_first, a.is_last, a.keep_last_tail);
+}
+// The hand-off of dsg_sample_clip_queue: the slots of the batch carry clips of different lengths, so what k_window_handoff takes as arguments
+// -- the clip a row goes to, its length, the window index, first / last -- comes per slot from a table in device memory (uploaded once per
+// round on the handle's stream).  A `dead` slot (no clip this round) writes nothing: not the clip, not the tail, not c_seed.  A slot that
+// starts a clip (is_first) neither shifts nor blends, whatever the slot's previous clip left in tail_in.
+struct HandoffSlot {
+    float* clip_out;        // [n_out][J] of the slot's clip
+    int n_out, c;           // its length and the window it stands on
+    int flags;              // HQ_FIRST | HQ_LAST | HQ_DEAD
+    int pad_;
+};
+enum { HQ_FIRST = 1, HQ_LAST = 2, HQ_DEAD = 4 };
+struct HandoffQArgs {
+    const float* xs32; const float* tail_in; float* tail_out; float* c_seed; const HandoffSlot* slots;
+    int B, J, Jp, T, S;
+    int root_shift, keep_last_tail;
+};
+__global__ void k_window_handoff_q(const HandoffQArgs a) {
+    const size_t per = (size_t)a.T * (a.Jp / 4), n = (size_t)a.B * per;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int j0 = (int)(i % nq) * 4;
-        const size_t bf = i / nq;
-        const int f = (int)(bf % a.T), b = (int)(bf / a.T);
-        if (j0 >= a.J) continue;
-        const int nv = a.J - j0 < 4 ? a.J - j0 : 4;
-        f32x4 v = *(const f32x4*)(a.xs32 + bf * a.Jp + j0);
-        const float* t0 = a.tail_in + (size_t)b * a.S * a.J;      // frame 0 of the previous window's tail
-        if (!a.is_first && a.root_shift && j0 == 0) {
-            const float* s0 = a.xs32 + (size_t)b * a.T * a.Jp;
-#pragma unroll
-            for (int e = 0; e < 3; ++e)
-                if (e < nv) { const float delta = s0[e] - t0[e]; v[e] = v[e] - delta; }
-        }
-        if (!a.is_first && f == 0) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) if (e < nv) v[e] = t0[j0 + e] * 0.5f + v[e] * 0.5f;
-        }
-        const int df = a.c * keep + f - a.S;
-        if ((f < keep || (a.is_last && a.keep_last_tail)) && df >= 0 && df < a.n_out)
-            handoff_store4(a.clip_out + ((size_t)b * a.n_out + df) * a.J + j0, v, nv);
-        if (f >= keep) {
-            const int sf = f - keep;
-            handoff_store4(a.tail_out + ((size_t)b * a.S + sf) * a.J + j0, v, nv);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) if (e < nv) a.c_seed[((size_t)b * a.J + j0 + e) * a.S + sf] = v[e];
-        }
+        const HandoffSlot s = a.slots[i / per];
+        if (s.flags & HQ_DEAD) continue;
+        handoff_row(a.xs32, a.tail_in, a.tail_out, a.c_seed, s.clip_out, i, a.J, a.Jp, a.T, a.S, s.n_out, s.c, a.root_shift,
+                    (s.flags & HQ_FIRST) ? 1 : 0, (s.flags & HQ_LAST) ? 1 : 0, a.keep_last_tail);
     }
 }
 // The constraint of one window cut out of a clip-level one (dsg_set_clip_inpainting): the inverse walk of k_window_handoff.  motion / mask
@@ -1798,6 +1835,7 @@ struct ClipXInArgs {
     float qa, qb;
     NoiseKey nkey; unsigned draw;
     const unsigned* keys;   // keyed noise: the key table (noise_key_of), else null
+    const unsigned* offs;   // keyed noise: per-element draw offsets, as XInArgs::offs
     int B, J, Jp, Jq, T, S, n_out, c;
     float* xs32; void* xsA;
     int dupB, xs_frag;
@@ -1822,7 +1860,7 @@ __global__ void k_clip_x_in(const ClipXInArgs a) {
             } else {
                 v = clip_inp_load4(a.init + ((size_t)b * a.n_out + (df < a.n_out ? df : a.n_out - 1)) * a.J + j0, nv);
             }
-            z = a.keys ? philox_normal4((unsigned)(((size_t)f * a.Jq + j0) >> 2), a.draw, noise_key_of(a.keys, b))
+            z = a.keys ? philox_normal4((unsigned)(((size_t)f * a.Jq + j0) >> 2), a.draw + (a.offs ? a.offs[b] : 0u), noise_key_of(a.keys, b))
                        : philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
 #pragma unroll
             for (int e = 0; e < 4; ++e) z[e] = e < nv ? q_sample1(a.qa, v[e], a.qb, z[e]) : 0.f;

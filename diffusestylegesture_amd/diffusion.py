@@ -545,6 +545,79 @@ class DSGDiffusion:
         self._last_model = inners[0]
         return outs
 
+    # ---- clips of different lengths over one batch of slots (dsg_sample_clip_queue) ------------------------------------------
+    def sample_clip_queue(self, lanes, clips, B, *, root_shift, keep_last_tail, ddim=False, eta=0.0, skip_timesteps=0, clip_denoised=False,
+                          guided=False, mask_local="ones"):
+        """N clips of their own lengths over `lanes` x `B` slots in ONE library call: a slot is refilled when its clip ends
+        (`lib.clip_queue_plan` is the schedule).  `lanes`: a DSGDenoiser (or the ClassifierFreeSampleModel around one) or a list of them.
+        `clips`: one dict per clip -- "feats": its K_i per-window features exactly as y['audio'] takes them, each [T_a, A_src] (or
+        [1, T_a, A_src]); "style" [style_dim_in]; "stream": its stream id, or a (seed, stream_id) pair (a bare id keeps the seed of
+        `manual_seed`); optional "seed0" [J, 1, S] = y['seed'] of window 0 (None: zeros), "seed_last" (DiffuseStyleGesture++), "scale"
+        (`guided=True`: y['scale'] of the clip, default 1).  Returns one [n_out_i, J] numpy array per clip, in the order given; clip i is bit
+        for bit `sample_clip` of that clip alone (batch 1) after `manual_seed(seed_i, stream_i)` under the same kernel set.  The draw counter
+        advances by max(K_i) * (1 + n_run), as the longest clip alone would advance it.  Per-clip inpainting / init motion: not through the
+        queue yet (the library refuses lanes that carry them)."""
+        lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
+        clips = list(clips)
+        if not lanes or not clips:
+            raise ValueError("sample_clip_queue: at least one lane and one clip")
+        inners = []
+        for m in lanes:
+            inner, _ = self._library_model(m, None)
+            if inner is None:
+                raise TypeError("sample_clip_queue drives library denoisers (DSGDenoiser lanes)")
+            inners.append(inner)
+        cfg = inners[0].cfg
+        S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
+        n_run = self.num_timesteps - skip_timesteps
+        use_torch = L.is_torch(clips[0]["feats"][0])
+        stream = L.current_stream_ptr() if use_torch else None
+        if isinstance(mask_local, str):
+            mask_local = np.ones((T,), np.uint8)
+        mbuf = L.Buf(mask_local, "uint8") if mask_local is not None else L.Buf(None)
+        if mbuf.obj is not None and int(np.prod(mbuf.obj.shape)) != T:
+            raise ValueError(f"sample_clip_queue: mask_local is one mask of {T} entries, shared by every slot")
+        jobs = (L.dsg_clip_job * len(clips))()
+        keep, outs = [mbuf], []
+        for job, clip in zip(jobs, clips):
+            feats = list(clip["feats"])
+            if not feats:
+                raise ValueError("sample_clip_queue: a clip without windows")
+            if use_torch:
+                import torch
+                audio = L.Buf(torch.stack([f.float().reshape(cfg.audio_frames, cfg.audio_src_dim) for f in feats]))
+            else:
+                audio = L.Buf(np.stack([np.asarray(f, np.float32).reshape(cfg.audio_frames, cfg.audio_src_dim) for f in feats]))
+            style = L.Buf(clip["style"])
+            if int(np.prod(style.obj.shape)) != cfg.style_dim_in:
+                raise ValueError(f"style shape {tuple(style.obj.shape)}")
+            seed0, last = L.Buf(clip.get("seed0")), L.Buf(clip.get("seed_last"))
+            for name, b in (("seed0", seed0), ("seed_last", last)):
+                if b.obj is not None and int(np.prod(b.obj.shape)) != J * S:
+                    raise ValueError(f"{name} shape {tuple(b.obj.shape)}")
+            st = clip.get("stream", 0)
+            sd, sid = (st if isinstance(st, (tuple, list)) else (self._seed, st))
+            K = len(feats)
+            out = np.empty((K * (T - S) - (0 if keep_last_tail else S), J), np.float32)
+            job.style, job.seed0, job.seed_last, job.audio, job.out = style.ptr, seed0.ptr, last.ptr, audio.ptr, out.ctypes.data
+            job.K, job.scale = K, float(1.0 if clip.get("scale") is None else clip["scale"])
+            job.seed, job.stream_id = int(sd) & _U64, int(sid) & _U64
+            keep += [audio, style, seed0, last]
+            outs.append(out)
+        for m in inners:
+            m.set_schedule(self)
+        a = L.dsg_sample_args()
+        a.mode, a.skip_timesteps, a.eta = (L.MODE_DDIM if ddim else L.MODE_DDPM), int(skip_timesteps), float(eta)
+        a.seed, a.stream_id, a.draw_base = int(self._seed) & _U64, 0, self._draw
+        a.clip_denoised = int(bool(clip_denoised))
+        hs = (C.c_void_p * len(inners))(*[m.handle for m in inners])
+        lib = inners[0].lib
+        lib.check(lib.cdll.dsg_sample_clip_queue(hs, len(inners), jobs, len(clips), int(B), mbuf.p, int(bool(guided)), C.byref(a),
+                                                 int(bool(root_shift)), int(bool(keep_last_tail)), stream))
+        self._draw += max(int(j.K) for j in jobs) * (1 + n_run)
+        self._last_model = inners[0]
+        return outs
+
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
                          randomize_class=False, cond_fn_with_grad=False, dump_steps=None, const_noise=False,

@@ -35,6 +35,13 @@ class dsg_sample_args(C.Structure):
         ("dump_steps", C.c_void_p), ("dump_out", C.c_void_p), ("clip_denoised", C.c_int32), ("first_step", C.c_int32), ("max_steps", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
+class dsg_clip_job(C.Structure):
+    """One clip of dsg_sample_clip_queue (include/dsg.h)."""
+    _fields_ = [
+        ("style", C.c_void_p), ("seed0", C.c_void_p), ("seed_last", C.c_void_p), ("audio", C.c_void_p), ("out", C.c_void_p),
+        ("K", C.c_int32), ("scale", C.c_float), ("seed", C.c_uint64), ("stream_id", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
 # every symbol include/dsg.h declares: name -> (restype, argtypes)
 _P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
 SYMBOLS = {
@@ -60,6 +67,8 @@ SYMBOLS = {
     "dsg_sample_clip": (_I, [_P, _P, _P, _P, _P, _I, _P, C.POINTER(dsg_sample_args), _I, _I, _I, _P, _I, _P]),
     "dsg_sample_clip_multi": (_I, [C.POINTER(_P), _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _I, C.POINTER(_P),
                                    C.POINTER(dsg_sample_args), _I, _I, _I, C.POINTER(_P), _I, _P]),
+    "dsg_clip_queue_plan": (_I, [_P, _I, _I, _P, _P, C.POINTER(C.c_int32)]),
+    "dsg_sample_clip_queue": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_clip_job), _I, _I, _P, _I, C.POINTER(dsg_sample_args), _I, _I, _P]),
     "dsg_set_kernel_set": (_I, [_P, _I]),
     "dsg_get_kernel_set": (_I, [_P, C.POINTER(_I)]),
     "dsg_recommend_kernel_set": (_I, [_P, _I, _I, C.POINTER(_I)]),
@@ -123,6 +132,16 @@ def trim(device: int = -1, library: "DSGLibrary | None" = None):
     rel, held = C.c_longlong(0), C.c_longlong(0)
     lib.check(lib.cdll.dsg_trim(device, C.byref(rel), C.byref(held)))
     return int(rel.value), int(held.value)
+
+
+def clip_queue_plan(K, n_slots: int, library: "DSGLibrary | None" = None):
+    """dsg_clip_queue_plan: the schedule dsg_sample_clip_queue follows for clips of K[j] windows over n_slots slots (host only).
+    Returns (slot[j], first_round[j], n_rounds)."""
+    lib = library or default_library()
+    k = np.ascontiguousarray(K, dtype=np.int32)
+    slot, first, n_rounds = np.zeros(len(k), np.int32), np.zeros(len(k), np.int32), C.c_int32(0)
+    lib.check(lib.cdll.dsg_clip_queue_plan(k.ctypes.data, len(k), int(n_slots), slot.ctypes.data, first.ctypes.data, C.byref(n_rounds)))
+    return slot.tolist(), first.tolist(), int(n_rounds.value)
 
 
 _default = None

@@ -542,6 +542,68 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
     return _dsgplus_finish(out, S, J, real_n_frames, feature_division, use_torch)
 
 
+def _queue_lanes(lanes, clips, B):
+    """(the lanes' DSGDenoisers, guided, B) of a clip-queue call: guidance is on when any clip carries a scale; B defaults to
+    min(max_batch, ceil(N / lanes)) -- max_batch halved with guidance, the twins ride in the same batch."""
+    from .model import ClassifierFreeSampleModel
+    lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
+    inners = [m.model if isinstance(m, ClassifierFreeSampleModel) else m for m in lanes]
+    guided = any(c.get("scale") is not None for c in clips)
+    if B is None:
+        room = min(m.max_batch for m in inners) // (2 if guided else 1)
+        B = max(1, min(room, -(-len(clips) // len(inners))))
+    return inners, guided, int(B)
+
+
+def _queue_stream(clip, i):
+    return int(clip.get("clip_id", i))
+
+
+def generate_clip_queue(lanes, diffusion, clips, seed=123456, smoothing=True, skip_timesteps=0, ddim=False, eta=0.0,
+                        kernel_set="recommended", *, B=None):
+    """ZEGGS clips of DIFFERENT lengths through `DSGDiffusion.sample_clip_queue`: the clips share the `lanes` x `B` slots and a slot takes
+    the next clip when its clip ends, so no round is spent on padding (`lib.clip_queue_plan`).  `lanes`: a DSGDenoiser or a list of lanes
+    (`model.clone()`).  `clips`: one dict per clip -- "feats": its K_i per-window WavLM features, each [T, A_src] or [1, T, A_src];
+    "style": one-hot list or [6] array; optional "seed_pose" [1, J, 1, S] (default zeros), "scale" (classifier-free guidance for the whole
+    call as soon as one clip has it; the others run at scale 1), "clip_id" (default: the clip's index).  All clips share `seed`; clip i draws
+    from the Philox stream (seed, clip_id) and is bit for bit `generate_clip(lane of batch 1, ..., windows="library", stream_id=clip_id)`
+    under the same kernel set.  `kernel_set` as in `generate_clips_streams`.  Returns a list of [K_i*stride - n_seed, J] arrays in the
+    order given."""
+    clips = list(clips)
+    inners, guided, B = _queue_lanes(lanes, clips, B)
+    jobs = [{"feats": c["feats"], "style": np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"],
+             "seed0": c.get("seed_pose"), "scale": c.get("scale"), "stream": _queue_stream(c, i)} for i, c in enumerate(clips)]
+    with _lane_kernel_sets(inners, B, kernel_set):
+        diffusion.manual_seed(seed, 0)
+        return diffusion.sample_clip_queue(inners, jobs, B, root_shift=smoothing, keep_last_tail=False, ddim=ddim, eta=eta,
+                                           skip_timesteps=skip_timesteps, guided=guided)
+
+
+def generate_clip_queue_dsgplus(lanes, diffusion, clips, seed=123456, skip_timesteps=0, feature_division=3, ddim=False, eta=0.0,
+                                kernel_set="recommended", *, B=None):
+    """`generate_clip_queue` for the DSG+ window loop (all three model names of that tree): every clip dict carries "feats" (K_i
+    stride-long windows, each [1, T, A_src]), "style", "seed_pose" [1, J, 1, S] (the ground-truth seed of window 0), "real_n_frames", and
+    for DiffuseStyleGesture++ "seed_last" [1, J, 1, S]; optional "scale", "clip_id".  The per-window features are built as
+    `_dsgplus_window_y` builds them; every clip is finished as `_dsgplus_finish` finishes it -- cropped to ITS real_n_frames, the first
+    J // feature_division features kept.  Clip i is bit for bit `generate_clip_dsgplus(lane of batch 1, ..., windows="library",
+    stream_id=clip_id)`.  Returns a list of [real_n_frames_i, J // feature_division] arrays in the order given."""
+    clips = list(clips)
+    inners, guided, B = _queue_lanes(lanes, clips, B)
+    cfg = inners[0].cfg
+    jobs = []
+    for i, c in enumerate(clips):
+        use_torch = L.is_torch(c["feats"][0])
+        feats = [f if f.ndim == 3 else f[None] for f in c["feats"]]
+        audio = [_dsgplus_window_y(cfg, feats, w, None, c["seed_pose"], c.get("seed_last"), use_torch, None)["audio"] for w in range(len(feats))]
+        jobs.append({"feats": audio, "style": np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"],
+                     "seed0": c["seed_pose"], "seed_last": c.get("seed_last"), "scale": c.get("scale"), "stream": _queue_stream(c, i)})
+    with _lane_kernel_sets(inners, B, kernel_set):
+        diffusion.manual_seed(seed, 0)
+        seqs = diffusion.sample_clip_queue(inners, jobs, B, root_shift=False, keep_last_tail=True, ddim=ddim, eta=eta,
+                                           skip_timesteps=skip_timesteps, guided=guided)
+    return [np.ascontiguousarray(q[: int(c["real_n_frames"]), : cfg.njoints // feature_division], dtype=np.float32) for q, c in zip(seqs, clips)]
+
+
 def window_audio(audio, n_frames, n_poses=88, n_seed=8, sr=16000, fps=20):
     """Audio slices per window with the n_seed-frame left context (sample.py:214-249): zeros for window 0, the
     previous chunk's tail otherwise.  Returns (list of float32 arrays of (n_poses * sr/fps) samples, n_frames)."""

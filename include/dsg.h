@@ -242,6 +242,49 @@ int dsg_sample_clip(dsg_handle* h, const float* style, const float* seed0, const
 int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* const* styles, const float* const* seed0s,
                           const float* const* audios, const uint8_t* mask_local, int mask_batch, const float* const* scales,
                           const dsg_sample_args* args, int K, int root_shift, int keep_last_tail, float** outs, int B, void* stream);
+/* Clip queue: clips of DIFFERENT lengths share one batch of slots.  dsg_sample_clip / _multi advance B clips in lock step, so every clip of
+ * a call has the same number of windows K; a corpus of recordings from seconds to minutes then either runs in groups padded to each group's
+ * longest clip or one clip at a time.  The queue gives every clip (a job) a slot of the n_lanes * B slots and refills a slot when its clip
+ * ends.  Every clip comes out bit for bit as dsg_sample_clip produces it alone -- B = 1, args->seed = job.seed, args->stream_id =
+ * job.stream_id, the same draw_base, conditioning, root_shift / keep_last_tail -- under the same named kernel set: its noise is keyed by its
+ * own Philox pair (as dsg_set_noise_streams keys a batch), a slot on window c of its clip draws draw_base + c * (1 + n_run) for x_T and the
+ * following n_run for the steps (a per-element draw offset read beside the element's key), and the hand-off (root shift, one-frame blend,
+ * stitching, next seed: k_window_handoff_q) knows each slot's clip.  Reference counterpart: none -- the reference samples one clip at a
+ * time (main/mydiffusion_zeggs/sample.py:418).
+ * A job: style [style_dim_in]; seed0 [J, 1, S] = y['seed'] of window 0 (NULL: zeros); seed_last [J, 1, S] (variant 5: required, else NULL);
+ * audio [K, T_a, A_src] = the clip's K per-window features as dsg_sample_clip takes them; out [n_out(K), J] with n_out(K) = K * (T - S) - S,
+ * or K * (T - S) with keep_last_tail; scale = y['scale'], read when guided != 0; (seed, stream_id) = the clip's Philox pair.  Every pointer
+ * host or device.  A device `out` is written by the hand-off itself; host ones go through one library-owned device buffer, one copy per job.
+ * The plan (dsg_clip_queue_plan: host only, no device, and exactly what the queue call follows): jobs are taken longest first (K descending,
+ * ties by lower index); each goes to the slot with the least load so far (ties: lowest slot); first_round[j] is that load, slot[j] the slot,
+ * *n_rounds the largest load.  Global slot s of n_slots = n_lanes * B is lane s % n_lanes, position s / n_lanes.  The call runs n_rounds
+ * rounds; a round is one window of dsg_sample_clip_multi for every lane at the constant batch B (with guided != 0: B conditional elements +
+ * their B twins).  A slot without a clip in a round -- finished, or never given one -- keeps running on the conditioning it holds and writes
+ * nothing; rows are independent, so nothing of it reaches a clip.  mask_local: uint8[T] shared by every slot, or NULL.  args: mode,
+ * skip_timesteps, eta, clip_denoised and draw_base are read (draw_base is every clip's); seed / stream_id are ignored.  Each lane runs the
+ * kernel set of ITS handle (DSG_KSET_AUTO: by B, as ever).  dsg_last_sample_ms afterwards: the sum over the rounds, n_steps = n_rounds * n_run.
+ * DSG_E_INVALID, each with the cause in dsg_last_error: n_jobs < 1; a job with K < 1, a null style / audio / out, or (variant 5) no
+ * seed_last; B < 1 or B (2 B with guided) > max_batch; n_lanes > 16; lanes of different models, devices or step counts; args with
+ * step_noise, init_noise, init_image, n_dump, first_step, max_steps or const_noise; a handle that carries sticky noise streams
+ * (dsg_set_noise_streams), a window-level or clip-level inpainting constraint, or a clip-level init motion -- per-clip inpainting and
+ * editing through the queue are not implemented yet.  DSG_E_STATE: before dsg_finalize_weights / dsg_set_schedule.
+ * On every return path, errors included, the lanes are left as they came: unkeyed, no draw offsets, one lane.  Variant 5: the call overwrites
+ * the lanes' y['seed_last'] rows, so a later dsg_set_window_cond needs dsg_set_seed_last again.
+ * Added without a version step, as the setters above: dsg_version() stays 330. */
+typedef struct dsg_clip_job {
+    const float* style;      /* [style_dim_in] */
+    const float* seed0;      /* [J,1,S] = y['seed'] of window 0; NULL = zeros */
+    const float* seed_last;  /* variant 5: [J,1,S]; NULL otherwise */
+    const float* audio;      /* [K, T_a, A_src], the K per-window features as dsg_sample_clip takes them */
+    float* out;              /* [n_out(K), J]; n_out(K) = K*(T-S)-S, or K*(T-S) with keep_last_tail */
+    int32_t K;               /* >= 1 */
+    float scale;             /* y['scale'], read when guided != 0 */
+    uint64_t seed, stream_id;/* the clip's Philox pair */
+    int32_t reserved[4];
+} dsg_clip_job;
+int dsg_clip_queue_plan(const int32_t* K, int n_jobs, int n_slots, int32_t* slot, int32_t* first_round, int32_t* n_rounds);
+int dsg_sample_clip_queue(dsg_handle** lanes, int n_lanes, const dsg_clip_job* jobs, int n_jobs, int B, const uint8_t* mask_local, int guided,
+                          const dsg_sample_args* args, int root_shift, int keep_last_tail, void* stream);
 /* Motion inpainting over a whole clip, for dsg_sample_clip / _multi: mask uint8 [B, n_frames, J] (non-zero = keep the given motion), motion
  * fp32 [B, n_frames, J]; host or device; frame-major, exactly the layout and frame numbering of dsg_sample_clip's `out`.  Sticky for the
  * handle, like dsg_set_inpainting.  The library keeps its own device copy (allocated on first use, grown when needed, freed with the
