@@ -195,6 +195,11 @@ struct dsg_handle {
     // copies of what is uploaded per round (they outlive the copies).  Allocated on first use
     float *q_style = nullptr, *q_audio = nullptr; HandoffSlot* q_slots = nullptr;
     std::vector<HandoffSlot> q_slots_host; std::vector<float> q_scale_host;
+    // dsg_sample_clip_queue_edit: the round's per-slot edit table (k_clipq_inp_window / k_clipq_x_in) with its host copy, and the staging of
+    // the call's host-side edit tensors (every job this lane runs, all at once; grown when needed, q_stage_cap bytes).  q_edit_init: for the
+    // rounds of a call in which a job of this lane has an init motion, sample_prepare starts the round through k_clipq_x_in
+    EditSlot* q_edits = nullptr; std::vector<EditSlot> q_edits_host; bool q_edit_init = false;
+    unsigned char* q_stage = nullptr; size_t q_stage_cap = 0;
     int latency_mode = -1;               // dsg_config.latency_mode: -1 auto, 0 never the LATENCY set, 1 always
 #ifndef DSG_EMU
     dsg_aql::Ctx aql;                    // hand-written AQL submission of the step loop (dsg_aql.h)
@@ -2112,18 +2117,37 @@ static int launch_x_in(dsg_handle* h, const float* x, const float* init, int do_
     return 0;
 }
 // window h->clip_init_c of a clip that starts from the handle's clip-level init motion (dsg_sample_clip): cut + q_sample + state write
-static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B,
-                            const KernelSel& ks) {
+static ClipXInArgs clip_x_in_args(dsg_handle* h, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B,
+                                  const KernelSel& ks) {
     ClipXInArgs a;
     a.keys = keys; a.offs = offs;
     a.init = h->cinit_motion; a.c_seed = h->c_seed; a.qa = qa; a.qb = qb; a.nkey = nk; a.draw = draw;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.S = h->S; a.n_out = h->clip_init_n_out; a.c = h->clip_init_c;
     a.xs32 = h->xs32; a.xsA = is_bf16(h) ? h->xsA : nullptr;
     a.dupB = h->cfgB; a.xs_frag = ks.xs_frag ? 1 : 0;
+    return a;
+}
+static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B,
+                            const KernelSel& ks) {
+    const ClipXInArgs a = clip_x_in_args(h, qa, qb, nk, keys, offs, draw, B, ks);
     const size_t n = (size_t)B * h->T * (h->Jp / 4);
     const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
     if (is_bf16(h)) hipLaunchKernelGGL((k_clip_x_in<PBF16>), dim3(grid), dim3(256), 0, h->stream, a);
     else hipLaunchKernelGGL((k_clip_x_in<PF32>), dim3(grid), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// a round of dsg_sample_clip_queue_edit on a lane that runs a job with an init motion: init, length and window index per slot (h->q_edits)
+static int launch_clip_x_in_q(dsg_handle* h, int do_q, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw,
+                              int B, const KernelSel& ks) {
+    ClipXInQArgs a;
+    a.x = clip_x_in_args(h, qa, qb, nk, keys, offs, draw, B, ks);
+    a.x.init = nullptr; a.x.n_out = 0; a.x.c = 0;      // (per slot, from the table)
+    a.slots = h->q_edits; a.do_q = do_q;
+    const size_t n = (size_t)B * h->T * (h->Jp / 4);
+    const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
+    if (is_bf16(h)) hipLaunchKernelGGL((k_clipq_x_in<PBF16>), dim3(grid), dim3(256), 0, h->stream, a);
+    else hipLaunchKernelGGL((k_clipq_x_in<PF32>), dim3(grid), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2504,7 +2528,9 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     }
     const unsigned* keys_d = keyed ? h->dyn + 8 : nullptr;
     const unsigned* offs_d = keyed ? h->dyn + 8 + 4 * (size_t)h->Bmax : nullptr;
-    if (h->clip_init_c >= 0)      // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
+    if (h->q_edit_init)           // (a round of dsg_sample_clip_queue_edit on a lane that runs a job with an init motion)
+        CHK(launch_clip_x_in_q(h, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
+    else if (h->clip_init_c >= 0) // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
         CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
     else
         CHK(launch_x_in(h, noise_d, init_d, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0],
@@ -2905,6 +2931,15 @@ extern "C" int dsg_clip_queue_plan(const int32_t* K, int n_jobs, int n_slots, in
     return 0;
 }
 
+static int launch_clip_inp_window_q(dsg_handle* h, int B) {
+    ClipInpQArgs a;
+    a.slots = h->q_edits; a.inp32 = h->inp32; a.inp_mask = h->inp_mask;
+    a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S;
+    const size_t n = (size_t)B * h->T * (h->Jp / 4);
+    hipLaunchKernelGGL(k_clipq_inp_window, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 static int launch_handoff_q(dsg_handle* h, int B, int round, int root_shift, int keep_last_tail) {
     HandoffQArgs a;
     a.xs32 = h->xs32; a.tail_in = h->clip_tail[(round + 1) & 1]; a.tail_out = h->clip_tail[round & 1]; a.c_seed = h->c_seed; a.slots = h->q_slots;
@@ -2916,8 +2951,13 @@ static int launch_handoff_q(dsg_handle* h, int B, int round, int root_shift, int
     return 0;
 }
 
-extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job* jobs, int n_jobs, int B, const uint8_t* mask_local, int guided,
-                                     const dsg_sample_args* args, int root_shift, int keep_last_tail, void* stream) {
+// edits: NULL (dsg_sample_clip_queue), or one dsg_clip_edit per job -- the clip's constraint and / or the clip it is re-denoised from, in the
+// coordinates of the job's `out`.  Host tensors are staged on the lane that runs the job before the rounds start; per round the lane's edit
+// table (EditSlot) goes up beside the hand-off's, k_clipq_inp_window cuts the round's constraint for every slot (lanes that run a constrained
+// job: inpB = B for the rounds of this call) and sample_prepare starts the round through k_clipq_x_in (lanes that run a job with an init)
+extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip_job* jobs, const dsg_clip_edit* edits, int n_jobs, int B,
+                                          const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift, int keep_last_tail,
+                                          void* stream) {
     if (!hs || !jobs || !args || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: bad argument");
     if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
     if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: n_jobs < 1");
@@ -2938,8 +2978,8 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
         if (rows > h->Bmax) return fail(DSG_E_INVALID, guided ? "dsg_sample_clip_queue: classifier-free guidance needs max_batch >= 2 * B" : "dsg_sample_clip_queue: B exceeds max_batch");
         if (h->nkB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries noise streams (dsg_set_noise_streams(h, NULL, NULL, 0) first): every job brings its own pair");
         if (h->inpB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries a window-level inpainting constraint (dsg_set_inpainting(h, NULL, NULL, ...) first)");
-        if (h->cinpB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries a clip-level inpainting constraint (dsg_set_clip_inpainting(h, NULL, NULL, ...) first): per-clip inpainting through the queue is not implemented");
-        if (h->cinitB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries a clip-level init motion (dsg_set_clip_init(h, NULL, ...) first): per-clip editing through the queue is not implemented");
+        if (h->cinpB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries a clip-level inpainting constraint (dsg_set_clip_inpainting(h, NULL, NULL, ...) first): a queue takes per-clip inpainting per job (dsg_sample_clip_queue_edit)");
+        if (h->cinitB > 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: the handle carries a clip-level init motion (dsg_set_clip_init(h, NULL, ...) first): a queue takes per-clip init motion per job (dsg_sample_clip_queue_edit)");
     }
     if (args->step_noise || args->init_noise || args->init_image || args->n_dump || args->first_step || args->max_steps || args->const_noise)
         return fail(DSG_E_INVALID, "dsg_sample_clip_queue: step_noise / init_noise / init_image / dump_steps / first_step / max_steps / const_noise are not for a queue of clips");
@@ -2951,6 +2991,8 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
         if (q.K < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has K < 1");
         if (!q.style || !q.audio || !q.out) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has a null style / audio / out");
         if (variant5 && !q.seed_last) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: variant 5 needs seed_last for every job (job " + std::to_string(j) + " has none)");
+        if (edits && !edits[j].inp_mask != !edits[j].inp_motion)
+            return fail(DSG_E_INVALID, "dsg_sample_clip_queue_edit: inp_mask and inp_motion go together (both NULL: no constraint); job " + std::to_string(j) + " has one of them");
     }
     const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J, Ta = hs[0]->Ta, As = hs[0]->As, sdi = hs[0]->cfg.style_dim_in;
     const int n_slots = n * B, keep = T - S;
@@ -2992,8 +3034,64 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
         h->draw_offs.assign(B, 0u);
         CHK(order_after(h, stream));
     }
-    // What the call sets on a lane for its rounds -- the keyed table and its draw offsets, lanes_now, (variant 5) the batch of seed_last -- is
-    // put back on every return path.  Every lane came in unkeyed (checked above).  Variant 5: the rows of c_seed_last now hold the jobs' snippets,
+    // the edits: where each job's tensors are read on the device -- the caller's where they are device memory, else a piece of the staging of
+    // the lane that runs the job (slot[j] % n), uploaded here on that lane's stream (the first round's sample_prepare drains it)
+    const size_t r16 = 15;
+    std::vector<EditSlot> ed(n_jobs, EditSlot{nullptr, nullptr, nullptr, 0, 0});
+    std::vector<char> lane_inp(n, 0), lane_init(n, 0);
+    if (edits) {
+        std::vector<size_t> need(n, 0);
+        for (int j = 0; j < n_jobs; ++j) {
+            const dsg_clip_edit& e = edits[j];
+            const int i = slot[j] % n;
+            if (e.inp_mask) lane_inp[i] = 1;
+            if (e.init_motion) lane_init[i] = 1;
+            if (e.inp_motion && !is_device_ptr(e.inp_motion)) need[i] += (n_clip[j] * sizeof(float) + r16) & ~r16;
+            if (e.inp_mask && !is_device_ptr(e.inp_mask)) need[i] += (n_clip[j] + r16) & ~r16;
+            if (e.init_motion && !is_device_ptr(e.init_motion)) need[i] += (n_clip[j] * sizeof(float) + r16) & ~r16;
+        }
+        for (int i = 0; i < n; ++i) {
+            dsg_handle* h = hs[i];
+            if (!lane_inp[i] && !lane_init[i]) continue;
+            if (!h->q_edits) CHK(dalloc(h, &h->q_edits, (size_t)h->Bmax));
+            if (lane_inp[i]) {      // (each pointer on its own, as dsg_set_inpainting)
+                if (!h->inp32) CHK(dalloc(h, &h->inp32, (size_t)h->Bmax * T * h->Jp));
+                if (!h->inp_mask) CHK(dalloc(h, &h->inp_mask, (size_t)h->Bmax * T * h->Jp));
+            }
+            if (need[i] > h->q_stage_cap) {
+                // grown: the old staging goes back at once (nothing on the handle's stream may still read it)
+                HIPCHK(hipStreamSynchronize(h->stream));
+                if (h->q_stage) {
+                    void* old = h->q_stage;
+                    h->q_stage = nullptr; h->q_stage_cap = 0;
+                    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), old), h->allocs.end());
+                    (void)hipFree(old);
+                }
+                CHK(dalloc(h, &h->q_stage, need[i], false));
+                h->q_stage_cap = need[i];
+            }
+        }
+        std::vector<size_t> at(n, 0);
+        for (int j = 0; j < n_jobs; ++j) {
+            const dsg_clip_edit& e = edits[j];
+            dsg_handle* h = hs[slot[j] % n];
+            size_t& p = at[slot[j] % n];
+            auto staged = [&](const void* src, size_t bytes, const void** dst) -> int {
+                if (!src || is_device_ptr(src)) { *dst = src; return 0; }
+                CHK(upload(h, h->q_stage + p, src, bytes));
+                *dst = h->q_stage + p;
+                p += (bytes + r16) & ~r16;
+                return 0;
+            };
+            CHK(staged(e.inp_motion, n_clip[j] * sizeof(float), (const void**)&ed[j].motion));
+            CHK(staged(e.init_motion, n_clip[j] * sizeof(float), (const void**)&ed[j].init));
+            CHK(staged(e.inp_mask, n_clip[j], (const void**)&ed[j].mask));
+            ed[j].n_out = (int)(n_clip[j] / J);
+        }
+    }
+    // What the call sets on a lane for its rounds -- the keyed table and its draw offsets, lanes_now, (variant 5) the batch of seed_last, with
+    // edits the epilogue's inpainting (inpB) and the start through the edit table (q_edit_init) -- is put back on every return path.  Every
+    // lane came in unkeyed and with inpB == 0 (checked above).  Variant 5: the rows of c_seed_last now hold the jobs' snippets,
     // so the lane asks for dsg_set_seed_last again, as a fresh handle does
     struct QueueNow {
         dsg_handle** hs; int n; bool seed_last_written = false;
@@ -3002,6 +3100,7 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
             for (int i = 0; i < n; ++i) {
                 dsg_handle* h = hs[i];
                 h->lanes_now = 1; h->nkB = 0; h->nk_seeds = false; h->nkeys.clear(); h->draw_offs_on = false;
+                h->inpB = 0; h->q_edit_init = false;
                 if (seed_last_written) h->seed_last_B = 0;
             }
         }
@@ -3013,6 +3112,7 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
         for (int i = 0; i < n; ++i) {
             dsg_handle* h = hs[i];
             h->nkeys.assign(4 * (size_t)B, 0u);
+            h->q_edits_host.assign(B, EditSlot{nullptr, nullptr, nullptr, 0, 0});      // (a dead slot: a slot without edits)
             for (int b = 0; b < B; ++b) {
                 const int j = sched[(size_t)r * n_slots + (size_t)b * n + i];      // global slot s: lane s % n, position s / n
                 HandoffSlot& hq = h->q_slots_host[b];
@@ -3035,6 +3135,7 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
                 h->nkeys[4 * b + 2] = (unsigned)(q.stream_id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(q.stream_id >> 32);
                 h->draw_offs[b] = (uint32_t)c * (uint32_t)(1 + n_run);      // what dsg_sample_clip alone consumes before window c
                 hq = HandoffSlot{clip[j], (int)(n_clip[j] / J), c, (c == 0 ? HQ_FIRST : 0) | (c == Ks[j] - 1 ? HQ_LAST : 0), 0};
+                h->q_edits_host[b] = ed[j]; h->q_edits_host[b].c = c;
             }
             h->nkB = B; h->nk_seeds = true; h->draw_offs_on = true;
             if (variant5) h->seed_last_B = B;
@@ -3042,6 +3143,10 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
             // sample_prepare drains the stream -- so the host copy is free to change in the next round
             HIPCHK(hipMemcpyAsync(h->q_slots, h->q_slots_host.data(), (size_t)B * sizeof(HandoffSlot), hipMemcpyHostToDevice, h->stream));
             CHK(set_window_cond(h, h->q_style, h->c_seed, h->q_audio, mask_local, 1, B, 0, guided ? h->q_scale_host.data() : nullptr, stream));
+            if (lane_inp[i] || lane_init[i])      // the round's edit table: where the hand-off table goes up, for the same reason
+                HIPCHK(hipMemcpyAsync(h->q_edits, h->q_edits_host.data(), (size_t)B * sizeof(EditSlot), hipMemcpyHostToDevice, h->stream));
+            if (lane_inp[i]) { CHK(launch_clip_inp_window_q(h, B)); h->inpB = B; }
+            h->q_edit_init = lane_init[i] != 0;
         }
         for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, sjobs[i]));
         CHK(run_lanes(hs, n, wargs.data(), sjobs.data()));
@@ -3067,6 +3172,11 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
         CHK(order_before(h, stream));
     }
     return 0;
+}
+
+extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job* jobs, int n_jobs, int B, const uint8_t* mask_local, int guided,
+                                     const dsg_sample_args* args, int root_shift, int keep_last_tail, void* stream) {
+    return dsg_sample_clip_queue_edit(hs, n, jobs, nullptr, n_jobs, B, mask_local, guided, args, root_shift, keep_last_tail, stream);
 }
 
 extern "C" int dsg_sync(dsg_handle* h) {

@@ -1801,25 +1801,55 @@ __device__ __forceinline__ f32x4 clip_inp_load4(const float* src, int n) {      
     for (int e = 0; e < 4; ++e) if (e < n) v[e] = src[e];
     return v;
 }
-__global__ void k_clip_inp_window(const ClipInpArgs a) {
-    const int nq = a.Jp / 4, keep = a.T - a.S;
-    const size_t n = (size_t)a.B * a.T * nq;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int j0 = (int)(i % nq) * 4;
-        const size_t bf = i / nq;
-        const int f = (int)(bf % a.T), b = (int)(bf / a.T);
-        const int df = a.c * keep + f - a.S;
-        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-        unsigned mk = 0;
-        if (df >= 0 && df < a.n_out && j0 < a.J) {
-            const int nv = a.J - j0 < 4 ? a.J - j0 : 4;
-            const size_t src = ((size_t)b * a.n_out + df) * a.J + j0;
-            v = clip_inp_load4(a.motion + src, nv);
+// One feature quad of a (slot, frame) row of the cut: spelled ONCE for k_clip_inp_window and k_clipq_inp_window, which promise the same bits
+// (as handoff_row for the two hand-offs).  i = ((b * T + f) * Jp / 4 + quad); motion / mask = the [n_out][J] constraint of THIS slot, or null:
+// the slot is unconstrained, every frame 0 / unmasked
+__device__ __forceinline__ void clip_inp_row(const float* motion, const unsigned char* mask, float* inp32, unsigned char* inp_mask, size_t i, int J,
+                                             int Jp, int T, int S, int n_out, int c) {
+    const int nq = Jp / 4, keep = T - S;
+    const int j0 = (int)(i % nq) * 4;
+    const size_t bf = i / nq;
+    const int f = (int)(bf % T);
+    const int df = c * keep + f - S;
+    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+    unsigned mk = 0;
+    if (motion && df >= 0 && df < n_out && j0 < J) {
+        const int nv = J - j0 < 4 ? J - j0 : 4;
+        const size_t src = (size_t)df * J + j0;
+        v = clip_inp_load4(motion + src, nv);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) if (e < nv) mk |= (a.mask[src + e] ? 1u : 0u) << (8 * e);
-        }
-        *(f32x4*)(a.inp32 + bf * a.Jp + j0) = v;
-        *(unsigned*)(a.inp_mask + bf * a.Jp + j0) = mk;
+        for (int e = 0; e < 4; ++e) if (e < nv) mk |= (mask[src + e] ? 1u : 0u) << (8 * e);
+    }
+    *(f32x4*)(inp32 + bf * Jp + j0) = v;
+    *(unsigned*)(inp_mask + bf * Jp + j0) = mk;
+}
+__global__ void k_clip_inp_window(const ClipInpArgs a) {
+    const size_t per = (size_t)a.T * (a.Jp / 4), n = (size_t)a.B * per;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t at = (i / per) * (size_t)a.n_out * a.J;
+        clip_inp_row(a.motion + at, a.mask + at, a.inp32, a.inp_mask, i, a.J, a.Jp, a.T, a.S, a.n_out, a.c);
+    }
+}
+// The edits of dsg_sample_clip_queue_edit: every slot of the batch carries its own clip, so what k_clip_inp_window and k_clip_x_in take as
+// arguments -- the constraint and the init motion of the clip, its length, the window index -- comes per slot from a table in device memory
+// (uploaded once per round on the handle's stream, beside the hand-off's HandoffSlot table).  A slot whose clip has no constraint has motion ==
+// mask == null, one without an init motion init == null; a dead slot (no clip this round) has all three null.
+struct EditSlot {
+    const float* motion; const unsigned char* mask;      // [n_out][J] each: the constraint of the slot's clip, or both null
+    const float* init;                                   // [n_out][J]: the clip it is re-denoised from, or null
+    int n_out, c;                                        // the clip's length and the window the slot stands on
+};
+// k_clip_inp_window over the slots of a queue round: inp32 / inp_mask [B][T][Jp] as the pose-head epilogue reads them; a slot without a
+// constraint is written 0 / unmasked, so the epilogue's per-byte select keeps its x0 bits
+struct ClipInpQArgs {
+    const EditSlot* slots; float* inp32; unsigned char* inp_mask;
+    int B, J, Jp, T, S;
+};
+__global__ void k_clipq_inp_window(const ClipInpQArgs a) {
+    const size_t per = (size_t)a.T * (a.Jp / 4), n = (size_t)a.B * per;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const EditSlot s = a.slots[i / per];
+        clip_inp_row(s.motion, s.mask, a.inp32, a.inp_mask, i, a.J, a.Jp, a.T, a.S, s.n_out, s.c);
     }
 }
 // The start of one window of a clip that is re-denoised from an existing clip (dsg_set_clip_init; init_image + skip_timesteps of
@@ -1840,37 +1870,62 @@ struct ClipXInArgs {
     float* xs32; void* xsA;
     int dupB, xs_frag;
 };
+// One feature quad of a (slot, frame) row of the start: spelled ONCE for k_clip_x_in and k_clipq_x_in, which promise the same bits.
+// i = ((b * T + f) * Jp / 4 + quad); init = the [n_out][J] clip of THIS slot.  init == null (k_clipq_x_in only: a slot without an init
+// motion) starts as k_x_in starts it: do_q ? q_sample1(qa, 0, qb, z) : z
 template <class P>
-__global__ void k_clip_x_in(const ClipXInArgs a) {
+__device__ __forceinline__ void clip_x_in_row(const ClipXInArgs& a, const float* init, int n_out, int c, int do_q, size_t i) {
     typedef typename P::elem elem;
     const int nq = a.Jp / 4, keep = a.T - a.S;
-    const size_t n = (size_t)a.B * a.T * nq;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int j0 = (int)(i % nq) * 4;
-        const size_t bf = i / nq;
-        const int f = (int)(bf % a.T), b = (int)(bf / a.T);
-        f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (j0 < a.J) {
-            const int nv = a.J - j0 < 4 ? a.J - j0 : 4;
-            const int df = a.c * keep + f - a.S;
-            f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (df < 0) {                                   // (window 0 only, and there f < S)
+    const int j0 = (int)(i % nq) * 4;
+    const size_t bf = i / nq;
+    const int f = (int)(bf % a.T), b = (int)(bf / a.T);
+    f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (j0 < a.J) {
+        const int nv = a.J - j0 < 4 ? a.J - j0 : 4;
+        const int df = c * keep + f - a.S;
+        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (init && df < 0) {                           // (window 0 only, and there f < S)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nv) v[e] = a.c_seed[((size_t)b * a.J + j0 + e) * a.S + f];
-            } else {
-                v = clip_inp_load4(a.init + ((size_t)b * a.n_out + (df < a.n_out ? df : a.n_out - 1)) * a.J + j0, nv);
-            }
-            z = a.keys ? philox_normal4((unsigned)(((size_t)f * a.Jq + j0) >> 2), a.draw + (a.offs ? a.offs[b] : 0u), noise_key_of(a.keys, b))
-                       : philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
+            for (int e = 0; e < 4; ++e) if (e < nv) v[e] = a.c_seed[((size_t)b * a.J + j0 + e) * a.S + f];
+        } else if (init) {
+            v = clip_inp_load4(init + (size_t)(df < n_out ? df : n_out - 1) * a.J + j0, nv);
+        }
+        z = a.keys ? philox_normal4((unsigned)(((size_t)f * a.Jq + j0) >> 2), a.draw + (a.offs ? a.offs[b] : 0u), noise_key_of(a.keys, b))
+                   : philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
+        if (init || do_q) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) z[e] = e < nv ? q_sample1(a.qa, v[e], a.qb, z[e]) : 0.f;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (e >= nv) z[e] = 0.f;
         }
-        *(f32x4*)(a.xs32 + ((size_t)b * a.T + f) * a.Jp + j0) = z;
-        if (a.xsA) P::store4((elem*)a.xsA + xs_off<P>(b * a.T + f, j0, a.Jp, a.xs_frag), z);
-        if (a.dupB > 0) {
-            *(f32x4*)(a.xs32 + ((size_t)(b + a.dupB) * a.T + f) * a.Jp + j0) = z;
-            if (a.xsA) P::store4((elem*)a.xsA + xs_off<P>((b + a.dupB) * a.T + f, j0, a.Jp, a.xs_frag), z);
-        }
+    }
+    *(f32x4*)(a.xs32 + ((size_t)b * a.T + f) * a.Jp + j0) = z;
+    if (a.xsA) P::store4((elem*)a.xsA + xs_off<P>(b * a.T + f, j0, a.Jp, a.xs_frag), z);
+    if (a.dupB > 0) {
+        *(f32x4*)(a.xs32 + ((size_t)(b + a.dupB) * a.T + f) * a.Jp + j0) = z;
+        if (a.xsA) P::store4((elem*)a.xsA + xs_off<P>((b + a.dupB) * a.T + f, j0, a.Jp, a.xs_frag), z);
+    }
+}
+template <class P>
+__global__ void k_clip_x_in(const ClipXInArgs a) {
+    const size_t per = (size_t)a.T * (a.Jp / 4), n = (size_t)a.B * per;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        clip_x_in_row<P>(a, a.init + (i / per) * (size_t)a.n_out * a.J, a.n_out, a.c, 1, i);
+}
+// k_clip_x_in over the slots of a queue round (dsg_sample_clip_queue_edit, in place of k_x_in for the rounds of a call in which some clip has
+// an init motion): init, length and window index per slot from the EditSlot table; `x` carries everything else (its init / n_out / c are not
+// read).  do_q = the call runs with skip_timesteps > 0: what k_x_in does for a slot without an init motion
+struct ClipXInQArgs {
+    ClipXInArgs x; const EditSlot* slots; int do_q;
+};
+template <class P>
+__global__ void k_clipq_x_in(const ClipXInQArgs a) {
+    const size_t per = (size_t)a.x.T * (a.x.Jp / 4), n = (size_t)a.x.B * per;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const EditSlot s = a.slots[i / per];
+        clip_x_in_row<P>(a.x, s.init, s.n_out, s.c, a.do_q, i);
     }
 }
 // Self-check of the fence-free hand-off (dsg_hip.cpp: uc_selfcheck): `buf` is uncached device memory; the two kernels run as

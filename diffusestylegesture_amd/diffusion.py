@@ -555,8 +555,12 @@ class DSGDiffusion:
         `manual_seed`); optional "seed0" [J, 1, S] = y['seed'] of window 0 (None: zeros), "seed_last" (DiffuseStyleGesture++), "scale"
         (`guided=True`: y['scale'] of the clip, default 1).  Returns one [n_out_i, J] numpy array per clip, in the order given; clip i is bit
         for bit `sample_clip` of that clip alone (batch 1) after `manual_seed(seed_i, stream_i)` under the same kernel set.  The draw counter
-        advances by max(K_i) * (1 + n_run), as the longest clip alone would advance it.  Per-clip inpainting / init motion: not through the
-        queue yet (the library refuses lanes that carry them)."""
+        advances by max(K_i) * (1 + n_run), as the longest clip alone would advance it.
+        Per-clip edits, three more optional keys (numpy or torch, host or device): "inpainting_mask" / "inpainted_motion" (both or
+        neither) and "init_motion", each [n_out_i, J] or [1, n_out_i, J] in the coordinates of the clip returned -- what `sample_clip`
+        takes as `inpainting_mask` / `inpainted_motion` / `init_motion` for that clip alone, and clip i is bit for bit that call.  They
+        travel with the clip (dsg_sample_clip_queue_edit, called only when some clip has one); a clip without them beside clips with
+        some comes out as it does without."""
         lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
         clips = list(clips)
         if not lanes or not clips:
@@ -571,15 +575,18 @@ class DSGDiffusion:
         S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
         n_run = self.num_timesteps - skip_timesteps
         use_torch = L.is_torch(clips[0]["feats"][0])
-        stream = L.current_stream_ptr() if use_torch else None
+        edit_keys = ("inpainting_mask", "inpainted_motion", "init_motion")
+        stream = L.current_stream_ptr() if use_torch or any(L.is_torch(c.get(k)) for c in clips for k in edit_keys) else None
         if isinstance(mask_local, str):
             mask_local = np.ones((T,), np.uint8)
         mbuf = L.Buf(mask_local, "uint8") if mask_local is not None else L.Buf(None)
         if mbuf.obj is not None and int(np.prod(mbuf.obj.shape)) != T:
             raise ValueError(f"sample_clip_queue: mask_local is one mask of {T} entries, shared by every slot")
         jobs = (L.dsg_clip_job * len(clips))()
+        from .model import _mask_bytes
+        edits, edited = (L.dsg_clip_edit * len(clips))(), False
         keep, outs = [mbuf], []
-        for job, clip in zip(jobs, clips):
+        for i, (job, edit, clip) in enumerate(zip(jobs, edits, clips)):
             feats = list(clip["feats"])
             if not feats:
                 raise ValueError("sample_clip_queue: a clip without windows")
@@ -604,6 +611,16 @@ class DSGDiffusion:
             job.seed, job.stream_id = int(sd) & _U64, int(sid) & _U64
             keep += [audio, style, seed0, last]
             outs.append(out)
+            mk, mo, init = (clip.get(k) for k in edit_keys)
+            if (mk is None) != (mo is None):
+                raise ValueError(f"sample_clip_queue: clip {i}: inpainting_mask and inpainted_motion go together")
+            bufs = [L.Buf(None if mk is None else _mask_bytes(mk), "uint8"), L.Buf(mo), L.Buf(init)]
+            for name, b in zip(edit_keys, bufs):
+                if b.obj is not None and tuple(b.obj.shape) not in (out.shape, (1,) + out.shape):
+                    raise ValueError(f"sample_clip_queue: clip {i}: {name} shape {tuple(b.obj.shape)} != {out.shape}")
+            edit.inp_mask, edit.inp_motion, edit.init_motion = (b.ptr for b in bufs)
+            edited = edited or any(b.obj is not None for b in bufs)
+            keep += bufs
         for m in inners:
             m.set_schedule(self)
         a = L.dsg_sample_args()
@@ -612,8 +629,11 @@ class DSGDiffusion:
         a.clip_denoised = int(bool(clip_denoised))
         hs = (C.c_void_p * len(inners))(*[m.handle for m in inners])
         lib = inners[0].lib
-        lib.check(lib.cdll.dsg_sample_clip_queue(hs, len(inners), jobs, len(clips), int(B), mbuf.p, int(bool(guided)), C.byref(a),
-                                                 int(bool(root_shift)), int(bool(keep_last_tail)), stream))
+        tail = (int(B), mbuf.p, int(bool(guided)), C.byref(a), int(bool(root_shift)), int(bool(keep_last_tail)), stream)
+        if edited:
+            lib.check(lib.cdll.dsg_sample_clip_queue_edit(hs, len(inners), jobs, edits, len(clips), *tail))
+        else:
+            lib.check(lib.cdll.dsg_sample_clip_queue(hs, len(inners), jobs, len(clips), *tail))
         self._draw += max(int(j.K) for j in jobs) * (1 + n_run)
         self._last_model = inners[0]
         return outs

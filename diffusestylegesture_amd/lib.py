@@ -42,6 +42,11 @@ class dsg_clip_job(C.Structure):
         ("K", C.c_int32), ("scale", C.c_float), ("seed", C.c_uint64), ("stream_id", C.c_uint64), ("reserved", C.c_int32 * 4)]
 
 
+class dsg_clip_edit(C.Structure):
+    """The edits of one clip of dsg_sample_clip_queue_edit (include/dsg.h): parallel to the jobs, every pointer nullable."""
+    _fields_ = [("inp_mask", C.c_void_p), ("inp_motion", C.c_void_p), ("init_motion", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
 # every symbol include/dsg.h declares: name -> (restype, argtypes)
 _P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
 SYMBOLS = {
@@ -69,6 +74,8 @@ SYMBOLS = {
                                    C.POINTER(dsg_sample_args), _I, _I, _I, C.POINTER(_P), _I, _P]),
     "dsg_clip_queue_plan": (_I, [_P, _I, _I, _P, _P, C.POINTER(C.c_int32)]),
     "dsg_sample_clip_queue": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_clip_job), _I, _I, _P, _I, C.POINTER(dsg_sample_args), _I, _I, _P]),
+    "dsg_sample_clip_queue_edit": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_clip_job), C.POINTER(dsg_clip_edit), _I, _I, _P, _I,
+                                        C.POINTER(dsg_sample_args), _I, _I, _P]),
     "dsg_set_kernel_set": (_I, [_P, _I]),
     "dsg_get_kernel_set": (_I, [_P, C.POINTER(_I)]),
     "dsg_recommend_kernel_set": (_I, [_P, _I, _I, C.POINTER(_I)]),

@@ -559,20 +559,27 @@ def _queue_stream(clip, i):
     return int(clip.get("clip_id", i))
 
 
+def _queue_edits(clip):
+    """the per-clip edits of a clip-queue dict, passed through as `DSGDiffusion.sample_clip_queue` takes them"""
+    return {k: clip[k] for k in ("inpainting_mask", "inpainted_motion", "init_motion") if clip.get(k) is not None}
+
+
 def generate_clip_queue(lanes, diffusion, clips, seed=123456, smoothing=True, skip_timesteps=0, ddim=False, eta=0.0,
                         kernel_set="recommended", *, B=None):
     """ZEGGS clips of DIFFERENT lengths through `DSGDiffusion.sample_clip_queue`: the clips share the `lanes` x `B` slots and a slot takes
     the next clip when its clip ends, so no round is spent on padding (`lib.clip_queue_plan`).  `lanes`: a DSGDenoiser or a list of lanes
     (`model.clone()`).  `clips`: one dict per clip -- "feats": its K_i per-window WavLM features, each [T, A_src] or [1, T, A_src];
     "style": one-hot list or [6] array; optional "seed_pose" [1, J, 1, S] (default zeros), "scale" (classifier-free guidance for the whole
-    call as soon as one clip has it; the others run at scale 1), "clip_id" (default: the clip's index).  All clips share `seed`; clip i draws
+    call as soon as one clip has it; the others run at scale 1), "clip_id" (default: the clip's index), and the clip's own edits
+    "inpainting_mask" / "inpainted_motion" / "init_motion", each [K_i*stride - n_seed, J] (or [1, ...]) as `generate_clip` takes them for
+    that clip.  All clips share `seed`; clip i draws
     from the Philox stream (seed, clip_id) and is bit for bit `generate_clip(lane of batch 1, ..., windows="library", stream_id=clip_id)`
-    under the same kernel set.  `kernel_set` as in `generate_clips_streams`.  Returns a list of [K_i*stride - n_seed, J] arrays in the
+    with the clip's edits under the same kernel set.  `kernel_set` as in `generate_clips_streams`.  Returns a list of [K_i*stride - n_seed, J] arrays in the
     order given."""
     clips = list(clips)
     inners, guided, B = _queue_lanes(lanes, clips, B)
     jobs = [{"feats": c["feats"], "style": np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"],
-             "seed0": c.get("seed_pose"), "scale": c.get("scale"), "stream": _queue_stream(c, i)} for i, c in enumerate(clips)]
+             "seed0": c.get("seed_pose"), "scale": c.get("scale"), "stream": _queue_stream(c, i), **_queue_edits(c)} for i, c in enumerate(clips)]
     with _lane_kernel_sets(inners, B, kernel_set):
         diffusion.manual_seed(seed, 0)
         return diffusion.sample_clip_queue(inners, jobs, B, root_shift=smoothing, keep_last_tail=False, ddim=ddim, eta=eta,
@@ -583,7 +590,9 @@ def generate_clip_queue_dsgplus(lanes, diffusion, clips, seed=123456, skip_times
                                 kernel_set="recommended", *, B=None):
     """`generate_clip_queue` for the DSG+ window loop (all three model names of that tree): every clip dict carries "feats" (K_i
     stride-long windows, each [1, T, A_src]), "style", "seed_pose" [1, J, 1, S] (the ground-truth seed of window 0), "real_n_frames", and
-    for DiffuseStyleGesture++ "seed_last" [1, J, 1, S]; optional "scale", "clip_id".  The per-window features are built as
+    for DiffuseStyleGesture++ "seed_last" [1, J, 1, S]; optional "scale", "clip_id", and the clip's own edits "inpainting_mask" /
+    "inpainted_motion" / "init_motion" in the [K_i*stride, J] coordinates `generate_clip_dsgplus` documents (all J features, before the
+    crop and the feature division).  The per-window features are built as
     `_dsgplus_window_y` builds them; every clip is finished as `_dsgplus_finish` finishes it -- cropped to ITS real_n_frames, the first
     J // feature_division features kept.  Clip i is bit for bit `generate_clip_dsgplus(lane of batch 1, ..., windows="library",
     stream_id=clip_id)`.  Returns a list of [real_n_frames_i, J // feature_division] arrays in the order given."""
@@ -596,7 +605,8 @@ def generate_clip_queue_dsgplus(lanes, diffusion, clips, seed=123456, skip_times
         feats = [f if f.ndim == 3 else f[None] for f in c["feats"]]
         audio = [_dsgplus_window_y(cfg, feats, w, None, c["seed_pose"], c.get("seed_last"), use_torch, None)["audio"] for w in range(len(feats))]
         jobs.append({"feats": audio, "style": np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"],
-                     "seed0": c["seed_pose"], "seed_last": c.get("seed_last"), "scale": c.get("scale"), "stream": _queue_stream(c, i)})
+                     "seed0": c["seed_pose"], "seed_last": c.get("seed_last"), "scale": c.get("scale"), "stream": _queue_stream(c, i),
+                     **_queue_edits(c)})
     with _lane_kernel_sets(inners, B, kernel_set):
         diffusion.manual_seed(seed, 0)
         seqs = diffusion.sample_clip_queue(inners, jobs, B, root_shift=False, keep_last_tail=True, ddim=ddim, eta=eta,

@@ -266,8 +266,9 @@ int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* const* styles,
  * DSG_E_INVALID, each with the cause in dsg_last_error: n_jobs < 1; a job with K < 1, a null style / audio / out, or (variant 5) no
  * seed_last; B < 1 or B (2 B with guided) > max_batch; n_lanes > 16; lanes of different models, devices or step counts; args with
  * step_noise, init_noise, init_image, n_dump, first_step, max_steps or const_noise; a handle that carries sticky noise streams
- * (dsg_set_noise_streams), a window-level or clip-level inpainting constraint, or a clip-level init motion -- per-clip inpainting and
- * editing through the queue are not implemented yet.  DSG_E_STATE: before dsg_finalize_weights / dsg_set_schedule.
+ * (dsg_set_noise_streams), a window-level or clip-level inpainting constraint, or a clip-level init motion -- the handle-level setters are
+ * [B, n_frames, J] for one n_frames; in a queue the constraint and the init motion travel with the job (dsg_sample_clip_queue_edit below).
+ * DSG_E_STATE: before dsg_finalize_weights / dsg_set_schedule.
  * On every return path, errors included, the lanes are left as they came: unkeyed, no draw offsets, one lane.  Variant 5: the call overwrites
  * the lanes' y['seed_last'] rows, so a later dsg_set_window_cond needs dsg_set_seed_last again.
  * Added without a version step, as the setters above: dsg_version() stays 330. */
@@ -331,6 +332,40 @@ int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const float* mot
  * sequence does: windows c > 0 start from the given root trajectory and the hand-off then moves them by the window's delta.
  * Added without a version step, as the two inpainting setters: dsg_version() stays 330. */
 int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int n_frames, void* stream);
+/* Clip queue with per-clip edits: dsg_sample_clip_queue where every job may bring its own inpainting constraint and / or the clip it is
+ * re-denoised from.  edits: NULL, or one dsg_clip_edit per job, parallel to jobs[]; dsg_sample_clip_queue(...) IS this call with edits ==
+ * NULL (same bits, same launches).  The three tensors of an edit are [n_out(K), J] in the layout and frame numbering of the job's `out`
+ * -- exactly what dsg_set_clip_inpainting / dsg_set_clip_init take for one batch element -- each host or device memory, each nullable.
+ * Job j comes out bit for bit as dsg_sample_clip produces it alone: B = 1, the job's (seed, stream_id), the same draw_base, conditioning,
+ * root_shift / keep_last_tail and named kernel set, after dsg_set_clip_inpainting(h, inp_mask, inp_motion, 1, n_out) and / or
+ * dsg_set_clip_init(h, init_motion, 1, n_out).  A job without edits beside jobs with some comes out as it does alone without edits: the
+ * pose-head epilogue selects per mask byte, so a slot whose mask is all zero keeps its x0 bits.
+ * Semantics per slot: those written above for the two setters, with the slot's own clip -- df = c * (T - S) + f - S; the constraint leaves
+ * frames outside [0, n_out) free; the init takes window 0's y['seed'] of that slot for df < 0 and holds clip row n_out - 1 for df >= n_out;
+ * root_shift is applied after either, in the window's own frame; guidance twins get the same start, the constraint acts after the
+ * combination; skip_timesteps == 0 with an init is allowed (the last timestep).  In a call where some job has an init motion, a slot without
+ * one starts exactly as it does in dsg_sample_clip_queue: q_sample of a zero init with skip_timesteps > 0, the draw itself with
+ * skip_timesteps == 0.  A dead slot is a slot without edits.
+ * On the device: per round one table of {constraint, init, n_out, c} per slot goes up beside the hand-off's; k_clipq_inp_window cuts every
+ * slot's constraint into the buffers of dsg_set_inpainting (lanes that run a constrained job only; without any, no cut kernel runs), and
+ * k_clipq_x_in starts the round in place of the plain start kernel (lanes that run a job with an init motion only).
+ * Staging: device tensors are read where they are and must stay valid until `stream` has passed the call.  Host tensors are uploaded before
+ * the first round, each on the stream of the lane that runs the job (slot[j] % n_lanes), into library-owned device memory of that lane
+ * (grown when needed, freed with the handle) that holds ALL host-side edits of the call's jobs on that lane at once: 9 * n_out * J bytes for
+ * a job with both edits (+ up to 15 bytes of padding per tensor).
+ * DSG_E_INVALID, with the cause and the job number in dsg_last_error: exactly one of inp_mask / inp_motion is NULL; and everything
+ * dsg_sample_clip_queue refuses, handles that carry the sticky dsg_set_clip_inpainting / dsg_set_clip_init included.  On every return
+ * path, errors included, the lanes are left as they came: no inpainting (dsg_set_inpainting's batch 0), no edit table, unkeyed, one lane.
+ * dsg_clip_job keeps its layout; its `reserved` stays unread.  Added without a version step: dsg_version() stays 330. */
+typedef struct dsg_clip_edit {      /* one per job, parallel to jobs[]; all three nullable */
+    const uint8_t* inp_mask;        /* [n_out(K), J]  non-zero = keep inp_motion there           */
+    const float*   inp_motion;      /* [n_out(K), J]                                             */
+    const float*   init_motion;     /* [n_out(K), J]  the clip to re-denoise from                */
+    int32_t reserved[2];
+} dsg_clip_edit;
+int dsg_sample_clip_queue_edit(dsg_handle** lanes, int n_lanes, const dsg_clip_job* jobs, const dsg_clip_edit* edits /* NULL or [n_jobs] */,
+                               int n_jobs, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args,
+                               int root_shift, int keep_last_tail, void* stream);
 /* Per-element noise streams ("keyed noise") for dsg_sample / _multi / dsg_sample_clip / _multi.  seeds, stream_ids: HOST uint64[B], copied by
  * the call.  While set, element b of the batch draws from its own pair (seed_b, sid_b): draw d at frame f, feature j is
  *   philox4x32_10(ctr = ((f * Jq + j) >> 2, d, sid_b lo, sid_b hi), key = (seed_b lo, seed_b hi)) + Box-Muller,   Jq = J rounded up to 4,
