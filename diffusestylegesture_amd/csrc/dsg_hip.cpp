@@ -16,8 +16,10 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 using namespace dsg;
@@ -189,8 +191,11 @@ struct dsg_handle {
     // (8 + 5 * max_batch words: + the draw offsets) every sampling call uploads
     int nkB = 0; bool nk_seeds = false; std::vector<unsigned> nkeys, dyn_host;
     // per-element draw offsets of keyed noise (GemmArgs::draw_off; words 8 + 4 max_batch .. of `dyn`): dsg_sample_clip_queue sets them per round
-    // (draw_offs_on, for the rounds of that call only); every other keyed call uploads zeros
-    bool draw_offs_on = false; std::vector<unsigned> draw_offs;
+    // (draw_offs_on, for the rounds of that call only); every other keyed call uploads zeros.  On the device they are pairs {offset, hold}
+    // (DrawOff) for the pose head, and behind them (words 8 + 6 max_batch ..) the offsets of the start kernels once more: with per-clip
+    // skip_timesteps (dsg_sample_clip_queue_steps) a slot that starts `hold` loop indices into the round draws its steps at offset - hold
+    // (draw_offs) and its start at the offset itself (draw_starts); everywhere else hold is 0 and the two agree
+    bool draw_offs_on = false; std::vector<unsigned> draw_offs, draw_starts; std::vector<int> draw_holds;
     // dsg_sample_clip_queue: the round's per-slot style / audio gathered on the device, the hand-off table (k_window_handoff_q) and the host
     // copies of what is uploaded per round (they outlive the copies).  Allocated on first use
     float *q_style = nullptr, *q_audio = nullptr; HandoffSlot* q_slots = nullptr;
@@ -627,8 +632,8 @@ extern "C" int dsg_create(const dsg_config* c, dsg_handle** out) {
     CHK(dalloc(h, &h->mask, (size_t)B * h->T));
     CHK(dalloc(h, &h->ctr, 8));
     CHK(dalloc(h, &h->cfg_scale, (size_t)B));
-    CHK(dalloc(h, &h->dyn, 8 + 5 * (size_t)B));      // + the key table of keyed noise (GemmArgs::dyn) + its draw offsets (GemmArgs::draw_off)
-    h->dyn_host.assign(8 + 5 * (size_t)B, 0u);
+    CHK(dalloc(h, &h->dyn, 8 + 7 * (size_t)B));      // + the key table of keyed noise (GemmArgs::dyn) + its draw offsets and holds (GemmArgs::draw_off) + the start offsets
+    h->dyn_host.assign(8 + 7 * (size_t)B, 0u);
     CHK(dalloc(h, &h->t_arr, (size_t)B));
     // the xs32 master is read as a GEMM operand in fp32 mode: rows padded to a 16-row tile exist (allocated above)
     return 0;
@@ -2138,12 +2143,11 @@ static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, cons
     return 0;
 }
 // a round of dsg_sample_clip_queue_edit on a lane that runs a job with an init motion: init, length and window index per slot (h->q_edits)
-static int launch_clip_x_in_q(dsg_handle* h, int do_q, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw,
-                              int B, const KernelSel& ks) {
+static int launch_clip_x_in_q(dsg_handle* h, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B, const KernelSel& ks) {
     ClipXInQArgs a;
-    a.x = clip_x_in_args(h, qa, qb, nk, keys, offs, draw, B, ks);
-    a.x.init = nullptr; a.x.n_out = 0; a.x.c = 0;      // (per slot, from the table)
-    a.slots = h->q_edits; a.do_q = do_q;
+    a.x = clip_x_in_args(h, 0.f, 0.f, nk, keys, offs, draw, B, ks);
+    a.x.init = nullptr; a.x.n_out = 0; a.x.c = 0;      // (per slot, from the table, as do_q and the q_sample pair)
+    a.slots = h->q_edits;
     const size_t n = (size_t)B * h->T * (h->Jp / 4);
     const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
     if (is_bf16(h)) hipLaunchKernelGGL((k_clipq_x_in<PBF16>), dim3(grid), dim3(256), 0, h->stream, a);
@@ -2522,14 +2526,18 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
         }
         // the draw offsets behind the table: the queue's (dsg_sample_clip_queue, per round), zeros in every other keyed call -- written with
         // every keyed upload, so that nothing of a queue call can outlive it on the device
-        const size_t off0 = 8 + 4 * (size_t)h->Bmax;
-        for (int b = 0; b < h->nkB; ++b) dyn[off0 + b] = h->draw_offs_on ? h->draw_offs[b] : 0u;
-        HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? off0 + (size_t)h->nkB : 5) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+        const size_t off0 = 8 + 4 * (size_t)h->Bmax, start0 = 8 + 6 * (size_t)h->Bmax;
+        for (int b = 0; b < h->nkB; ++b) {
+            dyn[off0 + 2 * b] = h->draw_offs_on ? h->draw_offs[b] : 0u;
+            dyn[off0 + 2 * b + 1] = h->draw_offs_on ? (unsigned)h->draw_holds[b] : 0u;
+            dyn[start0 + b] = h->draw_offs_on ? h->draw_starts[b] : 0u;
+        }
+        HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? start0 + (size_t)h->nkB : 5) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
     }
     const unsigned* keys_d = keyed ? h->dyn + 8 : nullptr;
-    const unsigned* offs_d = keyed ? h->dyn + 8 + 4 * (size_t)h->Bmax : nullptr;
-    if (h->q_edit_init)           // (a round of dsg_sample_clip_queue_edit on a lane that runs a job with an init motion)
-        CHK(launch_clip_x_in_q(h, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
+    const unsigned* offs_d = keyed ? h->dyn + 8 + 6 * (size_t)h->Bmax : nullptr;      // (the start kernels': GemmArgs::draw_off is the pair table)
+    if (h->q_edit_init)           // (a round of the clip queue on a lane that runs a job with an init motion, or of a call with per-clip skips)
+        CHK(launch_clip_x_in_q(h, nk, keys_d, offs_d, a->draw_base, B, ksel));
     else if (h->clip_init_c >= 0) // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
         CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
     else
@@ -2908,26 +2916,61 @@ extern "C" int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* con
 // and the per-slot hand-off (k_window_handoff_q).  A slot without a clip in a round is dead: it runs on whatever conditioning it holds --
 // rows are independent -- and writes nothing.
 // ---------------------------------------------------------------------------------------------------------
-extern "C" int dsg_clip_queue_plan(const int32_t* K, int n_jobs, int n_slots, int32_t* slot, int32_t* first_round, int32_t* n_rounds) {
-    if (!K || !slot || !first_round || !n_rounds) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: null argument");
-    if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: n_jobs < 1");
-    if (n_slots < 1) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: n_slots < 1");
-    for (int j = 0; j < n_jobs; ++j)
-        if (K[j] < 1) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: job " + std::to_string(j) + " has K < 1");
+// The placement, written once for both exports: jobs in the order n_run descending (where given), K descending, index ascending; each to the
+// slot with the fewest rounds so far, ties to the lowest slot.  `who`: the export's name, for the messages
+static int clip_queue_place(const char* who, const int32_t* K, const int32_t* n_run, int n_jobs, int n_slots, int32_t* slot, int32_t* first_round,
+                            int32_t* n_rounds) {
+    const std::string w(who);
+    if (!K || !slot || !first_round || !n_rounds) return fail(DSG_E_INVALID, w + ": null argument");
+    if (n_jobs < 1) return fail(DSG_E_INVALID, w + ": n_jobs < 1");
+    if (n_slots < 1) return fail(DSG_E_INVALID, w + ": n_slots < 1");
+    for (int j = 0; j < n_jobs; ++j) {
+        if (K[j] < 1) return fail(DSG_E_INVALID, w + ": job " + std::to_string(j) + " has K < 1");
+        if (n_run && n_run[j] < 1) return fail(DSG_E_INVALID, w + ": job " + std::to_string(j) + " has n_run < 1");
+    }
     std::vector<int> order(n_jobs);
     for (int j = 0; j < n_jobs; ++j) order[j] = j;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return K[a] > K[b]; });      // longest first, ties by lower index
+    // deepest first, then longest, ties by lower index
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return n_run && n_run[a] != n_run[b] ? n_run[a] > n_run[b] : K[a] > K[b]; });
     std::vector<int64_t> load(n_slots, 0);
     int64_t most = 0;
     for (int j : order) {
         int best = 0;
-        for (int s = 1; s < n_slots; ++s) if (load[s] < load[best]) best = s;      // least load so far, ties: lowest slot
-        if (load[best] + K[j] > 0x7fffffff) return fail(DSG_E_INVALID, "dsg_clip_queue_plan: more than 2^31 - 1 rounds");
+        for (int s = 1; s < n_slots; ++s) if (load[s] < load[best]) best = s;      // fewest rounds so far, ties: lowest slot
+        if (load[best] + K[j] > 0x7fffffff) return fail(DSG_E_INVALID, w + ": more than 2^31 - 1 rounds");
         slot[j] = best; first_round[j] = (int32_t)load[best];
         load[best] += K[j];
         most = std::max(most, load[best]);
     }
     *n_rounds = (int32_t)most;
+    return 0;
+}
+extern "C" int dsg_clip_queue_plan(const int32_t* K, int n_jobs, int n_slots, int32_t* slot, int32_t* first_round, int32_t* n_rounds) {
+    return clip_queue_place("dsg_clip_queue_plan", K, nullptr, n_jobs, n_slots, slot, first_round, n_rounds);
+}
+// The plan with a step count per job (dsg_sample_clip_queue_steps: n_run[j] = schedule length - the job's skip_timesteps): the deep jobs go
+// first, so the closing rounds hold only light ones and run short.  A round is as long as the deepest job alive in it.  n_run == NULL (all
+// equal): the order and outputs of dsg_clip_queue_plan
+extern "C" int dsg_clip_queue_plan_steps(const int32_t* K, const int32_t* n_run, int n_jobs, int n_slots, int32_t* slot, int32_t* first_round,
+                                         int32_t* n_rounds, int64_t* total_steps) {
+    CHK(clip_queue_place("dsg_clip_queue_plan_steps", K, n_run, n_jobs, n_slots, slot, first_round, n_rounds));
+    if (total_steps) {
+        if (!n_run) *total_steps = *n_rounds;
+        else {
+            // the deepest job alive per round: a job covers rounds [first, first + K) -- swept by the rounds at which jobs begin and end
+            std::vector<std::pair<int64_t, int>> ev;      // (round, +-n_run): an end sorts in front of a begin of the same round
+            ev.reserve(2 * (size_t)n_jobs);
+            for (int j = 0; j < n_jobs; ++j) { ev.emplace_back(first_round[j], n_run[j]); ev.emplace_back((int64_t)first_round[j] + K[j], -n_run[j]); }
+            std::sort(ev.begin(), ev.end());
+            std::multiset<int> alive;
+            int64_t total = 0, at = 0;
+            for (const auto& e : ev) {
+                if (e.first > at) { if (!alive.empty()) total += (e.first - at) * (int64_t)*alive.rbegin(); at = e.first; }
+                if (e.second > 0) alive.insert(e.second); else alive.erase(alive.find(-e.second));
+            }
+            *total_steps = total;
+        }
+    }
     return 0;
 }
 
@@ -2954,10 +2997,14 @@ static int launch_handoff_q(dsg_handle* h, int B, int round, int root_shift, int
 // edits: NULL (dsg_sample_clip_queue), or one dsg_clip_edit per job -- the clip's constraint and / or the clip it is re-denoised from, in the
 // coordinates of the job's `out`.  Host tensors are staged on the lane that runs the job before the rounds start; per round the lane's edit
 // table (EditSlot) goes up beside the hand-off's, k_clipq_inp_window cuts the round's constraint for every slot (lanes that run a constrained
-// job: inpB = B for the rounds of this call) and sample_prepare starts the round through k_clipq_x_in (lanes that run a job with an init)
-extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip_job* jobs, const dsg_clip_edit* edits, int n_jobs, int B,
-                                          const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift, int keep_last_tail,
-                                          void* stream) {
+// job: inpB = B for the rounds of this call) and sample_prepare starts the round through k_clipq_x_in (lanes that run a job with an init).
+// skip_timesteps: NULL (dsg_sample_clip_queue_edit), or one entry per job (< 0: args->skip_timesteps).  When an entry differs from the
+// call's, the rounds follow dsg_clip_queue_plan_steps; round r runs from s_r = the smallest skip alive in it, over all lanes, as dsg_sample
+// does with skip_timesteps = s_r; a slot with a larger skip holds for skip - s_r loop indices (DrawOff::hold) and every lane starts every
+// round through k_clipq_x_in, which reads do_q and the q_sample pair of the slot's own first timestep from the edit table
+extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_clip_job* jobs, const dsg_clip_edit* edits, const int32_t* skip_timesteps,
+                                           int n_jobs, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift,
+                                           int keep_last_tail, void* stream) {
     if (!hs || !jobs || !args || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: bad argument");
     if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
     if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: n_jobs < 1");
@@ -2984,7 +3031,6 @@ extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip
     if (args->step_noise || args->init_noise || args->init_image || args->n_dump || args->first_step || args->max_steps || args->const_noise)
         return fail(DSG_E_INVALID, "dsg_sample_clip_queue: step_noise / init_noise / init_image / dump_steps / first_step / max_steps / const_noise are not for a queue of clips");
     if (args->mode != DSG_MODE_DDPM && args->mode != DSG_MODE_DDIM) return fail(DSG_E_INVALID, "mode");
-    if (args->skip_timesteps < 0 || args->skip_timesteps >= hs[0]->sched.n) return fail(DSG_E_INVALID, "skip_timesteps out of range");
     const int variant5 = hs[0]->cfg.variant == 5;
     for (int j = 0; j < n_jobs; ++j) {
         const dsg_clip_job& q = jobs[j];
@@ -2996,11 +3042,20 @@ extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip
     }
     const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J, Ta = hs[0]->Ta, As = hs[0]->As, sdi = hs[0]->cfg.style_dim_in;
     const int n_slots = n * B, keep = T - S;
-    const int n_run = hs[0]->sched.n - args->skip_timesteps;
-    std::vector<int32_t> Ks(n_jobs), slot(n_jobs), first(n_jobs);
-    for (int j = 0; j < n_jobs; ++j) Ks[j] = jobs[j].K;
+    const int n_sched = hs[0]->sched.n;
+    std::vector<int32_t> Ks(n_jobs), slot(n_jobs), first(n_jobs), skips(n_jobs, args->skip_timesteps), n_runs(n_jobs);
+    bool own_skips = false;      // some job's skip differs from the call's: otherwise this IS dsg_sample_clip_queue_edit, launch for launch
+    for (int j = 0; j < n_jobs; ++j) {
+        Ks[j] = jobs[j].K;
+        if (skip_timesteps && skip_timesteps[j] >= 0) skips[j] = skip_timesteps[j];
+        if (skips[j] < 0 || skips[j] >= n_sched)
+            return fail(DSG_E_INVALID, "dsg_sample_clip_queue: skip_timesteps out of range: job " + std::to_string(j) + " has skip_timesteps " + std::to_string(skips[j]) +
+                                       " outside [0, " + std::to_string(n_sched - 1) + "]");
+        own_skips = own_skips || skips[j] != args->skip_timesteps;
+        n_runs[j] = n_sched - skips[j];
+    }
     int32_t n_rounds = 0;
-    CHK(dsg_clip_queue_plan(Ks.data(), n_jobs, n_slots, slot.data(), first.data(), &n_rounds));
+    CHK(dsg_clip_queue_plan_steps(Ks.data(), own_skips ? n_runs.data() : nullptr, n_jobs, n_slots, slot.data(), first.data(), &n_rounds, nullptr));
     std::vector<int> sched((size_t)n_rounds * n_slots, -1);      // [round][slot] -> job, -1: dead
     for (int j = 0; j < n_jobs; ++j)
         for (int c = 0; c < Ks[j]; ++c) sched[(size_t)(first[j] + c) * n_slots + slot[j]] = j;
@@ -3031,14 +3086,22 @@ extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip
         if (!h->q_slots) CHK(dalloc(h, &h->q_slots, (size_t)h->Bmax));
         h->q_slots_host.assign(B, HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0});
         h->q_scale_host.assign(B, 1.f);
-        h->draw_offs.assign(B, 0u);
+        h->draw_offs.assign(B, 0u); h->draw_starts.assign(B, 0u); h->draw_holds.assign(B, 0);
         CHK(order_after(h, stream));
     }
     // the edits: where each job's tensors are read on the device -- the caller's where they are device memory, else a piece of the staging of
     // the lane that runs the job (slot[j] % n), uploaded here on that lane's stream (the first round's sample_prepare drains it)
     const size_t r16 = 15;
-    std::vector<EditSlot> ed(n_jobs, EditSlot{nullptr, nullptr, nullptr, 0, 0});
-    std::vector<char> lane_inp(n, 0), lane_init(n, 0);
+    std::vector<EditSlot> ed(n_jobs, EditSlot{nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0, 0});
+    // the start of a slot's chain -- do_q and the q_sample pair -- is filled in per round, from the schedule of the lane that runs the slot:
+    // what k_x_in / k_clip_x_in get on that lane for the slot's skip_timesteps
+    auto chain_start = [](const dsg_handle* h, int skip, EditSlot& e) {
+        const int i0 = h->sched.n - skip - 1;
+        e.qa = (float)h->sched.sqrt_ac[i0]; e.qb = (float)h->sched.sqrt_1mac[i0]; e.do_q = skip > 0 ? 1 : 0;
+    };
+    std::vector<char> lane_inp(n, 0), lane_init(n, own_skips ? 1 : 0);      // (per-clip skips: every lane starts every round through the table)
+    if (own_skips)
+        for (int i = 0; i < n; ++i) if (!hs[i]->q_edits) CHK(dalloc(hs[i], &hs[i]->q_edits, (size_t)hs[i]->Bmax));
     if (edits) {
         std::vector<size_t> need(n, 0);
         for (int j = 0; j < n_jobs; ++j) {
@@ -3108,15 +3171,25 @@ extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip
     std::vector<SampleJob> sjobs(n);
     std::vector<dsg_sample_args> wargs(n, *args);      // (draw_base is args->draw_base for every clip: the windows are told apart by the offsets)
     const size_t n_tail = (size_t)J * S;
+    int64_t steps_run = 0;
     for (int r = 0; r < n_rounds; ++r) {
+        // the round's first timestep: the smallest skip alive in it, over all lanes (some slot is alive in every round of the plan)
+        int s_r = n_sched;
+        for (int s = 0; s < n_slots; ++s) { const int j = sched[(size_t)r * n_slots + s]; if (j >= 0) s_r = std::min(s_r, (int)skips[j]); }
+        const int n_run = n_sched - s_r;
+        steps_run += n_run;
         for (int i = 0; i < n; ++i) {
             dsg_handle* h = hs[i];
+            wargs[i].skip_timesteps = s_r;
             h->nkeys.assign(4 * (size_t)B, 0u);
-            h->q_edits_host.assign(B, EditSlot{nullptr, nullptr, nullptr, 0, 0});      // (a dead slot: a slot without edits)
+            // a dead slot: a slot without edits and with hold 0 -- it starts as k_x_in starts it for the round's skip
+            EditSlot ed_dead = {nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0, 0};
+            chain_start(h, s_r, ed_dead);
+            h->q_edits_host.assign(B, ed_dead);
             for (int b = 0; b < B; ++b) {
                 const int j = sched[(size_t)r * n_slots + (size_t)b * n + i];      // global slot s: lane s % n, position s / n
                 HandoffSlot& hq = h->q_slots_host[b];
-                h->draw_offs[b] = 0u;
+                h->draw_offs[b] = 0u; h->draw_starts[b] = 0u; h->draw_holds[b] = 0;
                 if (j < 0) { hq = HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0}; continue; }
                 const dsg_clip_job& q = jobs[j];
                 const int c = r - first[j];
@@ -3133,9 +3206,13 @@ extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip
                 }
                 h->nkeys[4 * b] = (unsigned)(q.seed & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(q.seed >> 32);
                 h->nkeys[4 * b + 2] = (unsigned)(q.stream_id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(q.stream_id >> 32);
-                h->draw_offs[b] = (uint32_t)c * (uint32_t)(1 + n_run);      // what dsg_sample_clip alone consumes before window c
+                // what dsg_sample_clip alone consumes before window c; its step i is the round's loop index i + hold
+                h->draw_holds[b] = skips[j] - s_r;
+                h->draw_starts[b] = (uint32_t)c * (uint32_t)(1 + n_runs[j]);
+                h->draw_offs[b] = h->draw_starts[b] - (uint32_t)h->draw_holds[b];
                 hq = HandoffSlot{clip[j], (int)(n_clip[j] / J), c, (c == 0 ? HQ_FIRST : 0) | (c == Ks[j] - 1 ? HQ_LAST : 0), 0};
                 h->q_edits_host[b] = ed[j]; h->q_edits_host[b].c = c;
+                chain_start(h, skips[j], h->q_edits_host[b]);
             }
             h->nkB = B; h->nk_seeds = true; h->draw_offs_on = true;
             if (variant5) h->seed_last_B = B;
@@ -3167,13 +3244,18 @@ extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip
         if (clip[j] != jobs[j].out) CHK(from_dev(hs[slot[j] % n], jobs[j].out, clip[j], n_clip[j]));      // (on the stream of the lane that wrote it)
     for (int i = 0; i < n; ++i) {
         dsg_handle* h = hs[i];
-        h->last_steps = n_rounds * n_run; h->timing_valid = true; h->clip_timing = true;
+        h->last_steps = (int)steps_run; h->timing_valid = true; h->clip_timing = true;
         h->last_kset = sjobs[i].c.ks.set;
         CHK(order_before(h, stream));
     }
     return 0;
 }
 
+extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip_job* jobs, const dsg_clip_edit* edits, int n_jobs, int B,
+                                          const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift, int keep_last_tail,
+                                          void* stream) {
+    return dsg_sample_clip_queue_steps(hs, n, jobs, edits, nullptr, n_jobs, B, mask_local, guided, args, root_shift, keep_last_tail, stream);
+}
 extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job* jobs, int n_jobs, int B, const uint8_t* mask_local, int guided,
                                      const dsg_sample_args* args, int root_shift, int keep_last_tail, void* stream) {
     return dsg_sample_clip_queue_edit(hs, n, jobs, nullptr, n_jobs, B, mask_local, guided, args, root_shift, keep_last_tail, stream);

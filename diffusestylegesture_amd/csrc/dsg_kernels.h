@@ -555,8 +555,10 @@ struct GemmArgs {
     int B;
     int const_noise;
     int keyed;              // EPI_OUT: per-element noise streams (dsg_set_noise_streams): the key of element b from dyn + 8, batch term of the counter 0
-    const unsigned* draw_off;   // keyed: uint32 [B] behind the key table (dyn + 8 + 4 max_batch: it does not move with the batch), element b's draw index is
-                            // dyn[4] + step + draw_off[b] (wraps) -- 0 everywhere but in dsg_sample_clip_queue, whose slots stand on different windows
+    const unsigned* draw_off;   // keyed: uint32 pairs {offset, hold} [B] behind the key table (dyn + 8 + 4 max_batch: 8-byte aligned, it does not move with the
+                            // batch).  Element b's draw index is dyn[4] + step + offset[b] (wraps), and for loop indices step < hold[b] the epilogue leaves the
+                            // element alone: no draw, no write of its state, shadow or twin.  {0, 0} everywhere but in the clip queue, whose slots stand
+                            // on different windows (dsg_sample_clip_queue) and may start later on the round's timestep axis (dsg_sample_clip_queue_steps)
     int ws_G;               // dsg_stream.h: row-block groups of the persistent grid (multiple of 8)
     int a_frag;             // PRO_DIRECT: A is stored fragment-major ([row tile][k-block][64 lanes][16 B], qk_off) -- hidden, attention rows
     int out_frag;           // EPI_GELU: the output goes out fragment-major (it is the next GEMM's A operand)
@@ -747,6 +749,8 @@ __device__ __forceinline__ void ln_rows(const GemmArgs& g, int m0, int tid, char
 // Epilogue operands of one 16 x 16 output tile (bias, residual rows, x_t, noise): requested early, they do not depend on
 // the main loop
 struct TileOps { f32x4 pb, pr, pz; float pbs; bool ovalid; };
+// one entry of GemmArgs::draw_off: read as ONE 8-byte word, workgroup-uniform
+struct __attribute__((aligned(8))) DrawOff { unsigned off; int hold; };
 // x_t of (row m, features j0 .. j0 + 3) for the sampler epilogue: unconditional load from a clamped (always valid) row
 template <class P>
 __device__ __forceinline__ f32x4 out_xt_load(const GemmArgs& g, int m, int j0) {
@@ -775,7 +779,7 @@ __device__ __forceinline__ void gemm_prefetch_tile(const GemmArgs& g, int m0, in
             o.pb = *(const f32x4*)(g.bias + j0);
             // x_t: unconditional load from a clamped (always valid) row; unused when the lane is not `ovalid`
             o.pr = xt_ready ? *xt_ready : out_xt_load<P>(g, m, j0);
-            if (o.ovalid && g.out_mode != OUT_FORWARD && !g.no_noise) {
+            if (o.ovalid && g.out_mode != OUT_FORWARD && (g.keyed || !g.no_noise)) {
                 const int f = sx - 1;
                 const int bn = g.const_noise ? 0 : b;
                 if (g.ext_noise) {
@@ -788,16 +792,26 @@ __device__ __forceinline__ void gemm_prefetch_tile(const GemmArgs& g, int m0, in
                     // (noise_key_of), with the batch term of the counter 0.  Requested here with pb / pr, in front of the main loop.  Keyed, a pass
                     // of the loop serves the lanes of ONE batch element of the wave (1 or 2 elements per 16-row tile); unkeyed there is one pass.
                     // This form costs no kernel a spill or a wave of occupancy; selecting the key's address per lane in a straight line did
-                    // (k_ws<EPI_OUT, 16, ONE>, at its bound of 128 registers: 8 bytes of scratch).  The element's draw offset (GemmArgs::draw_off) is
-                    // read at the same point, one more workgroup-uniform word beside the key
+                    // (k_ws<EPI_OUT, 16, ONE>, at its bound of 128 registers: 8 bytes of scratch).  The element's draw offset and its hold
+                    // (GemmArgs::draw_off) are read at the same point, one workgroup-uniform 8-byte read beside the key.  A held element (a slot of
+                    // dsg_sample_clip_queue_steps whose own chain starts at a later loop index of the round) gives up `ovalid` here: the epilogue
+                    // then writes nothing of it -- state, shadow, twin -- and no noise is drawn for it.  Keyed calls come through here with
+                    // no_noise too (DDIM, eta = 0), for the hold alone
                     bool todo = true;
                     do {
                         const int bu = g.keyed ? __builtin_amdgcn_readfirstlane(bn) : 0;
                         if (!g.keyed || bn == bu) {
                             NoiseKey nk = {g.dyn[0], g.dyn[1], g.dyn[2], g.dyn[3]};
                             unsigned off = 0u;
-                            if (g.keyed) { nk = noise_key_of(g.dyn + 8, bu); off = g.draw_off[bu]; }
-                            o.pz = philox_normal4((imul24((int)imul24(bn, g.keyed ? 0 : g.T) + f, g.Jq) + (unsigned)j0) >> 2, g.dyn[4] + (unsigned)step + off, nk);
+                            bool held = false;
+                            if (g.keyed) {
+                                nk = noise_key_of(g.dyn + 8, bu);
+                                const DrawOff oh = ((const DrawOff*)g.draw_off)[bu];
+                                off = oh.off; held = step < oh.hold;
+                            }
+                            if (held) o.ovalid = false;
+                            else if (!g.no_noise)
+                                o.pz = philox_normal4((imul24((int)imul24(bn, g.keyed ? 0 : g.T) + f, g.Jq) + (unsigned)j0) >> 2, g.dyn[4] + (unsigned)step + off, nk);
                             todo = false;
                         }
                     } while (todo);
@@ -1834,10 +1848,14 @@ __global__ void k_clip_inp_window(const ClipInpArgs a) {
 // arguments -- the constraint and the init motion of the clip, its length, the window index -- comes per slot from a table in device memory
 // (uploaded once per round on the handle's stream, beside the hand-off's HandoffSlot table).  A slot whose clip has no constraint has motion ==
 // mask == null, one without an init motion init == null; a dead slot (no clip this round) has all three null.
+// The start of the slot's chain rides along: do_q and the q_sample pair of the slot's OWN first timestep -- the call's for every slot, or with
+// per-clip skip_timesteps (dsg_sample_clip_queue_steps) the two fp32 values k_x_in / k_clip_x_in get for that skip.
 struct EditSlot {
     const float* motion; const unsigned char* mask;      // [n_out][J] each: the constraint of the slot's clip, or both null
     const float* init;                                   // [n_out][J]: the clip it is re-denoised from, or null
     int n_out, c;                                        // the clip's length and the window the slot stands on
+    float qa, qb;                                        // k_clipq_x_in: sqrt(abar), sqrt(1 - abar) of the slot's first timestep
+    int do_q, pad;                                       // k_clipq_x_in: the slot's skip_timesteps > 0 (a slot without an init is noised from zero)
 };
 // k_clip_inp_window over the slots of a queue round: inp32 / inp_mask [B][T][Jp] as the pose-head epilogue reads them; a slot without a
 // constraint is written 0 / unmasked, so the epilogue's per-byte select keeps its x0 bits
@@ -1872,9 +1890,10 @@ struct ClipXInArgs {
 };
 // One feature quad of a (slot, frame) row of the start: spelled ONCE for k_clip_x_in and k_clipq_x_in, which promise the same bits.
 // i = ((b * T + f) * Jp / 4 + quad); init = the [n_out][J] clip of THIS slot.  init == null (k_clipq_x_in only: a slot without an init
-// motion) starts as k_x_in starts it: do_q ? q_sample1(qa, 0, qb, z) : z
+// motion) starts as k_x_in starts it: do_q ? q_sample1(qa, 0, qb, z) : z.  qa / qb: the q_sample pair of the row's slot (a.qa / a.qb are
+// k_clip_x_in's, one pair for the batch)
 template <class P>
-__device__ __forceinline__ void clip_x_in_row(const ClipXInArgs& a, const float* init, int n_out, int c, int do_q, size_t i) {
+__device__ __forceinline__ void clip_x_in_row(const ClipXInArgs& a, const float* init, int n_out, int c, int do_q, float qa, float qb, size_t i) {
     typedef typename P::elem elem;
     const int nq = a.Jp / 4, keep = a.T - a.S;
     const int j0 = (int)(i % nq) * 4;
@@ -1895,7 +1914,7 @@ __device__ __forceinline__ void clip_x_in_row(const ClipXInArgs& a, const float*
                    : philox_normal4((unsigned)((((size_t)b * a.T + f) * a.Jq + j0) >> 2), a.draw, a.nkey);
         if (init || do_q) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) z[e] = e < nv ? q_sample1(a.qa, v[e], a.qb, z[e]) : 0.f;
+            for (int e = 0; e < 4; ++e) z[e] = e < nv ? q_sample1(qa, v[e], qb, z[e]) : 0.f;
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) if (e >= nv) z[e] = 0.f;
@@ -1912,20 +1931,21 @@ template <class P>
 __global__ void k_clip_x_in(const ClipXInArgs a) {
     const size_t per = (size_t)a.T * (a.Jp / 4), n = (size_t)a.B * per;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        clip_x_in_row<P>(a, a.init + (i / per) * (size_t)a.n_out * a.J, a.n_out, a.c, 1, i);
+        clip_x_in_row<P>(a, a.init + (i / per) * (size_t)a.n_out * a.J, a.n_out, a.c, 1, a.qa, a.qb, i);
 }
 // k_clip_x_in over the slots of a queue round (dsg_sample_clip_queue_edit, in place of k_x_in for the rounds of a call in which some clip has
-// an init motion): init, length and window index per slot from the EditSlot table; `x` carries everything else (its init / n_out / c are not
-// read).  do_q = the call runs with skip_timesteps > 0: what k_x_in does for a slot without an init motion
+// an init motion, and for every round of a call with per-clip skip_timesteps): init, length, window index, do_q and the q_sample pair per
+// slot from the EditSlot table; `x` carries everything else (its init / n_out / c / qa / qb are not read).  do_q = the slot's chain runs
+// with skip_timesteps > 0: what k_x_in does for a slot without an init motion.  x.offs: the START offsets, c * (1 + n_run of the slot)
 struct ClipXInQArgs {
-    ClipXInArgs x; const EditSlot* slots; int do_q;
+    ClipXInArgs x; const EditSlot* slots;
 };
 template <class P>
 __global__ void k_clipq_x_in(const ClipXInQArgs a) {
     const size_t per = (size_t)a.x.T * (a.x.Jp / 4), n = (size_t)a.x.B * per;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const EditSlot s = a.slots[i / per];
-        clip_x_in_row<P>(a.x, s.init, s.n_out, s.c, a.do_q, i);
+        clip_x_in_row<P>(a.x, s.init, s.n_out, s.c, s.do_q, s.qa, s.qb, i);
     }
 }
 // Self-check of the fence-free hand-off (dsg_hip.cpp: uc_selfcheck): `buf` is uncached device memory; the two kernels run as

@@ -560,7 +560,11 @@ class DSGDiffusion:
         neither) and "init_motion", each [n_out_i, J] or [1, n_out_i, J] in the coordinates of the clip returned -- what `sample_clip`
         takes as `inpainting_mask` / `inpainted_motion` / `init_motion` for that clip alone, and clip i is bit for bit that call.  They
         travel with the clip (dsg_sample_clip_queue_edit, called only when some clip has one); a clip without them beside clips with
-        some comes out as it does without."""
+        some comes out as it does without.
+        Per-clip strength: a clip may carry "skip_timesteps" (0 .. num_timesteps - 1); the keyword is the default for clips without one.
+        Clip i is then bit for bit `sample_clip` of that clip alone with ITS skip_timesteps, so fresh generations (0) and edits of any
+        depth share the slots of one call (dsg_sample_clip_queue_steps, called only when some clip has the key; `lib.clip_queue_plan`
+        with `n_run` is the schedule).  The draw counter advances by max(K_i * (1 + n_run_i))."""
         lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
         clips = list(clips)
         if not lanes or not clips:
@@ -573,7 +577,16 @@ class DSGDiffusion:
             inners.append(inner)
         cfg = inners[0].cfg
         S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
-        n_run = self.num_timesteps - skip_timesteps
+        skips, own_skips = [], False
+        for i, clip in enumerate(clips):
+            sk = clip.get("skip_timesteps")
+            if sk is None:      # (the keyword: checked by the library, as in a call without the key)
+                skips.append(int(skip_timesteps))
+                continue
+            own_skips = True
+            if not 0 <= int(sk) < self.num_timesteps:
+                raise ValueError(f"sample_clip_queue: clip {i}: skip_timesteps {int(sk)} outside [0, {self.num_timesteps - 1}]")
+            skips.append(int(sk))
         use_torch = L.is_torch(clips[0]["feats"][0])
         edit_keys = ("inpainting_mask", "inpainted_motion", "init_motion")
         stream = L.current_stream_ptr() if use_torch or any(L.is_torch(c.get(k)) for c in clips for k in edit_keys) else None
@@ -630,11 +643,14 @@ class DSGDiffusion:
         hs = (C.c_void_p * len(inners))(*[m.handle for m in inners])
         lib = inners[0].lib
         tail = (int(B), mbuf.p, int(bool(guided)), C.byref(a), int(bool(root_shift)), int(bool(keep_last_tail)), stream)
-        if edited:
+        if own_skips:
+            sk = np.asarray(skips, np.int32)
+            lib.check(lib.cdll.dsg_sample_clip_queue_steps(hs, len(inners), jobs, edits if edited else None, sk.ctypes.data, len(clips), *tail))
+        elif edited:
             lib.check(lib.cdll.dsg_sample_clip_queue_edit(hs, len(inners), jobs, edits, len(clips), *tail))
         else:
             lib.check(lib.cdll.dsg_sample_clip_queue(hs, len(inners), jobs, len(clips), *tail))
-        self._draw += max(int(j.K) for j in jobs) * (1 + n_run)
+        self._draw += max(int(j.K) * (1 + self.num_timesteps - sk) for j, sk in zip(jobs, skips))
         self._last_model = inners[0]
         return outs
 

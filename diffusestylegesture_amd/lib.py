@@ -76,6 +76,9 @@ SYMBOLS = {
     "dsg_sample_clip_queue": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_clip_job), _I, _I, _P, _I, C.POINTER(dsg_sample_args), _I, _I, _P]),
     "dsg_sample_clip_queue_edit": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_clip_job), C.POINTER(dsg_clip_edit), _I, _I, _P, _I,
                                         C.POINTER(dsg_sample_args), _I, _I, _P]),
+    "dsg_sample_clip_queue_steps": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_clip_job), C.POINTER(dsg_clip_edit), _P, _I, _I, _P, _I,
+                                         C.POINTER(dsg_sample_args), _I, _I, _P]),
+    "dsg_clip_queue_plan_steps": (_I, [_P, _P, _I, _I, _P, _P, C.POINTER(C.c_int32), C.POINTER(_I64)]),
     "dsg_set_kernel_set": (_I, [_P, _I]),
     "dsg_get_kernel_set": (_I, [_P, C.POINTER(_I)]),
     "dsg_recommend_kernel_set": (_I, [_P, _I, _I, C.POINTER(_I)]),
@@ -141,12 +144,22 @@ def trim(device: int = -1, library: "DSGLibrary | None" = None):
     return int(rel.value), int(held.value)
 
 
-def clip_queue_plan(K, n_slots: int, library: "DSGLibrary | None" = None):
+def clip_queue_plan(K, n_slots: int, library: "DSGLibrary | None" = None, n_run=None):
     """dsg_clip_queue_plan: the schedule dsg_sample_clip_queue follows for clips of K[j] windows over n_slots slots (host only).
-    Returns (slot[j], first_round[j], n_rounds)."""
+    Returns (slot[j], first_round[j], n_rounds).  With `n_run` (steps per clip: the schedule length minus the clip's skip_timesteps)
+    dsg_clip_queue_plan_steps, the schedule of a queue with per-clip skip_timesteps: returns (slot[j], first_round[j], n_rounds,
+    total_steps), total_steps = the sum over the rounds of the deepest clip alive in each."""
     lib = library or default_library()
     k = np.ascontiguousarray(K, dtype=np.int32)
     slot, first, n_rounds = np.zeros(len(k), np.int32), np.zeros(len(k), np.int32), C.c_int32(0)
+    if n_run is not None:
+        nr = np.ascontiguousarray(n_run, dtype=np.int32)
+        if nr.shape != k.shape:
+            raise ValueError(f"clip_queue_plan: n_run has {nr.size} entries for {k.size} clips")
+        total = C.c_int64(0)
+        lib.check(lib.cdll.dsg_clip_queue_plan_steps(k.ctypes.data, nr.ctypes.data, len(k), int(n_slots), slot.ctypes.data, first.ctypes.data,
+                                                     C.byref(n_rounds), C.byref(total)))
+        return slot.tolist(), first.tolist(), int(n_rounds.value), int(total.value)
     lib.check(lib.cdll.dsg_clip_queue_plan(k.ctypes.data, len(k), int(n_slots), slot.ctypes.data, first.ctypes.data, C.byref(n_rounds)))
     return slot.tolist(), first.tolist(), int(n_rounds.value)
 

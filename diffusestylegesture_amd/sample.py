@@ -560,8 +560,8 @@ def _queue_stream(clip, i):
 
 
 def _queue_edits(clip):
-    """the per-clip edits of a clip-queue dict, passed through as `DSGDiffusion.sample_clip_queue` takes them"""
-    return {k: clip[k] for k in ("inpainting_mask", "inpainted_motion", "init_motion") if clip.get(k) is not None}
+    """the per-clip edits of a clip-queue dict (and the clip's own skip_timesteps, the strength of its edit), passed through as `DSGDiffusion.sample_clip_queue` takes them"""
+    return {k: clip[k] for k in ("inpainting_mask", "inpainted_motion", "init_motion", "skip_timesteps") if clip.get(k) is not None}
 
 
 def generate_clip_queue(lanes, diffusion, clips, seed=123456, smoothing=True, skip_timesteps=0, ddim=False, eta=0.0,
@@ -572,7 +572,8 @@ def generate_clip_queue(lanes, diffusion, clips, seed=123456, smoothing=True, sk
     "style": one-hot list or [6] array; optional "seed_pose" [1, J, 1, S] (default zeros), "scale" (classifier-free guidance for the whole
     call as soon as one clip has it; the others run at scale 1), "clip_id" (default: the clip's index), and the clip's own edits
     "inpainting_mask" / "inpainted_motion" / "init_motion", each [K_i*stride - n_seed, J] (or [1, ...]) as `generate_clip` takes them for
-    that clip.  All clips share `seed`; clip i draws
+    that clip, and "skip_timesteps", the clip's own (default: the keyword): fresh generations and edits of any depth share one queue.
+    All clips share `seed`; clip i draws
     from the Philox stream (seed, clip_id) and is bit for bit `generate_clip(lane of batch 1, ..., windows="library", stream_id=clip_id)`
     with the clip's edits under the same kernel set.  `kernel_set` as in `generate_clips_streams`.  Returns a list of [K_i*stride - n_seed, J] arrays in the
     order given."""
@@ -592,7 +593,7 @@ def generate_clip_queue_dsgplus(lanes, diffusion, clips, seed=123456, skip_times
     stride-long windows, each [1, T, A_src]), "style", "seed_pose" [1, J, 1, S] (the ground-truth seed of window 0), "real_n_frames", and
     for DiffuseStyleGesture++ "seed_last" [1, J, 1, S]; optional "scale", "clip_id", and the clip's own edits "inpainting_mask" /
     "inpainted_motion" / "init_motion" in the [K_i*stride, J] coordinates `generate_clip_dsgplus` documents (all J features, before the
-    crop and the feature division).  The per-window features are built as
+    crop and the feature division) and its own "skip_timesteps" (default: the keyword).  The per-window features are built as
     `_dsgplus_window_y` builds them; every clip is finished as `_dsgplus_finish` finishes it -- cropped to ITS real_n_frames, the first
     J // feature_division features kept.  Clip i is bit for bit `generate_clip_dsgplus(lane of batch 1, ..., windows="library",
     stream_id=clip_id)`.  Returns a list of [real_n_frames_i, J // feature_division] arrays in the order given."""

@@ -345,7 +345,8 @@ int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int n_frames, v
  * root_shift is applied after either, in the window's own frame; guidance twins get the same start, the constraint acts after the
  * combination; skip_timesteps == 0 with an init is allowed (the last timestep).  In a call where some job has an init motion, a slot without
  * one starts exactly as it does in dsg_sample_clip_queue: q_sample of a zero init with skip_timesteps > 0, the draw itself with
- * skip_timesteps == 0.  A dead slot is a slot without edits.
+ * skip_timesteps == 0 (skip_timesteps is the call's here; dsg_sample_clip_queue_steps below gives every job its own, so that fresh clips
+ * and edits share one call).  A dead slot is a slot without edits.
  * On the device: per round one table of {constraint, init, n_out, c} per slot goes up beside the hand-off's; k_clipq_inp_window cuts every
  * slot's constraint into the buffers of dsg_set_inpainting (lanes that run a constrained job only; without any, no cut kernel runs), and
  * k_clipq_x_in starts the round in place of the plain start kernel (lanes that run a job with an init motion only).
@@ -366,6 +367,46 @@ typedef struct dsg_clip_edit {      /* one per job, parallel to jobs[]; all thre
 int dsg_sample_clip_queue_edit(dsg_handle** lanes, int n_lanes, const dsg_clip_job* jobs, const dsg_clip_edit* edits /* NULL or [n_jobs] */,
                                int n_jobs, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args,
                                int root_shift, int keep_last_tail, void* stream);
+/* Clip queue with per-clip skip_timesteps: one queue for generate and edit requests.  skip_timesteps -- how deep a clip is noised before it is
+ * sampled back, the strength of an edit -- travels with the job like its init motion and its constraint: skip_timesteps NULL, or int32
+ * [n_jobs] parallel to jobs[]; an entry < 0 reads as args->skip_timesteps.  Fresh generations (skip 0, from pure noise) and edits of any depth
+ * then share the slots of one call.  dsg_sample_clip_queue_edit(...) IS this call with skip_timesteps == NULL; with NULL, or with every entry
+ * equal to the call's skip, the call makes the same launches and produces the same bits, and its plan is dsg_clip_queue_plan's.
+ * Job j comes out bit for bit as dsg_sample_clip produces it alone with args->skip_timesteps = skip_j: B = 1, the job's (seed, stream_id),
+ * the same draw_base, conditioning, root_shift / keep_last_tail, named kernel set and edits, DDPM and DDIM.  Everything written above for
+ * dsg_sample_clip_queue_edit holds per slot with the slot's own skip: a slot with an init motion starts from q_sample of its slice at ITS
+ * first timestep (skip 0 with an init is allowed: the last timestep), a slot without one from q_sample of a zero init when its skip is
+ * > 0 and from the draw itself when it is 0; window c of job j draws draw_base + c * (1 + n_run_j) for its start and the following n_run_j
+ * for its steps, n_run_j = num_timesteps - skip_j.
+ * Rounds: with n = num_timesteps, round r runs ONE loop for all lanes from s_r = the smallest skip alive in it (over all lanes), n - s_r
+ * steps, as dsg_sample does with skip_timesteps = s_r: loop index i is timestep index n - 1 - s_r - i for every element, so the time
+ * embedding and the step coefficients stay one set per step.  A slot with skip_b > s_r HOLDS for its first skip_b - s_r loop indices: the
+ * pose-head epilogue leaves the element alone -- no draw, no write of its state, its bf16 shadow or its guidance twin -- and its chain runs
+ * on the loop's last n - skip_b steps, on the timesteps it runs alone.  A held element's rows still pass through the denoiser (rows are
+ * independent: the argument that covers dead slots), so a light edit beside a fresh clip occupies its slot for the fresh clip's steps;
+ * the plan keeps that small.  Per-element timesteps (slots on different timesteps within one step) are not part of this.
+ * The plan (dsg_clip_queue_plan_steps: host only, exactly what the call follows; n_run[j] = n - skip_j, NULL: all equal): jobs are taken
+ * deepest first (n_run descending, then K descending, then lower index); each goes to the slot with the fewest rounds so far (ties: lowest
+ * slot); slot / first_round / n_rounds as dsg_clip_queue_plan; *total_steps (nullable) = the sum over the rounds of the largest n_run alive
+ * in that round.  With n_run == NULL the order and outputs are dsg_clip_queue_plan's and total_steps = n_rounds.  The deep jobs go first, so
+ * the closing rounds hold only light ones and run short.  Example: 24 fresh clips and 24 edits with n_run = 100, all K = 4, on 16 slots of
+ * a 1000-step schedule: 8 rounds of 1000 steps and 4 rounds of 100, 8 400 steps in all; two separate calls take 8 800, index-order placement
+ * of an interleaved job list up to 12 000.  The gain in steps is modest; the point is one queue for everything.
+ * On the device: per slot one 8-byte word {draw offset, hold} beside the element's key (the offset is c * (1 + n_run_j) - hold: the
+ * element's step i is the round's loop index i + hold); in a call with per-job skips every lane starts every round through k_clipq_x_in,
+ * whose table carries per slot whether to q_sample and the fp32 pair sqrt(abar), sqrt(1 - abar) of the slot's own first timestep -- the
+ * two values the stand-alone start kernels get for skip_timesteps = skip_b.
+ * dsg_last_sample_ms afterwards: the sum over the rounds, n_steps = the sum over the rounds of n - s_r = the plan's total_steps.
+ * DSG_E_INVALID, with the job number in dsg_last_error: a skip outside [0, n - 1] after the substitution; and everything
+ * dsg_sample_clip_queue_edit refuses.  On every return path, errors included, the lanes are left as they came: no inpainting, no edit
+ * table, unkeyed, no draw offsets and no holds, one lane.  dsg_clip_job and dsg_clip_edit keep their layouts.  Added without a version
+ * step: dsg_version() stays 330. */
+int dsg_sample_clip_queue_steps(dsg_handle** lanes, int n_lanes, const dsg_clip_job* jobs, const dsg_clip_edit* edits /* NULL or [n_jobs] */,
+                                const int32_t* skip_timesteps /* NULL or [n_jobs]; an entry < 0: args->skip_timesteps */,
+                                int n_jobs, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args,
+                                int root_shift, int keep_last_tail, void* stream);
+int dsg_clip_queue_plan_steps(const int32_t* K, const int32_t* n_run /* NULL: all equal */, int n_jobs, int n_slots,
+                              int32_t* slot, int32_t* first_round, int32_t* n_rounds, int64_t* total_steps /* nullable */);
 /* Per-element noise streams ("keyed noise") for dsg_sample / _multi / dsg_sample_clip / _multi.  seeds, stream_ids: HOST uint64[B], copied by
  * the call.  While set, element b of the batch draws from its own pair (seed_b, sid_b): draw d at frame f, feature j is
  *   philox4x32_10(ctr = ((f * Jq + j) >> 2, d, sid_b lo, sid_b hi), key = (seed_b lo, seed_b hi)) + Box-Muller,   Jq = J rounded up to 4,
