@@ -205,6 +205,10 @@ struct dsg_handle {
     // rounds of a call in which a job of this lane has an init motion, sample_prepare starts the round through k_clipq_x_in
     EditSlot* q_edits = nullptr; std::vector<EditSlot> q_edits_host; bool q_edit_init = false;
     unsigned char* q_stage = nullptr; size_t q_stage_cap = 0;
+    // queue session (dsg_queue_open .. dsg_queue_close): the session that owns this lane -- while set, every entry point that samples on the
+    // handle or changes its state is refused (owned_by_queue) -- and the round's gather table (k_clipq_gather) with its host copy
+    struct dsg_queue* owner = nullptr;
+    GatherSlot* q_gather = nullptr; std::vector<GatherSlot> q_gather_host;
     int latency_mode = -1;               // dsg_config.latency_mode: -1 auto, 0 never the LATENCY set, 1 always
 #ifndef DSG_EMU
     dsg_aql::Ctx aql;                    // hand-written AQL submission of the step loop (dsg_aql.h)
@@ -251,6 +255,8 @@ struct dsg_handle {
 };
 
 // bf16 activations (DSG_PREC_BF16, DSG_PREC_BF16W2): the compute-dtype shadows / fragment layouts of the bf16 kernels
+// a lane of an open queue session belongs to it: DSG_E_STATE for whoever else wants to sample on it or change its state
+static int owned_by_queue(const dsg_handle* h) { return h && h->owner ? fail(DSG_E_STATE, "handle belongs to an open queue") : 0; }
 static inline bool is_bf16(const dsg_handle* h) { return h->prec != DSG_PREC_FP32; }
 static inline bool core_narrow(const dsg_handle* h) { return h->core == Core::C128 || h->core == Core::C256; }      // the ZEGGS / tiny widths
 static inline bool core_wide(const dsg_handle* h) { return h->core == Core::C384 || h->core == Core::C512; }        // the DSG+ widths
@@ -641,6 +647,7 @@ extern "C" int dsg_create(const dsg_config* c, dsg_handle** out) {
 
 extern "C" int dsg_destroy(dsg_handle* h) {
     if (!h) return 0;
+    CHK(owned_by_queue(h));
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& kv : h->graphs) { (void)hipGraphExecDestroy(kv.second.exec); (void)hipGraphDestroy(kv.second.graph); }
@@ -683,6 +690,7 @@ extern "C" int dsg_clone(dsg_handle* src, int max_batch, dsg_handle** out) {
 extern "C" int dsg_load_tensor(dsg_handle* h, const char* name, const void* data, const int64_t* shape, int ndim,
                                int dtype) {
     if (!h || !name || !data || !shape) return fail(DSG_E_INVALID, "dsg_load_tensor: null argument");
+    CHK(owned_by_queue(h));
     if (h->is_clone) return fail(DSG_E_STATE, "dsg_load_tensor on a clone: load the weights into the source handle");
     if (dtype != 0) return fail(DSG_E_NOT_IMPLEMENTED, "dsg_load_tensor: only float32 (dtype 0)");
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -760,6 +768,7 @@ static int padded_vec(dsg_handle* h, float** dst, const float* src, int n, int n
 static int finalize_weights(dsg_handle* h);
 extern "C" int dsg_finalize_weights(dsg_handle* h) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
+    CHK(owned_by_queue(h));
     if (h->is_clone) return fail(DSG_E_STATE, "dsg_finalize_weights on a clone");
     h->alloc_shared = true;
     const int rc = finalize_weights(h);
@@ -835,6 +844,7 @@ static int finalize_weights(dsg_handle* h) {
 
 extern "C" int dsg_set_schedule(dsg_handle* h, const double* betas, const int64_t* tmap, int n) {
     if (!h || !betas || !tmap) return fail(DSG_E_INVALID, "dsg_set_schedule: null argument");
+    CHK(owned_by_queue(h));
     Sched s;
     CHK(build_sched(betas, n, s));
     s.tmap.resize(n);
@@ -871,6 +881,7 @@ static int order_before(dsg_handle* h, void* user_stream);
 // snippet for every window of a clip (BEAT-TWH sample.py:85-93), so it is handed over once and kept.
 extern "C" int dsg_set_seed_last(dsg_handle* h, const float* seed_last, int B, void* stream) {
     if (!h || !seed_last) return fail(DSG_E_INVALID, "null argument");
+    CHK(owned_by_queue(h));
     if (h->cfg.variant != 5) return fail(DSG_E_INVALID, "dsg_set_seed_last is for variant 5 (cross_local_attention5) only");
     if (B <= 0 || B > h->Bmax) return fail(DSG_E_INVALID, "batch exceeds max_batch");
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -978,10 +989,12 @@ static int set_window_cond(dsg_handle* h, const float* style, const float* seed,
 }
 extern "C" int dsg_set_window_cond(dsg_handle* h, const float* style, const float* seed, const float* audio,
                                    const uint8_t* mask_local, int mask_batch, int B, int uncond, void* stream) {
+    CHK(owned_by_queue(h));
     return set_window_cond(h, style, seed, audio, mask_local, mask_batch, B, uncond, nullptr, stream);
 }
 extern "C" int dsg_set_window_cond_cfg(dsg_handle* h, const float* style, const float* seed, const float* audio,
                                        const uint8_t* mask_local, int mask_batch, int B, const float* scale, void* stream) {
+    CHK(owned_by_queue(h));
     if (!scale) return fail(DSG_E_INVALID, "dsg_set_window_cond_cfg: scale required (y['scale'])");
     return set_window_cond(h, style, seed, audio, mask_local, mask_batch, B, 0, scale, stream);
 }
@@ -1236,6 +1249,7 @@ static int ensure_set_buffers(dsg_handle* h, const KernelSel& k) {
 
 extern "C" int dsg_set_kernel_set(dsg_handle* h, int set) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
+    CHK(owned_by_queue(h));
     if (set < DSG_KSET_AUTO || set > DSG_KSET_ROWS) return fail(DSG_E_INVALID, "dsg_set_kernel_set: unknown kernel set");
     if (set != DSG_KSET_AUTO) CHK(check_set(h, set));      // (round-5 advisor: this entry point used to accept LATENCY at latent_dim 384 / 512, and every later call failed)
     if (getenv("DSG_KSET")) {                  // an A/B run pinned the set for the whole process: say so once, keep the pinned set
@@ -2207,6 +2221,7 @@ static int rows_for(dsg_handle* h, int B, int* rows) {
 // conditioning does not touch it.  The constraint is kept in the state's layout, in cached memory like the conditioning: the loop only reads it.
 extern "C" int dsg_set_inpainting(dsg_handle* h, const uint8_t* mask, const float* motion, int B, void* stream) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
+    CHK(owned_by_queue(h));
     if (!mask && !motion) { h->inpB = 0; return 0; }
     if (!mask || !motion) return fail(DSG_E_INVALID, "dsg_set_inpainting: mask and motion go together (both NULL switches the constraint off)");
     if (B <= 0 || B > h->Bmax) return fail(DSG_E_INVALID, "batch exceeds max_batch");
@@ -2238,6 +2253,7 @@ extern "C" int dsg_set_inpainting(dsg_handle* h, const uint8_t* mask, const floa
 // buffers of dsg_set_inpainting, which are allocated here too.  Sticky until switched off (both NULL); dsg_forward / dsg_sample / _multi ignore it.
 extern "C" int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const float* motion, int B, int n_frames, void* stream) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
+    CHK(owned_by_queue(h));
     if (!mask && !motion) { h->cinpB = 0; h->cinp_frames = 0; return 0; }
     if (!mask || !motion) return fail(DSG_E_INVALID, "dsg_set_clip_inpainting: mask and motion go together (both NULL switches the constraint off)");
     if (B <= 0 || B > h->Bmax) return fail(DSG_E_INVALID, "batch exceeds max_batch");
@@ -2273,6 +2289,7 @@ extern "C" int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const
 // (NULL); dsg_forward / dsg_sample / _multi ignore it.
 extern "C" int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int n_frames, void* stream) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
+    CHK(owned_by_queue(h));
     if (!motion) { h->cinitB = 0; h->cinit_frames = 0; return 0; }
     if (B <= 0 || B > h->Bmax) return fail(DSG_E_INVALID, "batch exceeds max_batch");
     if (n_frames < 1) return fail(DSG_E_INVALID, "dsg_set_clip_init: n_frames < 1");
@@ -2307,6 +2324,7 @@ extern "C" int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int 
 // global generator, gaussian_diffusion.py:704, :542).
 extern "C" int dsg_set_noise_streams(dsg_handle* h, const uint64_t* seeds, const uint64_t* stream_ids, int B) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
+    CHK(owned_by_queue(h));
     if (!seeds && !stream_ids) { h->nkB = 0; return 0; }
     if (B < 1 || B > h->Bmax)
         return fail(DSG_E_INVALID, "dsg_set_noise_streams: batch " + std::to_string(B) + " outside 1 .. max_batch (" + std::to_string(h->Bmax) + ")");
@@ -2323,6 +2341,7 @@ extern "C" int dsg_set_noise_streams(dsg_handle* h, const uint64_t* seeds, const
 
 extern "C" int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, float* out, int B, void* stream) {
     if (!h || !x || !t || !out) return fail(DSG_E_INVALID, "dsg_forward: null argument");
+    CHK(owned_by_queue(h));
     if (!h->finalized || !h->cond_set) return fail(DSG_E_STATE, "dsg_forward before finalize / set_window_cond");
     int rows = 0;
     CHK(rows_for(h, B, &rows));
@@ -2724,6 +2743,7 @@ static int sample_finish(dsg_handle* h, float* out, void* stream, SampleJob& job
 
 extern "C" int dsg_sample(dsg_handle* h, const dsg_sample_args* a, float* out, int B, void* stream) {
     if (!h || !a || !out) return fail(DSG_E_INVALID, "dsg_sample: null argument");
+    CHK(owned_by_queue(h));
     SampleJob job;
     CHK(sample_prepare(h, a, B, stream, job));
     CHK(run_lanes(&h, 1, a, &job));
@@ -2739,6 +2759,7 @@ extern "C" int dsg_sample_multi(dsg_handle** hs, int n, const dsg_sample_args* a
     if (!hs || !args || !outs || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_multi: bad argument");
     for (int i = 0; i < n; ++i) {
         if (!hs[i] || !outs[i]) return fail(DSG_E_INVALID, "dsg_sample_multi: null handle / output");
+        CHK(owned_by_queue(hs[i]));
         for (int j = 0; j < i; ++j) if (hs[j] == hs[i]) return fail(DSG_E_INVALID, "dsg_sample_multi: a handle appears twice");
         if (hs[i]->cfg.device != hs[0]->cfg.device) return fail(DSG_E_INVALID, "dsg_sample_multi: lanes must live on one device");
     }
@@ -2792,6 +2813,7 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
     for (int i = 0; i < n; ++i) {
         dsg_handle* h = hs[i];
         if (!h || !outs[i] || !styles[i] || !audios[i]) return fail(DSG_E_INVALID, "dsg_sample_clip: null handle / style / audio / output");
+        CHK(owned_by_queue(h));
         for (int j = 0; j < i; ++j) if (hs[j] == h) return fail(DSG_E_INVALID, "dsg_sample_clip_multi: a handle appears twice");
         if (h->cfg.device != hs[0]->cfg.device) return fail(DSG_E_INVALID, "dsg_sample_clip_multi: lanes must live on one device");
         if (h->J != hs[0]->J || h->T != hs[0]->T || h->S != hs[0]->S) return fail(DSG_E_INVALID, "dsg_sample_clip_multi: lanes of one model");
@@ -2994,23 +3016,13 @@ static int launch_handoff_q(dsg_handle* h, int B, int round, int root_shift, int
     return 0;
 }
 
-// edits: NULL (dsg_sample_clip_queue), or one dsg_clip_edit per job -- the clip's constraint and / or the clip it is re-denoised from, in the
-// coordinates of the job's `out`.  Host tensors are staged on the lane that runs the job before the rounds start; per round the lane's edit
-// table (EditSlot) goes up beside the hand-off's, k_clipq_inp_window cuts the round's constraint for every slot (lanes that run a constrained
-// job: inpB = B for the rounds of this call) and sample_prepare starts the round through k_clipq_x_in (lanes that run a job with an init).
-// skip_timesteps: NULL (dsg_sample_clip_queue_edit), or one entry per job (< 0: args->skip_timesteps).  When an entry differs from the
-// call's, the rounds follow dsg_clip_queue_plan_steps; round r runs from s_r = the smallest skip alive in it, over all lanes, as dsg_sample
-// does with skip_timesteps = s_r; a slot with a larger skip holds for skip - s_r loop indices (DrawOff::hold) and every lane starts every
-// round through k_clipq_x_in, which reads do_q and the q_sample pair of the slot's own first timestep from the edit table
-extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_clip_job* jobs, const dsg_clip_edit* edits, const int32_t* skip_timesteps,
-                                           int n_jobs, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift,
-                                           int keep_last_tail, void* stream) {
-    if (!hs || !jobs || !args || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: bad argument");
-    if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
-    if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: n_jobs < 1");
+// The checks of a queue on its lanes, B, guided and args, and on one job: written once for dsg_sample_clip_queue_steps and the session
+// (dsg_queue_open / dsg_queue_submit), which make the same refusals with the same messages
+static int clip_queue_check_lanes(dsg_handle** hs, int n, int B, int guided, const dsg_sample_args* args) {
     for (int i = 0; i < n; ++i) {
         dsg_handle* h = hs[i];
         if (!h) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: null handle");
+        CHK(owned_by_queue(h));
         for (int j = 0; j < i; ++j) if (hs[j] == h) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: a handle appears twice");
         if (!h->finalized) return fail(DSG_E_STATE, "dsg_sample_clip_queue before dsg_finalize_weights");
         if (h->sched.n == 0) return fail(DSG_E_STATE, "dsg_sample_clip_queue before dsg_set_schedule");
@@ -3031,15 +3043,34 @@ extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_cli
     if (args->step_noise || args->init_noise || args->init_image || args->n_dump || args->first_step || args->max_steps || args->const_noise)
         return fail(DSG_E_INVALID, "dsg_sample_clip_queue: step_noise / init_noise / init_image / dump_steps / first_step / max_steps / const_noise are not for a queue of clips");
     if (args->mode != DSG_MODE_DDPM && args->mode != DSG_MODE_DDIM) return fail(DSG_E_INVALID, "mode");
+    return 0;
+}
+static int clip_queue_check_job(const dsg_clip_job& q, const dsg_clip_edit* edit, int64_t j, int variant5) {
+    if (q.K < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has K < 1");
+    if (!q.style || !q.audio || !q.out) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has a null style / audio / out");
+    if (variant5 && !q.seed_last) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: variant 5 needs seed_last for every job (job " + std::to_string(j) + " has none)");
+    if (edit && !edit->inp_mask != !edit->inp_motion)
+        return fail(DSG_E_INVALID, "dsg_sample_clip_queue_edit: inp_mask and inp_motion go together (both NULL: no constraint); job " + std::to_string(j) + " has one of them");
+    return 0;
+}
+
+// edits: NULL (dsg_sample_clip_queue), or one dsg_clip_edit per job -- the clip's constraint and / or the clip it is re-denoised from, in the
+// coordinates of the job's `out`.  Host tensors are staged on the lane that runs the job before the rounds start; per round the lane's edit
+// table (EditSlot) goes up beside the hand-off's, k_clipq_inp_window cuts the round's constraint for every slot (lanes that run a constrained
+// job: inpB = B for the rounds of this call) and sample_prepare starts the round through k_clipq_x_in (lanes that run a job with an init).
+// skip_timesteps: NULL (dsg_sample_clip_queue_edit), or one entry per job (< 0: args->skip_timesteps).  When an entry differs from the
+// call's, the rounds follow dsg_clip_queue_plan_steps; round r runs from s_r = the smallest skip alive in it, over all lanes, as dsg_sample
+// does with skip_timesteps = s_r; a slot with a larger skip holds for skip - s_r loop indices (DrawOff::hold) and every lane starts every
+// round through k_clipq_x_in, which reads do_q and the q_sample pair of the slot's own first timestep from the edit table
+extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_clip_job* jobs, const dsg_clip_edit* edits, const int32_t* skip_timesteps,
+                                           int n_jobs, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift,
+                                           int keep_last_tail, void* stream) {
+    if (!hs || !jobs || !args || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: bad argument");
+    if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
+    if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: n_jobs < 1");
+    CHK(clip_queue_check_lanes(hs, n, B, guided, args));
     const int variant5 = hs[0]->cfg.variant == 5;
-    for (int j = 0; j < n_jobs; ++j) {
-        const dsg_clip_job& q = jobs[j];
-        if (q.K < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has K < 1");
-        if (!q.style || !q.audio || !q.out) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has a null style / audio / out");
-        if (variant5 && !q.seed_last) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: variant 5 needs seed_last for every job (job " + std::to_string(j) + " has none)");
-        if (edits && !edits[j].inp_mask != !edits[j].inp_motion)
-            return fail(DSG_E_INVALID, "dsg_sample_clip_queue_edit: inp_mask and inp_motion go together (both NULL: no constraint); job " + std::to_string(j) + " has one of them");
-    }
+    for (int j = 0; j < n_jobs; ++j) CHK(clip_queue_check_job(jobs[j], edits ? &edits[j] : nullptr, j, variant5));
     const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J, Ta = hs[0]->Ta, As = hs[0]->As, sdi = hs[0]->cfg.style_dim_in;
     const int n_slots = n * B, keep = T - S;
     const int n_sched = hs[0]->sched.n;
@@ -3259,6 +3290,388 @@ extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip
 extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job* jobs, int n_jobs, int B, const uint8_t* mask_local, int guided,
                                      const dsg_sample_args* args, int root_shift, int keep_last_tail, void* stream) {
     return dsg_sample_clip_queue_edit(hs, n, jobs, nullptr, n_jobs, B, mask_local, guided, args, root_shift, keep_last_tail, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Queue session (dsg_queue_*): the clip queue as an object that lives between rounds.  Jobs are submitted while it runs, every round is a
+// round of dsg_sample_clip_queue_steps -- the same tables, set_window_cond, sample_prepare, run_lanes, launch_handoff_q -- and a job's rows
+// are in the caller's memory after the round that made them final.  What differs from the one-shot call:
+//   placement  first come, first served: at the start of a round the free slots, lowest first, take the pending jobs, oldest ticket first
+//              (dsg_queue_place is the same rule on the host);
+//   inputs     a job's host tensors are copied into session-owned device memory at submit; the round's per-slot conditioning is gathered on
+//              the device (k_clipq_gather, one launch per lane) instead of copied slot by slot from the caller's memory;
+//   start      every lane starts every round through the edit table (k_clipq_x_in), as the one-shot call does with per-job skips: a job
+//              with its own skip or an init motion may arrive in any round;
+//   outputs    a host `out` is fed from a session-owned device clip, the rows that became final copied after every round.
+// ---------------------------------------------------------------------------------------------------------
+struct QBlock { void* p; size_t cap; };
+struct QJob {
+    dsg_clip_job job;                 // the pointers as the device reads them: the caller's device tensors, or staging
+    EditSlot ed;                      // motion / mask / init as the device reads them, n_out
+    float* host_out = nullptr;        // the caller's host `out` (null: a device `out`, written by the hand-off itself)
+    float* clip = nullptr;            // [n_out][J] on the device
+    int n_out = 0, skip = 0, n_run = 0;
+    int state = DSG_JOB_PENDING, windows_done = 0, rows_ready = 0, rows_copied = 0, slot = -1, first_round = -1;
+    std::vector<QBlock> blocks;       // the staging the job holds; back to the session's free list when it is done or cancelled
+};
+struct dsg_queue {
+    std::vector<dsg_handle*> hs;
+    int n = 0, B = 0, guided = 0, root_shift = 0, keep_last_tail = 0;
+    dsg_sample_args args;
+    unsigned char* mask_d = nullptr;  // the session's copy of mask_local (null: none was given)
+    std::vector<QJob> jobs;           // index = ticket
+    std::vector<int64_t> slot_job;    // [n * B] -> ticket, -1: free
+    size_t next_pending = 0;          // no ticket below it is pending
+    int64_t rounds_total = 0;
+    std::multimap<size_t, void*> free_blocks;      // recycled staging, by capacity
+    std::vector<void*> all_blocks;                 // every staging block ever allocated: released at close
+    bool seed_last_written = false;
+};
+// staging: blocks in power-of-two size classes (>= 256 bytes), recycled within the session, never freed between rounds (hipFree synchronises)
+static int queue_take(dsg_queue* q, size_t bytes, QJob& jb, void** out) {
+    size_t cap = 256;
+    while (cap < bytes) cap <<= 1;
+    void* p = nullptr;
+    auto it = q->free_blocks.find(cap);
+    if (it != q->free_blocks.end()) { p = it->second; q->free_blocks.erase(it); }
+    else {
+        if (hipMalloc(&p, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(DSG_E_RUNTIME, "dsg_queue_submit: out of device memory for " + std::to_string(cap) + " bytes of staging");
+        }
+        q->all_blocks.push_back(p);
+    }
+    jb.blocks.push_back(QBlock{p, cap});
+    *out = p;
+    return 0;
+}
+static void queue_give(dsg_queue* q, QJob& jb) {
+    for (const QBlock& b : jb.blocks) q->free_blocks.emplace(b.cap, b.p);
+    jb.blocks.clear();
+}
+static int queue_rows_ready(const dsg_queue* q, const QJob& jb) {
+    const int keep = q->hs[0]->T - q->hs[0]->S, S = q->hs[0]->S;
+    if (jb.windows_done >= jb.job.K) return jb.n_out;
+    // window c leaves rows [c * keep - S, (c + 1) * keep - S) final (handoff_row), with keep_last_tail too: there only the LAST window writes
+    // its closing S frames, and a job past its last window reports n_out above
+    const int64_t r = (int64_t)jb.windows_done * keep - S;
+    return (int)std::max<int64_t>(0, std::min<int64_t>(jb.n_out, r));
+}
+
+extern "C" int dsg_queue_place(const int32_t* K, const int32_t* arrive_round, int n_jobs, int n_slots, int32_t* slot, int32_t* first_round,
+                               int32_t* n_rounds) {
+    if (!K || !slot || !first_round || !n_rounds) return fail(DSG_E_INVALID, "dsg_queue_place: null argument");
+    if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_queue_place: n_jobs < 1");
+    if (n_slots < 1) return fail(DSG_E_INVALID, "dsg_queue_place: n_slots < 1");
+    for (int j = 0; j < n_jobs; ++j) {
+        if (K[j] < 1) return fail(DSG_E_INVALID, "dsg_queue_place: job " + std::to_string(j) + " has K < 1");
+        if (arrive_round && (arrive_round[j] < 0 || (j > 0 && arrive_round[j] < arrive_round[j - 1])))
+            return fail(DSG_E_INVALID, "dsg_queue_place: arrive_round must be non-negative and non-decreasing (job " + std::to_string(j) + ")");
+    }
+    // the session's rule, round by round: the free slots, lowest first, take the jobs that have arrived, oldest first.  (The session's
+    // round counter advances only with a round that runs; an arrival later than the round at which every slot has gone idle is taken at
+    // its own round here.)
+    std::vector<int64_t> free_at(n_slots, 0);      // the round from which the slot is free
+    int next = 0;
+    int64_t r = 0, last = 0;
+    while (next < n_jobs) {
+        if (last <= r && arrive_round && arrive_round[next] > r) r = arrive_round[next];      // every slot idle: on to the next arrival
+        for (int s = 0; s < n_slots && next < n_jobs; ++s) {
+            if (free_at[s] > r) continue;
+            if ((arrive_round ? arrive_round[next] : 0) > r) break;
+            if (r + K[next] > 0x7fffffff) return fail(DSG_E_INVALID, "dsg_queue_place: more than 2^31 - 1 rounds");
+            slot[next] = s; first_round[next] = (int32_t)r; free_at[s] = r + K[next]; last = std::max(last, free_at[s]); ++next;
+        }
+        ++r;
+    }
+    *n_rounds = (int32_t)last;
+    return 0;
+}
+
+extern "C" int dsg_queue_open(dsg_handle** hs, int n, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift,
+                              int keep_last_tail, dsg_queue** out) {
+    if (!hs || !args || !out || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: bad argument");
+    if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
+    CHK(clip_queue_check_lanes(hs, n, B, guided, args));
+    if (args->skip_timesteps < 0 || args->skip_timesteps >= hs[0]->sched.n)
+        return fail(DSG_E_INVALID, "dsg_sample_clip_queue: skip_timesteps out of range: args has skip_timesteps " + std::to_string(args->skip_timesteps) +
+                                   " outside [0, " + std::to_string(hs[0]->sched.n - 1) + "]");
+    HIPCHK(hipSetDevice(hs[0]->cfg.device));
+    const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J, Ta = hs[0]->Ta, As = hs[0]->As, sdi = hs[0]->cfg.style_dim_in;
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        for (int k = 0; k < 2; ++k)
+            if (!h->clip_tail[k]) CHK(dalloc(h, &h->clip_tail[k], (size_t)h->Bmax * J * S));
+        if (!h->q_style) CHK(dalloc(h, &h->q_style, (size_t)h->Bmax * sdi));
+        if (!h->q_audio) CHK(dalloc(h, &h->q_audio, (size_t)h->Bmax * Ta * As));
+        if (!h->q_slots) CHK(dalloc(h, &h->q_slots, (size_t)h->Bmax));
+        if (!h->q_edits) CHK(dalloc(h, &h->q_edits, (size_t)h->Bmax));
+        if (!h->q_gather) CHK(dalloc(h, &h->q_gather, (size_t)h->Bmax));
+    }
+    dsg_queue* q = new dsg_queue();
+    q->hs.assign(hs, hs + n);
+    q->n = n; q->B = B; q->guided = guided ? 1 : 0; q->root_shift = root_shift ? 1 : 0; q->keep_last_tail = keep_last_tail ? 1 : 0;
+    q->args = *args;
+    q->slot_job.assign((size_t)n * B, -1);
+    if (mask_local) {
+        if (hipMalloc((void**)&q->mask_d, (size_t)T) != hipSuccess) { (void)hipGetLastError(); delete q; return fail(DSG_E_RUNTIME, "dsg_queue_open: out of device memory"); }
+        const hipError_t e = hipMemcpy(q->mask_d, mask_local, (size_t)T, is_device_ptr(mask_local) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(q->mask_d); delete q; HIPCHK(e); }
+    }
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        h->q_slots_host.assign(B, HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0});
+        h->q_gather_host.assign(B, GatherSlot{nullptr, nullptr, nullptr, nullptr, 0, 0});
+        h->q_scale_host.assign(B, 1.f);
+        h->draw_offs.assign(B, 0u); h->draw_starts.assign(B, 0u); h->draw_holds.assign(B, 0);
+        h->lanes_now = n; h->clip_ms = 0.0;
+        h->owner = q;
+    }
+    *out = q;
+    return 0;
+}
+
+extern "C" int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg_clip_edit* edit, int skip_timesteps, int64_t* ticket, void* stream) {
+    if (!q || !job || !ticket) return fail(DSG_E_INVALID, "dsg_queue_submit: null argument");
+    dsg_handle* h0 = q->hs[0];
+    const int64_t t = (int64_t)q->jobs.size();
+    CHK(clip_queue_check_job(*job, edit, t, h0->cfg.variant == 5));
+    const int n_sched = h0->sched.n, skip = skip_timesteps >= 0 ? skip_timesteps : q->args.skip_timesteps;
+    if (skip < 0 || skip >= n_sched)
+        return fail(DSG_E_INVALID, "dsg_sample_clip_queue: skip_timesteps out of range: job " + std::to_string(t) + " has skip_timesteps " + std::to_string(skip) +
+                                   " outside [0, " + std::to_string(n_sched - 1) + "]");
+    const int T = h0->T, S = h0->S, J = h0->J, keep = T - S;
+    const size_t n_tail = (size_t)J * S, n_audio = (size_t)h0->Ta * h0->As;
+    if ((int64_t)job->K * keep > 0x7fffffff) return fail(DSG_E_INVALID, "dsg_queue_submit: job " + std::to_string(t) + " has more than 2^31 - 1 rows");
+    HIPCHK(hipSetDevice(h0->cfg.device));
+    QJob jb;
+    jb.job = *job;
+    jb.n_out = job->K * keep - (q->keep_last_tail ? 0 : S);
+    jb.skip = skip; jb.n_run = n_sched - skip;
+    const size_t n_clip = (size_t)jb.n_out * J;
+    jb.ed = EditSlot{nullptr, nullptr, nullptr, jb.n_out, 0, 0.f, 0.f, 0, 0};
+    // a recycled block may still be read by a round in flight on some lane (HIP launches return early): the lanes are drained before the
+    // first host tensor is written over one.  They are idle whenever the step loop went through the AQL queues, so this waits for nothing
+    bool drained = false;
+    auto staged = [&](const void* src, size_t bytes, const void** dst) -> int {
+        if (!src || is_device_ptr(src)) { *dst = src; return 0; }
+        if (!drained) { for (dsg_handle* h : q->hs) HIPCHK(hipStreamSynchronize(h->stream)); drained = true; }
+        void* p = nullptr;
+        CHK(queue_take(q, bytes, jb, &p));
+        HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, h0->stream));
+        *dst = p;
+        return 0;
+    };
+    int rc = 0;
+    if (!rc) rc = staged(job->style, (size_t)h0->cfg.style_dim_in * sizeof(float), (const void**)&jb.job.style);
+    if (!rc) rc = staged(job->seed0, n_tail * sizeof(float), (const void**)&jb.job.seed0);
+    if (!rc) rc = staged(job->seed_last, n_tail * sizeof(float), (const void**)&jb.job.seed_last);
+    if (!rc) rc = staged(job->audio, (size_t)job->K * n_audio * sizeof(float), (const void**)&jb.job.audio);
+    if (!rc && edit) {
+        rc = staged(edit->inp_motion, n_clip * sizeof(float), (const void**)&jb.ed.motion);
+        if (!rc) rc = staged(edit->init_motion, n_clip * sizeof(float), (const void**)&jb.ed.init);
+        if (!rc) rc = staged(edit->inp_mask, n_clip, (const void**)&jb.ed.mask);
+    }
+    if (!rc) {
+        if (is_device_ptr(job->out)) jb.clip = job->out;
+        else {
+            void* p = nullptr;
+            rc = queue_take(q, n_clip * sizeof(float), jb, &p);
+            jb.clip = (float*)p; jb.host_out = job->out;
+        }
+    }
+    // the caller's host buffers are free on return: the copies above have landed
+    if (!rc && drained && hipStreamSynchronize(h0->stream) != hipSuccess) { (void)hipGetLastError(); rc = fail(DSG_E_RUNTIME, "dsg_queue_submit: staging copy failed"); }
+    if (rc) { queue_give(q, jb); return rc; }      // the session is as it was (the blocks taken so far wait in its free list)
+    // device tensors of the job are read where they are: whatever `stream` still does to them comes first on every lane
+    for (dsg_handle* h : q->hs) CHK(order_after(h, stream));
+    q->jobs.push_back(std::move(jb));
+    *ticket = t;
+    return 0;
+}
+
+static int launch_gather_q(dsg_handle* h, int B) {
+    GatherQArgs a;
+    a.slots = h->q_gather; a.q_style = h->q_style; a.q_audio = h->q_audio; a.c_seed = h->c_seed; a.c_seed_last = h->c_seed_last;
+    a.B = B; a.sdi = h->cfg.style_dim_in; a.n_audio = h->Ta * h->As; a.n_seed = h->J * h->S; a.variant5 = h->cfg.variant == 5 ? 1 : 0;
+    const size_t n = (size_t)B * ((a.sdi + 3) / 4 + (a.n_audio + 3) / 4 + (size_t)(a.variant5 ? 2 : 1) * ((a.n_seed + 3) / 4));
+    hipLaunchKernelGGL(k_clipq_gather, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void* stream) {
+    if (rounds_run) *rounds_run = 0;
+    if (!q) return fail(DSG_E_INVALID, "dsg_queue_run: null queue");
+    dsg_handle** hs = q->hs.data();
+    const int n = q->n, B = q->B, n_slots = n * B;
+    const int J = hs[0]->J, n_sched = hs[0]->sched.n, variant5 = hs[0]->cfg.variant == 5;
+    const size_t n_audio = (size_t)hs[0]->Ta * hs[0]->As;
+    HIPCHK(hipSetDevice(hs[0]->cfg.device));
+    for (int i = 0; i < n; ++i) { hs[i]->clip_ms = 0.0; CHK(order_after(hs[i], stream)); }
+    auto chain_start = [](const dsg_handle* h, int skip, EditSlot& e) {      // (as in dsg_sample_clip_queue_steps)
+        const int i0 = h->sched.n - skip - 1;
+        e.qa = (float)h->sched.sqrt_ac[i0]; e.qb = (float)h->sched.sqrt_1mac[i0]; e.do_q = skip > 0 ? 1 : 0;
+    };
+    std::vector<SampleJob> sjobs(n);
+    std::vector<dsg_sample_args> wargs(n, q->args);
+    int64_t steps_run = 0;
+    int done = 0;
+    while (max_rounds <= 0 || done < max_rounds) {
+        // placement: the free slots, lowest first, take the pending jobs, oldest ticket first
+        for (int s = 0; s < n_slots; ++s) {
+            if (q->slot_job[s] >= 0) continue;
+            while (q->next_pending < q->jobs.size() && q->jobs[q->next_pending].state != DSG_JOB_PENDING) ++q->next_pending;
+            if (q->next_pending >= q->jobs.size()) break;
+            QJob& jb = q->jobs[q->next_pending];
+            jb.state = DSG_JOB_RUNNING; jb.slot = s; jb.first_round = (int)q->rounds_total;
+            q->slot_job[s] = (int64_t)q->next_pending++;
+        }
+        // the round's first timestep: the smallest skip alive in it, over all lanes
+        int s_r = n_sched;
+        for (int s = 0; s < n_slots; ++s) if (q->slot_job[s] >= 0) s_r = std::min(s_r, q->jobs[q->slot_job[s]].skip);
+        if (s_r == n_sched) break;      // nothing alive, nothing pending
+        const int r = (int)(q->rounds_total & 0x7fffffff);      // (the hand-off uses its parity alone)
+        steps_run += n_sched - s_r;
+        for (int i = 0; i < n; ++i) {
+            dsg_handle* h = hs[i];
+            wargs[i].skip_timesteps = s_r;
+            h->nkeys.assign(4 * (size_t)B, 0u);
+            EditSlot ed_dead = {nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0, 0};      // a dead slot: no edits, hold 0, the round's own start
+            chain_start(h, s_r, ed_dead);
+            h->q_edits_host.assign(B, ed_dead);
+            bool lane_inp = false;
+            for (int b = 0; b < B; ++b) {
+                const int64_t t = q->slot_job[(size_t)b * n + i];      // global slot s: lane s % n, position s / n
+                HandoffSlot& hq = h->q_slots_host[b];
+                h->draw_offs[b] = 0u; h->draw_starts[b] = 0u; h->draw_holds[b] = 0;
+                h->q_gather_host[b] = GatherSlot{nullptr, nullptr, nullptr, nullptr, 0, 0};
+                if (t < 0) { hq = HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0}; continue; }
+                const QJob& jb = q->jobs[t];
+                const dsg_clip_job& cj = jb.job;
+                const int c = jb.windows_done;
+                h->q_gather_host[b] = GatherSlot{cj.style, cj.audio + (size_t)c * n_audio, cj.seed0, cj.seed_last, GQ_LIVE | (c == 0 ? GQ_FIRST : 0), 0};
+                if (c == 0 && variant5) q->seed_last_written = true;
+                h->q_scale_host[b] = cj.scale;
+                h->nkeys[4 * b] = (unsigned)(cj.seed & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(cj.seed >> 32);
+                h->nkeys[4 * b + 2] = (unsigned)(cj.stream_id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(cj.stream_id >> 32);
+                h->draw_holds[b] = jb.skip - s_r;
+                h->draw_starts[b] = (uint32_t)c * (uint32_t)(1 + jb.n_run);
+                h->draw_offs[b] = h->draw_starts[b] - (uint32_t)h->draw_holds[b];
+                hq = HandoffSlot{jb.clip, jb.n_out, c, (c == 0 ? HQ_FIRST : 0) | (c == cj.K - 1 ? HQ_LAST : 0), 0};
+                h->q_edits_host[b] = jb.ed; h->q_edits_host[b].c = c;
+                chain_start(h, jb.skip, h->q_edits_host[b]);
+                lane_inp = lane_inp || jb.ed.mask != nullptr;
+            }
+            if (lane_inp) {      // (each pointer on its own, as dsg_set_inpainting)
+                if (!h->inp32) CHK(dalloc(h, &h->inp32, (size_t)h->Bmax * h->T * h->Jp));
+                if (!h->inp_mask) CHK(dalloc(h, &h->inp_mask, (size_t)h->Bmax * h->T * h->Jp));
+            }
+            h->nkB = B; h->nk_seeds = true; h->draw_offs_on = true;
+            if (variant5) h->seed_last_B = B;
+            // the round's tables, uploaded here: behind the previous round's hand-off on the stream, and in front of the point where
+            // sample_prepare drains the stream -- so the host copies are free to change in the next round
+            HIPCHK(hipMemcpyAsync(h->q_slots, h->q_slots_host.data(), (size_t)B * sizeof(HandoffSlot), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->q_gather, h->q_gather_host.data(), (size_t)B * sizeof(GatherSlot), hipMemcpyHostToDevice, h->stream));
+            CHK(launch_gather_q(h, B));
+            CHK(set_window_cond(h, h->q_style, h->c_seed, h->q_audio, q->mask_d, 1, B, 0, q->guided ? h->q_scale_host.data() : nullptr, stream));
+            HIPCHK(hipMemcpyAsync(h->q_edits, h->q_edits_host.data(), (size_t)B * sizeof(EditSlot), hipMemcpyHostToDevice, h->stream));
+            h->inpB = 0;
+            if (lane_inp) { CHK(launch_clip_inp_window_q(h, B)); h->inpB = B; }
+            h->q_edit_init = true;
+        }
+        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, sjobs[i]));
+        CHK(run_lanes(hs, n, wargs.data(), sjobs.data()));
+        for (int i = 0; i < n; ++i) {
+            dsg_handle* h = hs[i];
+            HIPCHK(hipEventRecord(h->ev_t1, h->stream));
+            if (h->aql_timing) h->clip_ms += h->aql_ms;
+            else {
+                float ms = 0.f;
+                HIPCHK(hipEventSynchronize(h->ev_t1));
+                HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+                h->clip_ms += ms;
+            }
+            CHK(launch_handoff_q(h, B, r, q->root_shift, q->keep_last_tail));
+        }
+        // the round's windows are handed off: the rows that became final go to the callers' host memory, on the stream of the lane that
+        // wrote them; finished jobs leave their slots
+        std::vector<char> copied(n, 0);
+        for (int s = 0; s < n_slots; ++s) {
+            const int64_t t = q->slot_job[s];
+            if (t < 0) continue;
+            QJob& jb = q->jobs[t];
+            ++jb.windows_done;
+            jb.rows_ready = queue_rows_ready(q, jb);
+            if (jb.host_out && jb.rows_ready > jb.rows_copied) {
+                const size_t at = (size_t)jb.rows_copied * J, cnt = (size_t)(jb.rows_ready - jb.rows_copied) * J;
+                HIPCHK(hipMemcpyAsync(jb.host_out + at, jb.clip + at, cnt * sizeof(float), hipMemcpyDeviceToHost, hs[s % n]->stream));
+                jb.rows_copied = jb.rows_ready;
+                copied[s % n] = 1;
+            }
+        }
+        for (int i = 0; i < n; ++i) if (copied[i]) HIPCHK(hipStreamSynchronize(hs[i]->stream));
+        for (int s = 0; s < n_slots; ++s) {
+            const int64_t t = q->slot_job[s];
+            if (t < 0 || q->jobs[t].windows_done < q->jobs[t].job.K) continue;
+            q->jobs[t].state = DSG_JOB_DONE;
+            queue_give(q, q->jobs[t]);
+            q->slot_job[s] = -1;
+        }
+        ++q->rounds_total; ++done;
+    }
+    for (int i = 0; i < n; ++i) {
+        dsg_handle* h = hs[i];
+        if (done > 0) { h->last_steps = (int)steps_run; h->timing_valid = true; h->clip_timing = true; h->last_kset = sjobs[i].c.ks.set; }
+        CHK(order_before(h, stream));
+    }
+    if (rounds_run) *rounds_run = done;
+    return 0;
+}
+
+extern "C" int dsg_queue_job(dsg_queue* q, int64_t ticket, dsg_queue_job_info* info) {
+    if (!q || !info) return fail(DSG_E_INVALID, "dsg_queue_job: null argument");
+    if (ticket < 0 || ticket >= (int64_t)q->jobs.size()) return fail(DSG_E_INVALID, "dsg_queue_job: no such ticket: " + std::to_string(ticket));
+    const QJob& jb = q->jobs[ticket];
+    memset(info, 0, sizeof *info);
+    info->state = jb.state; info->windows_done = jb.windows_done; info->rows_ready = jb.rows_ready; info->slot = jb.slot; info->first_round = jb.first_round;
+    return 0;
+}
+extern "C" int dsg_queue_info(dsg_queue* q, int64_t* rounds_total, int* n_pending, int* n_running) {
+    if (!q) return fail(DSG_E_INVALID, "dsg_queue_info: null queue");
+    int pend = 0, run = 0;
+    for (size_t t = q->next_pending; t < q->jobs.size(); ++t) pend += q->jobs[t].state == DSG_JOB_PENDING;
+    for (int64_t t : q->slot_job) run += t >= 0;
+    if (rounds_total) *rounds_total = q->rounds_total;
+    if (n_pending) *n_pending = pend;
+    if (n_running) *n_running = run;
+    return 0;
+}
+extern "C" int dsg_queue_cancel(dsg_queue* q, int64_t ticket) {
+    if (!q) return fail(DSG_E_INVALID, "dsg_queue_cancel: null queue");
+    if (ticket < 0 || ticket >= (int64_t)q->jobs.size()) return fail(DSG_E_INVALID, "dsg_queue_cancel: no such ticket: " + std::to_string(ticket));
+    QJob& jb = q->jobs[ticket];
+    if (jb.state == DSG_JOB_DONE || jb.state == DSG_JOB_CANCELLED) return 0;      // nothing left to cancel
+    if (jb.state == DSG_JOB_RUNNING) q->slot_job[jb.slot] = -1;                    // dead from the next round on; the rows written so far stay
+    jb.state = DSG_JOB_CANCELLED;
+    queue_give(q, jb);      // (dsg_queue_submit drains the lanes before it writes over a recycled block)
+    return 0;
+}
+extern "C" int dsg_queue_close(dsg_queue* q) {
+    if (!q) return 0;
+    (void)hipSetDevice(q->hs[0]->cfg.device);
+    for (dsg_handle* h : q->hs) {
+        (void)hipStreamSynchronize(h->stream);
+        // as the one-shot call leaves its lanes on every return path
+        h->lanes_now = 1; h->nkB = 0; h->nk_seeds = false; h->nkeys.clear(); h->draw_offs_on = false;
+        h->inpB = 0; h->q_edit_init = false;
+        if (q->seed_last_written) h->seed_last_B = 0;
+        h->owner = nullptr;
+    }
+    for (void* p : q->all_blocks) (void)hipFree(p);
+    if (q->mask_d) (void)hipFree(q->mask_d);
+    delete q;
+    return 0;
 }
 
 extern "C" int dsg_sync(dsg_handle* h) {

@@ -1948,6 +1948,47 @@ __global__ void k_clipq_x_in(const ClipXInQArgs a) {
         clip_x_in_row<P>(a.x, s.init, s.n_out, s.c, s.do_q, s.qa, s.qb, i);
     }
 }
+// The conditioning of one round of a queue session (dsg_queue_run): the inputs of a submitted job are in device memory -- the caller's
+// tensors or the session's staging -- so the round's per-slot style and audio window are gathered here, one launch per lane per round, in
+// place of the 2 B small copies per lane the one-shot queue call issues from the caller's memory.  Per slot from a table in device memory
+// (uploaded where the hand-off table goes up): style [sdi], the audio of the window the slot stands on [n_audio = T_a * A_src], and on a
+// clip's first window y['seed'] of window 0 [n_seed = J * S] (null: zeros) and, variant 5, y['seed_last'].  Written: q_style [B][sdi],
+// q_audio [B][n_audio], c_seed [B][n_seed], c_seed_last [B][n_seed] -- what set_window_cond then reads.  A dead slot copies nothing; a slot
+// past its first window leaves c_seed alone (the hand-off wrote it).  One thread per 16-byte quad; a caller's device tensor may sit on any
+// 4-byte boundary and sdi / n_seed are no multiples of 4 in the product models, so source and destination are each accessed as 16 bytes
+// where their address allows and as scalars elsewhere (clip_inp_load4 / handoff_store4).  A pure copy: no bits change.
+struct GatherSlot {
+    const float* style; const float* audio;      // [sdi], [n_audio] of the window the slot stands on
+    const float* seed0; const float* seed_last;  // [n_seed] each; read on the first window only; seed0 null: zeros
+    int flags, pad_;                             // GQ_LIVE | GQ_FIRST
+};
+enum { GQ_LIVE = 1, GQ_FIRST = 2 };
+struct GatherQArgs {
+    const GatherSlot* slots; float* q_style; float* q_audio; float* c_seed; float* c_seed_last;
+    int B, sdi, n_audio, n_seed, variant5;
+};
+__device__ __forceinline__ void gather_quad(float* dst, const float* src, int at, int n) {      // quad `at / 4` of a row of n floats
+    const int nv = n - at < 4 ? n - at : 4;
+    const f32x4 v = src ? clip_inp_load4(src + at, nv) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    handoff_store4(dst + at, v, nv);
+}
+__global__ void k_clipq_gather(const GatherQArgs a) {
+    const int qs = (a.sdi + 3) / 4, qa = (a.n_audio + 3) / 4, qd = (a.n_seed + 3) / 4;
+    const size_t per = (size_t)qs + qa + qd + (a.variant5 ? qd : 0), n = (size_t)a.B * per;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int b = (int)(i / per);
+        int k = (int)(i % per);
+        const GatherSlot s = a.slots[b];
+        if (!(s.flags & GQ_LIVE)) continue;
+        if (k < qs) { gather_quad(a.q_style + (size_t)b * a.sdi, s.style, 4 * k, a.sdi); continue; }
+        k -= qs;
+        if (k < qa) { gather_quad(a.q_audio + (size_t)b * a.n_audio, s.audio, 4 * k, a.n_audio); continue; }
+        k -= qa;
+        if (!(s.flags & GQ_FIRST)) continue;
+        if (k < qd) { gather_quad(a.c_seed + (size_t)b * a.n_seed, s.seed0, 4 * k, a.n_seed); continue; }
+        gather_quad(a.c_seed_last + (size_t)b * a.n_seed, s.seed_last, 4 * (k - qd), a.n_seed);
+    }
+}
 // Self-check of the fence-free hand-off (dsg_hip.cpp: uc_selfcheck): `buf` is uncached device memory; the two kernels run as
 // dependent AQL packets WITHOUT acquire / release, 64 times over.  Writer workgroup b fills chunk b with a pattern of the
 // iteration; reader workgroup b verifies chunk b + 1 -- written on another XCD -- and counts stale words.  The iteration

@@ -546,6 +546,44 @@ class DSGDiffusion:
         return outs
 
     # ---- clips of different lengths over one batch of slots (dsg_sample_clip_queue) ------------------------------------------
+    def _clip_queue_job(self, cfg, clip, i, job, edit, use_torch, keep_last_tail, who="sample_clip_queue"):
+        """One clip dict of `sample_clip_queue` / `ClipQueue.submit` as the library's dsg_clip_job + dsg_clip_edit (filled in place).  Returns
+        (the host `out` [n_out, J], the buffers that must outlive the call, whether the clip has an edit)."""
+        from .model import _mask_bytes
+        S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
+        edit_keys = ("inpainting_mask", "inpainted_motion", "init_motion")
+        feats = list(clip["feats"])
+        if not feats:
+            raise ValueError(f"{who}: a clip without windows")
+        if use_torch:
+            import torch
+            audio = L.Buf(torch.stack([f.float().reshape(cfg.audio_frames, cfg.audio_src_dim) for f in feats]))
+        else:
+            audio = L.Buf(np.stack([np.asarray(f, np.float32).reshape(cfg.audio_frames, cfg.audio_src_dim) for f in feats]))
+        style = L.Buf(clip["style"])
+        if int(np.prod(style.obj.shape)) != cfg.style_dim_in:
+            raise ValueError(f"style shape {tuple(style.obj.shape)}")
+        seed0, last = L.Buf(clip.get("seed0")), L.Buf(clip.get("seed_last"))
+        for name, b in (("seed0", seed0), ("seed_last", last)):
+            if b.obj is not None and int(np.prod(b.obj.shape)) != J * S:
+                raise ValueError(f"{name} shape {tuple(b.obj.shape)}")
+        st = clip.get("stream", 0)
+        sd, sid = (st if isinstance(st, (tuple, list)) else (self._seed, st))
+        K = len(feats)
+        out = np.empty((K * (T - S) - (0 if keep_last_tail else S), J), np.float32)
+        job.style, job.seed0, job.seed_last, job.audio, job.out = style.ptr, seed0.ptr, last.ptr, audio.ptr, out.ctypes.data
+        job.K, job.scale = K, float(1.0 if clip.get("scale") is None else clip["scale"])
+        job.seed, job.stream_id = int(sd) & _U64, int(sid) & _U64
+        mk, mo, init = (clip.get(k) for k in edit_keys)
+        if (mk is None) != (mo is None):
+            raise ValueError(f"{who}: clip {i}: inpainting_mask and inpainted_motion go together")
+        bufs = [L.Buf(None if mk is None else _mask_bytes(mk), "uint8"), L.Buf(mo), L.Buf(init)]
+        for name, b in zip(edit_keys, bufs):
+            if b.obj is not None and tuple(b.obj.shape) not in (out.shape, (1,) + out.shape):
+                raise ValueError(f"{who}: clip {i}: {name} shape {tuple(b.obj.shape)} != {out.shape}")
+        edit.inp_mask, edit.inp_motion, edit.init_motion = (b.ptr for b in bufs)
+        return out, [audio, style, seed0, last] + bufs, any(b.obj is not None for b in bufs)
+
     def sample_clip_queue(self, lanes, clips, B, *, root_shift, keep_last_tail, ddim=False, eta=0.0, skip_timesteps=0, clip_denoised=False,
                           guided=False, mask_local="ones"):
         """N clips of their own lengths over `lanes` x `B` slots in ONE library call: a slot is refilled when its clip ends
@@ -596,44 +634,13 @@ class DSGDiffusion:
         if mbuf.obj is not None and int(np.prod(mbuf.obj.shape)) != T:
             raise ValueError(f"sample_clip_queue: mask_local is one mask of {T} entries, shared by every slot")
         jobs = (L.dsg_clip_job * len(clips))()
-        from .model import _mask_bytes
         edits, edited = (L.dsg_clip_edit * len(clips))(), False
         keep, outs = [mbuf], []
         for i, (job, edit, clip) in enumerate(zip(jobs, edits, clips)):
-            feats = list(clip["feats"])
-            if not feats:
-                raise ValueError("sample_clip_queue: a clip without windows")
-            if use_torch:
-                import torch
-                audio = L.Buf(torch.stack([f.float().reshape(cfg.audio_frames, cfg.audio_src_dim) for f in feats]))
-            else:
-                audio = L.Buf(np.stack([np.asarray(f, np.float32).reshape(cfg.audio_frames, cfg.audio_src_dim) for f in feats]))
-            style = L.Buf(clip["style"])
-            if int(np.prod(style.obj.shape)) != cfg.style_dim_in:
-                raise ValueError(f"style shape {tuple(style.obj.shape)}")
-            seed0, last = L.Buf(clip.get("seed0")), L.Buf(clip.get("seed_last"))
-            for name, b in (("seed0", seed0), ("seed_last", last)):
-                if b.obj is not None and int(np.prod(b.obj.shape)) != J * S:
-                    raise ValueError(f"{name} shape {tuple(b.obj.shape)}")
-            st = clip.get("stream", 0)
-            sd, sid = (st if isinstance(st, (tuple, list)) else (self._seed, st))
-            K = len(feats)
-            out = np.empty((K * (T - S) - (0 if keep_last_tail else S), J), np.float32)
-            job.style, job.seed0, job.seed_last, job.audio, job.out = style.ptr, seed0.ptr, last.ptr, audio.ptr, out.ctypes.data
-            job.K, job.scale = K, float(1.0 if clip.get("scale") is None else clip["scale"])
-            job.seed, job.stream_id = int(sd) & _U64, int(sid) & _U64
-            keep += [audio, style, seed0, last]
-            outs.append(out)
-            mk, mo, init = (clip.get(k) for k in edit_keys)
-            if (mk is None) != (mo is None):
-                raise ValueError(f"sample_clip_queue: clip {i}: inpainting_mask and inpainted_motion go together")
-            bufs = [L.Buf(None if mk is None else _mask_bytes(mk), "uint8"), L.Buf(mo), L.Buf(init)]
-            for name, b in zip(edit_keys, bufs):
-                if b.obj is not None and tuple(b.obj.shape) not in (out.shape, (1,) + out.shape):
-                    raise ValueError(f"sample_clip_queue: clip {i}: {name} shape {tuple(b.obj.shape)} != {out.shape}")
-            edit.inp_mask, edit.inp_motion, edit.init_motion = (b.ptr for b in bufs)
-            edited = edited or any(b.obj is not None for b in bufs)
+            out, bufs, has_edit = self._clip_queue_job(cfg, clip, i, job, edit, use_torch, keep_last_tail)
+            edited = edited or has_edit
             keep += bufs
+            outs.append(out)
         for m in inners:
             m.set_schedule(self)
         a = L.dsg_sample_args()
@@ -653,6 +660,16 @@ class DSGDiffusion:
         self._draw += max(int(j.K) * (1 + self.num_timesteps - sk) for j, sk in zip(jobs, skips))
         self._last_model = inners[0]
         return outs
+
+    def open_clip_queue(self, lanes, B, *, root_shift, keep_last_tail, ddim=False, eta=0.0, skip_timesteps=0, clip_denoised=False, guided=False,
+                        mask_local="ones"):
+        """The clip queue as a session (dsg_queue_*): a `ClipQueue` over `lanes` x `B` slots that takes clips while it runs and hands their
+        rows back window by window.  The arguments are those of `sample_clip_queue` without the clips; `guided` is fixed for the session,
+        every clip runs at its own "scale".  Use it as a context manager: the lanes belong to the session until it is closed.  Every clip
+        is bit for bit `sample_clip` of that clip alone, whenever it was submitted.  `draw_base` is this diffusion's counter at open; at
+        close the counter advances by the largest K * (1 + n_run) submitted, as the longest clip alone would advance it."""
+        return ClipQueue(self, lanes, B, root_shift=root_shift, keep_last_tail=keep_last_tail, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
+                         clip_denoised=clip_denoised, guided=guided, mask_local=mask_local)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
@@ -802,6 +819,145 @@ class DSGDiffusion:
 
 
 _INPAINT_KEYS = ("inpainting_mask", "inpainted_motion")
+
+
+class ClipQueue:
+    """A queue session (`DSGDiffusion.open_clip_queue`; dsg_queue_* of include/dsg.h).  `submit` a clip dict at any time, `run` rounds,
+    read `rows(ticket)` as windows finish, `result(ticket)` when the clip is done.  Host tensors of a clip are copied by `submit`; device
+    tensors must stay valid until the clip is done or cancelled (the session keeps a reference).  Not thread safe: submit and run from
+    one thread.  Placement is first come, first served (`lib.queue_place`)."""
+
+    def __init__(self, diffusion, lanes, B, *, root_shift, keep_last_tail, ddim, eta, skip_timesteps, clip_denoised, guided, mask_local):
+        lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
+        if not lanes:
+            raise ValueError("open_clip_queue: at least one lane")
+        self._handle = None
+        self.lanes = []
+        for m in lanes:
+            inner, _ = diffusion._library_model(m, None)
+            if inner is None:
+                raise TypeError("open_clip_queue drives library denoisers (DSGDenoiser lanes)")
+            self.lanes.append(inner)
+        self.diffusion, self.cfg, self.B, self.keep_last_tail = diffusion, self.lanes[0].cfg, int(B), bool(keep_last_tail)
+        self.lib = self.lanes[0].lib
+        T = self.cfg.n_poses
+        if isinstance(mask_local, str):
+            mask_local = np.ones((T,), np.uint8)
+        mbuf = L.Buf(mask_local, "uint8") if mask_local is not None else L.Buf(None)
+        if mbuf.obj is not None and int(np.prod(mbuf.obj.shape)) != T:
+            raise ValueError(f"open_clip_queue: mask_local is one mask of {T} entries, shared by every slot")
+        for m in self.lanes:
+            m.set_schedule(diffusion)
+        a = L.dsg_sample_args()
+        a.mode, a.skip_timesteps, a.eta = (L.MODE_DDIM if ddim else L.MODE_DDPM), int(skip_timesteps), float(eta)
+        a.seed, a.stream_id, a.draw_base = int(diffusion._seed) & _U64, 0, diffusion._draw
+        a.clip_denoised = int(bool(clip_denoised))
+        self.skip_timesteps = int(skip_timesteps)
+        self._seed = diffusion._seed
+        self._advance = 0
+        self._outs, self._keep = [], {}
+        hs = (C.c_void_p * len(self.lanes))(*[m.handle for m in self.lanes])
+        q = C.c_void_p()
+        self.lib.check(self.lib.cdll.dsg_queue_open(hs, len(self.lanes), self.B, mbuf.p, int(bool(guided)), C.byref(a), int(bool(root_shift)),
+                                                    int(self.keep_last_tail), C.byref(q)))
+        self._handle = q
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _q(self):
+        if self._handle is None:
+            raise L.DSGError("the clip queue is closed")
+        return self._handle
+
+    def submit(self, clip, out=None) -> int:
+        """One clip dict as `sample_clip_queue` takes it, "skip_timesteps" and the edit keys included.  Returns its ticket (0, 1, ...).
+        `out`: the caller's own C-contiguous float32 numpy array [n_out, J] to receive the clip (a playback buffer); rows past
+        `rows_ready` are never touched.  Default: an array of the session's."""
+        q, d = self._q(), self.diffusion
+        i = len(self._outs)
+        sk = clip.get("skip_timesteps")
+        if sk is not None and not 0 <= int(sk) < d.num_timesteps:
+            raise ValueError(f"ClipQueue.submit: clip {i}: skip_timesteps {int(sk)} outside [0, {d.num_timesteps - 1}]")
+        tensors = [clip["feats"][0] if len(clip["feats"]) else None] + [clip.get(k) for k in ("inpainting_mask", "inpainted_motion", "init_motion")]
+        use_torch = L.is_torch(tensors[0])
+        stream = L.current_stream_ptr() if any(L.is_torch(t) for t in tensors) else None
+        job, edit = L.dsg_clip_job(), L.dsg_clip_edit()
+        seed_was, d._seed = d._seed, self._seed          # (a bare stream id keeps the seed the session was opened under)
+        try:
+            own, bufs, has_edit = d._clip_queue_job(self.cfg, clip, i, job, edit, use_torch, self.keep_last_tail, who="ClipQueue.submit")
+        finally:
+            d._seed = seed_was
+        if out is not None:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == own.shape):
+                raise ValueError(f"ClipQueue.submit: clip {i}: out must be a C-contiguous float32 array of shape {own.shape}")
+            job.out = out.ctypes.data
+        else:
+            out = own
+        ticket = C.c_int64(-1)
+        self.lib.check(self.lib.cdll.dsg_queue_submit(q, C.byref(job), C.byref(edit) if has_edit else None, -1 if sk is None else int(sk),
+                                                      C.byref(ticket), stream))
+        assert ticket.value == i
+        self._outs.append(out)
+        dev = [b for b in bufs if b.obj is not None and L.is_torch(b.obj) and b.obj.is_cuda]
+        if dev:
+            self._keep[i] = dev                          # device tensors are read where they are, until the clip is done or cancelled
+        skip = self.skip_timesteps if sk is None else int(sk)
+        self._advance = max(self._advance, int(job.K) * (1 + d.num_timesteps - skip))
+        return i
+
+    def run(self, max_rounds=1) -> int:
+        """Up to `max_rounds` rounds (0: until nothing is alive or pending); returns the rounds run."""
+        n = C.c_int(0)
+        stream = L.current_stream_ptr() if self._keep else None
+        self.lib.check(self.lib.cdll.dsg_queue_run(self._q(), int(max_rounds), C.byref(n), stream))
+        self.diffusion._last_model = self.lanes[0]
+        for t in [t for t in self._keep if self.job(t)["state"] in (L.JOB_DONE, L.JOB_CANCELLED)]:
+            del self._keep[t]
+        return int(n.value)
+
+    def job(self, ticket) -> dict:
+        """{"state", "windows_done", "rows_ready", "slot", "first_round"} of a ticket (state: lib.JOB_*)."""
+        info = L.dsg_queue_job_info()
+        self.lib.check(self.lib.cdll.dsg_queue_job(self._q(), int(ticket), C.byref(info)))
+        return {k: int(getattr(info, k)) for k in ("state", "windows_done", "rows_ready", "slot", "first_round")}
+
+    def info(self) -> dict:
+        r, p, n = C.c_int64(0), C.c_int(0), C.c_int(0)
+        self.lib.check(self.lib.cdll.dsg_queue_info(self._q(), C.byref(r), C.byref(p), C.byref(n)))
+        return {"rounds_total": int(r.value), "n_pending": int(p.value), "n_running": int(n.value)}
+
+    def rows(self, ticket):
+        """The [rows_ready, J] view of the clip's result: the rows that are final so far."""
+        return self._outs[int(ticket)][:self.job(ticket)["rows_ready"]]
+
+    def result(self, ticket):
+        """The whole clip [n_out, J]; raises unless the job is done."""
+        st = self.job(ticket)["state"]
+        if st != L.JOB_DONE:
+            raise L.DSGError(f"ClipQueue.result: ticket {int(ticket)} is not done (state {st})")
+        return self._outs[int(ticket)]
+
+    def cancel(self, ticket):
+        self.lib.check(self.lib.cdll.dsg_queue_cancel(self._q(), int(ticket)))
+        self._keep.pop(int(ticket), None)
+
+    def close(self):
+        if self._handle is None:
+            return
+        q, self._handle = self._handle, None
+        self.lib.check(self.lib.cdll.dsg_queue_close(q))
+        self._keep.clear()
+        self.diffusion._draw += self._advance
 
 
 def _inpaint_mask(mask):

@@ -47,6 +47,14 @@ class dsg_clip_edit(C.Structure):
     _fields_ = [("inp_mask", C.c_void_p), ("inp_motion", C.c_void_p), ("init_motion", C.c_void_p), ("reserved", C.c_int32 * 2)]
 
 
+class dsg_queue_job_info(C.Structure):
+    """The state of one ticket of a queue session (dsg_queue_job, include/dsg.h)."""
+    _fields_ = [("state", C.c_int32), ("windows_done", C.c_int32), ("rows_ready", C.c_int32), ("slot", C.c_int32), ("first_round", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+JOB_PENDING, JOB_RUNNING, JOB_DONE, JOB_CANCELLED = 0, 1, 2, 3          # DSG_JOB_* of include/dsg.h
+
 # every symbol include/dsg.h declares: name -> (restype, argtypes)
 _P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
 SYMBOLS = {
@@ -79,6 +87,14 @@ SYMBOLS = {
     "dsg_sample_clip_queue_steps": (_I, [C.POINTER(_P), _I, C.POINTER(dsg_clip_job), C.POINTER(dsg_clip_edit), _P, _I, _I, _P, _I,
                                          C.POINTER(dsg_sample_args), _I, _I, _P]),
     "dsg_clip_queue_plan_steps": (_I, [_P, _P, _I, _I, _P, _P, C.POINTER(C.c_int32), C.POINTER(_I64)]),
+    "dsg_queue_open": (_I, [C.POINTER(_P), _I, _I, _P, _I, C.POINTER(dsg_sample_args), _I, _I, C.POINTER(_P)]),
+    "dsg_queue_submit": (_I, [_P, C.POINTER(dsg_clip_job), C.POINTER(dsg_clip_edit), _I, C.POINTER(_I64), _P]),
+    "dsg_queue_run": (_I, [_P, _I, C.POINTER(_I), _P]),
+    "dsg_queue_job": (_I, [_P, _I64, C.POINTER(dsg_queue_job_info)]),
+    "dsg_queue_info": (_I, [_P, C.POINTER(_I64), C.POINTER(_I), C.POINTER(_I)]),
+    "dsg_queue_cancel": (_I, [_P, _I64]),
+    "dsg_queue_close": (_I, [_P]),
+    "dsg_queue_place": (_I, [_P, _P, _I, _I, _P, _P, C.POINTER(C.c_int32)]),
     "dsg_set_kernel_set": (_I, [_P, _I]),
     "dsg_get_kernel_set": (_I, [_P, C.POINTER(_I)]),
     "dsg_recommend_kernel_set": (_I, [_P, _I, _I, C.POINTER(_I)]),
@@ -161,6 +177,21 @@ def clip_queue_plan(K, n_slots: int, library: "DSGLibrary | None" = None, n_run=
                                                      C.byref(n_rounds), C.byref(total)))
         return slot.tolist(), first.tolist(), int(n_rounds.value), int(total.value)
     lib.check(lib.cdll.dsg_clip_queue_plan(k.ctypes.data, len(k), int(n_slots), slot.ctypes.data, first.ctypes.data, C.byref(n_rounds)))
+    return slot.tolist(), first.tolist(), int(n_rounds.value)
+
+
+def queue_place(K, n_slots: int, arrive_round=None, library: "DSGLibrary | None" = None):
+    """dsg_queue_place: the placement a queue session follows (host only) -- at the start of every round the free slots, lowest first, take
+    the pending jobs, oldest ticket first.  `arrive_round[j]`: the session round before which job j is submitted (non-decreasing; None:
+    all 0).  Returns (slot[j], first_round[j], n_rounds)."""
+    lib = library or default_library()
+    k = np.ascontiguousarray(K, dtype=np.int32)
+    arr = None if arrive_round is None else np.ascontiguousarray(arrive_round, dtype=np.int32)
+    if arr is not None and arr.shape != k.shape:
+        raise ValueError(f"queue_place: arrive_round has {arr.size} entries for {k.size} jobs")
+    slot, first, n_rounds = np.zeros(len(k), np.int32), np.zeros(len(k), np.int32), C.c_int32(0)
+    lib.check(lib.cdll.dsg_queue_place(k.ctypes.data, None if arr is None else arr.ctypes.data, len(k), int(n_slots), slot.ctypes.data,
+                                       first.ctypes.data, C.byref(n_rounds)))
     return slot.tolist(), first.tolist(), int(n_rounds.value)
 
 

@@ -615,6 +615,101 @@ def generate_clip_queue_dsgplus(lanes, diffusion, clips, seed=123456, skip_times
     return [np.ascontiguousarray(q[: int(c["real_n_frames"]), : cfg.njoints // feature_division], dtype=np.float32) for q, c in zip(seqs, clips)]
 
 
+class _ClipQueueSession:
+    """What `open_clip_queue` / `open_clip_queue_dsgplus` return: `DSGDiffusion.open_clip_queue` behind the clip dicts of
+    `generate_clip_queue[_dsgplus]`.  The lanes keep the session's kernel set from open to close (a set cannot change while a session owns
+    the lane); close puts back what they ran before, as `_lane_kernel_sets` does."""
+
+    def __init__(self, lanes, diffusion, dsgplus, seed, skip_timesteps, ddim, eta, kernel_set, B, guided, root_shift, feature_division):
+        from .model import ClassifierFreeSampleModel
+        lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
+        inners = [m.model if isinstance(m, ClassifierFreeSampleModel) else m for m in lanes]
+        guided = bool(guided) or any(isinstance(m, ClassifierFreeSampleModel) for m in lanes)
+        if B is None:
+            B = max(1, min(m.max_batch for m in inners) // (2 if guided else 1))
+        self.cfg, self.dsgplus, self.feature_division, self._real, self._n = inners[0].cfg, dsgplus, feature_division, {}, 0
+        self._sets = _lane_kernel_sets(inners, int(B), kernel_set)
+        self._sets.__enter__()
+        try:
+            diffusion.manual_seed(seed, 0)
+            self.queue = diffusion.open_clip_queue(inners, int(B), root_shift=root_shift, keep_last_tail=dsgplus, ddim=ddim, eta=eta,
+                                                   skip_timesteps=skip_timesteps, guided=guided)
+        except Exception:
+            self._sets.__exit__(None, None, None)
+            raise
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def submit(self, clip) -> int:
+        """One clip dict of `generate_clip_queue` (`generate_clip_queue_dsgplus` for a DSG+ session); "clip_id" defaults to the ticket."""
+        c, cfg = clip, self.cfg
+        style = np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"]
+        job = {"style": style, "scale": c.get("scale"), "stream": _queue_stream(c, self._n), **_queue_edits(c)}
+        if self.dsgplus:
+            use_torch = L.is_torch(c["feats"][0])
+            feats = [f if f.ndim == 3 else f[None] for f in c["feats"]]
+            job["feats"] = [_dsgplus_window_y(cfg, feats, w, None, c["seed_pose"], c.get("seed_last"), use_torch, None)["audio"] for w in range(len(feats))]
+            job["seed0"], job["seed_last"] = c["seed_pose"], c.get("seed_last")
+        else:
+            job["feats"], job["seed0"] = c["feats"], c.get("seed_pose")
+        t = self.queue.submit(job)
+        self._n += 1
+        if self.dsgplus:
+            self._real[t] = int(c["real_n_frames"])
+        return t
+
+    def _crop(self, ticket, q):
+        if not self.dsgplus:
+            return q
+        return np.ascontiguousarray(q[: self._real[int(ticket)], : self.cfg.njoints // self.feature_division], dtype=np.float32)
+
+    def run(self, max_rounds=1) -> int:
+        return self.queue.run(max_rounds)
+
+    def job(self, ticket) -> dict:
+        return self.queue.job(ticket)
+
+    def rows(self, ticket):
+        """the rows that are final so far (DSG+: cropped to the clip's real_n_frames and feature division, as `result`)"""
+        return self._crop(ticket, self.queue.rows(ticket))
+
+    def result(self, ticket):
+        """the finished clip, as `generate_clip_queue[_dsgplus]` returns it; raises unless it is done"""
+        return self._crop(ticket, self.queue.result(ticket))
+
+    def cancel(self, ticket):
+        self.queue.cancel(ticket)
+
+    def close(self):
+        if self._sets is None:
+            return
+        sets, self._sets = self._sets, None
+        try:
+            self.queue.close()
+        finally:
+            sets.__exit__(None, None, None)
+
+
+def open_clip_queue(lanes, diffusion, seed=123456, smoothing=True, skip_timesteps=0, ddim=False, eta=0.0, kernel_set="recommended", *, B=None,
+                    guided=False):
+    """`generate_clip_queue` as a session: submit ZEGGS clip dicts while it runs, collect rows per window (`DSGDiffusion.open_clip_queue`).
+    Returns a context manager with submit / run / job / rows / result / cancel / close.  `guided` is fixed at open (a lane wrapped in
+    ClassifierFreeSampleModel turns it on); B defaults to the lanes' max_batch (halved with guidance).  Clip i is bit for bit
+    `generate_clip(lane of batch 1, ..., windows="library", stream_id=clip_id)` whenever it was submitted."""
+    return _ClipQueueSession(lanes, diffusion, False, seed, skip_timesteps, ddim, eta, kernel_set, B, guided, smoothing, 1)
+
+
+def open_clip_queue_dsgplus(lanes, diffusion, seed=123456, skip_timesteps=0, feature_division=3, ddim=False, eta=0.0, kernel_set="recommended", *,
+                            B=None, guided=False):
+    """`generate_clip_queue_dsgplus` as a session: the windows are built as `_dsgplus_window_y` builds them, `result` / `rows` crop as
+    `_dsgplus_finish` does."""
+    return _ClipQueueSession(lanes, diffusion, True, seed, skip_timesteps, ddim, eta, kernel_set, B, guided, False, feature_division)
+
+
 def window_audio(audio, n_frames, n_poses=88, n_seed=8, sr=16000, fps=20):
     """Audio slices per window with the n_seed-frame left context (sample.py:214-249): zeros for window 0, the
     previous chunk's tail otherwise.  Returns (list of float32 arrays of (n_poses * sr/fps) samples, n_frames)."""

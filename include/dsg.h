@@ -407,6 +407,70 @@ int dsg_sample_clip_queue_steps(dsg_handle** lanes, int n_lanes, const dsg_clip_
                                 int root_shift, int keep_last_tail, void* stream);
 int dsg_clip_queue_plan_steps(const int32_t* K, const int32_t* n_run /* NULL: all equal */, int n_jobs, int n_slots,
                               int32_t* slot, int32_t* first_round, int32_t* n_rounds, int64_t* total_steps /* nullable */);
+/* Clip queue as a session: submit while it runs, collect per window.  dsg_sample_clip_queue[_edit|_steps] take a closed list of jobs and
+ * return when all of them are done; a session (dsg_queue) lives between rounds, so a request that arrives while others run takes the next free
+ * slot, and a clip's rows are in the caller's memory after the round that made them final.  A round is a round of
+ * dsg_sample_clip_queue_steps: it starts from the smallest skip alive, slots with a larger skip hold, dead slots run on the conditioning they
+ * hold and write nothing, job j draws draw_base + c * (1 + n_run_j) for the start of its window c and the following n_run_j for its steps,
+ * edits go through the per-round edit table.  The promise is the queue's: job j comes out bit for bit as dsg_sample_clip produces it alone
+ * -- B = 1, its (seed, stream_id), its skip and edits, the same draw_base, root_shift / keep_last_tail and named kernel set -- whenever it was
+ * submitted, whatever ran beside it, whatever was cancelled.  Reference counterpart: none.
+ * dsg_queue_open: the checks of dsg_sample_clip_queue_steps on lanes, B, guided and args, with the same refusals and messages.  `guided` is
+ * fixed for the session (it decides the batch layout); every job runs at its own `scale`.  args and mask_local (uint8[T], host or device, or
+ * NULL) are copied.  From open to close the lanes belong to the session: dsg_sample*, dsg_forward, the dsg_set_* setters, dsg_load_tensor,
+ * dsg_finalize_weights, dsg_destroy and a second dsg_queue_open on such a handle return DSG_E_STATE ("handle belongs to an open queue");
+ * dsg_clone, dsg_sync, dsg_get_* and dsg_last_* stay usable.  Like a handle, a session is not thread safe: a service calls submit and run
+ * from one thread, alternating.
+ * dsg_queue_submit: the per-job checks of the queue calls; edit nullable; skip_timesteps < 0 reads as args->skip_timesteps.  *ticket counts
+ * from 0 in submission order.  OWNERSHIP: host tensors of the job -- style, seed0, seed_last, the K audio windows, the three edit tensors --
+ * are copied into session-owned device memory before the call returns, so the caller's host buffers are free on return.  Device tensors are
+ * read where they are, behind whatever `stream` has enqueued, and must stay valid until the job is DONE or CANCELLED.  `out` stays the
+ * caller's until then, host or device.  Staging blocks are recycled inside the session and released at close.  An allocation that fails:
+ * DSG_E_RUNTIME, and the session is as it was.
+ * PLACEMENT: at the start of every round the free slots take the pending jobs -- lowest free slot first, oldest ticket first.  Global slot s is
+ * lane s % n_lanes, position s / n_lanes, as in the one-shot call.  First come, first served is deliberate: predictable latency is what a
+ * session is for.  A caller who holds the whole corpus submits it longest first, which reproduces the one-shot plan, or keeps using the
+ * one-shot call.  dsg_queue_place is this rule on the host (no device): arrive_round[j] = the session round before which job j is submitted,
+ * non-negative and non-decreasing, NULL = all 0; slot / first_round / n_rounds as dsg_clip_queue_plan.  DSG_E_INVALID: K < 1, n_jobs < 1,
+ * n_slots < 1, decreasing arrivals.
+ * dsg_queue_run: up to max_rounds rounds (<= 0: until idle); returns early, with *rounds_run (nullable) as counted, when nothing is alive
+ * or pending.  On return rows [0, rows_ready) of every host `out` are in the caller's memory and final; rows past rows_ready are untouched.
+ * rows_ready = min(n_out, windows_done * (T - S) - S), n_out when the job is done: window c leaves rows [c * (T - S) - S, (c + 1) * (T - S) - S)
+ * final, with keep_last_tail as without -- there only the last window writes its closing S frames.
+ * Device `out`s are written by the hand-off itself and ordered before `stream`.  dsg_last_sample_ms on a lane afterwards: the sum over the
+ * rounds of this run call, n_steps their step total.  After an error from run the session is only good for dsg_queue_close.
+ * dsg_queue_job / dsg_queue_info: the state of one ticket / of the session (every pointer of _info nullable).
+ * dsg_queue_cancel: a pending job never runs; a running job's slot is dead from the next round on and the rows written so far stay; no
+ * other job is affected; a job that is done or cancelled already: no-op.
+ * dsg_queue_close: allowed with jobs pending or running, which are abandoned.  The lanes are left as the one-shot call leaves them on every
+ * return path -- unkeyed, no draw offsets or holds, no inpainting, no edit table, one lane; variant 5 asks for dsg_set_seed_last again --
+ * and the staging memory is freed.
+ * On the device: per lane and round one table of {style, audio window c, seed0, seed_last, flags} per slot goes up beside the hand-off's and
+ * k_clipq_gather copies the round's conditioning into the lane's buffers in one launch (the one-shot call issues up to 2 B copies per lane
+ * from the caller's memory); every lane starts every round through k_clipq_x_in, as the one-shot call does with per-job skips.
+ * Added without a version step: dsg_version() stays 330; dsg_clip_job and dsg_clip_edit keep their layouts. */
+typedef struct dsg_queue dsg_queue;
+enum { DSG_JOB_PENDING = 0, DSG_JOB_RUNNING = 1, DSG_JOB_DONE = 2, DSG_JOB_CANCELLED = 3 };
+typedef struct dsg_queue_job_info {
+    int32_t state;         /* DSG_JOB_*                                                   */
+    int32_t windows_done;  /* windows handed off so far                                   */
+    int32_t rows_ready;    /* rows [0, rows_ready) of the job's `out` are final and there */
+    int32_t slot;          /* global slot, -1 while pending                               */
+    int32_t first_round;   /* session round of its window 0, -1 while pending             */
+    int32_t reserved[3];
+} dsg_queue_job_info;
+int dsg_queue_open(dsg_handle** lanes, int n_lanes, int B, const uint8_t* mask_local, int guided,
+                   const dsg_sample_args* args, int root_shift, int keep_last_tail, dsg_queue** out);
+int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg_clip_edit* edit /* nullable */,
+                     int skip_timesteps /* < 0: args->skip_timesteps */, int64_t* ticket, void* stream);
+int dsg_queue_run(dsg_queue* q, int max_rounds /* <= 0: until idle */, int* rounds_run, void* stream);
+int dsg_queue_job(dsg_queue* q, int64_t ticket, dsg_queue_job_info* info);
+int dsg_queue_info(dsg_queue* q, int64_t* rounds_total, int* n_pending, int* n_running);
+int dsg_queue_cancel(dsg_queue* q, int64_t ticket);
+int dsg_queue_close(dsg_queue* q);
+/* host only, no device: exactly the placement the session follows */
+int dsg_queue_place(const int32_t* K, const int32_t* arrive_round, int n_jobs, int n_slots,
+                    int32_t* slot, int32_t* first_round, int32_t* n_rounds);
 /* Per-element noise streams ("keyed noise") for dsg_sample / _multi / dsg_sample_clip / _multi.  seeds, stream_ids: HOST uint64[B], copied by
  * the call.  While set, element b of the batch draws from its own pair (seed_b, sid_b): draw d at frame f, feature j is
  *   philox4x32_10(ctr = ((f * Jq + j) >> 2, d, sid_b lo, sid_b hi), key = (seed_b lo, seed_b hi)) + Box-Muller,   Jq = J rounded up to 4,
