@@ -196,19 +196,19 @@ struct dsg_handle {
     // skip_timesteps (dsg_sample_clip_queue_steps) a slot that starts `hold` loop indices into the round draws its steps at offset - hold
     // (draw_offs) and its start at the offset itself (draw_starts); everywhere else hold is 0 and the two agree
     bool draw_offs_on = false; std::vector<unsigned> draw_offs, draw_starts; std::vector<int> draw_holds;
-    // dsg_sample_clip_queue: the round's per-slot style / audio gathered on the device, the hand-off table (k_window_handoff_q) and the host
-    // copies of what is uploaded per round (they outlive the copies).  Allocated on first use
-    float *q_style = nullptr, *q_audio = nullptr; HandoffSlot* q_slots = nullptr;
-    std::vector<HandoffSlot> q_slots_host; std::vector<float> q_scale_host;
-    // dsg_sample_clip_queue_edit: the round's per-slot edit table (k_clipq_inp_window / k_clipq_x_in) with its host copy, and the staging of
-    // the call's host-side edit tensors (every job this lane runs, all at once; grown when needed, q_stage_cap bytes).  q_edit_init: for the
-    // rounds of a call in which a job of this lane has an init motion, sample_prepare starts the round through k_clipq_x_in
-    EditSlot* q_edits = nullptr; std::vector<EditSlot> q_edits_host; bool q_edit_init = false;
-    unsigned char* q_stage = nullptr; size_t q_stage_cap = 0;
-    // queue session (dsg_queue_open .. dsg_queue_close): the session that owns this lane -- while set, every entry point that samples on the
-    // handle or changes its state is refused (owned_by_queue) -- and the round's gather table (k_clipq_gather) with its host copy
+    // What a lane holds for the rounds of a clip queue (dsg_sample_clip_queue*, dsg_queue_*; QueueRound fills all of it).  The device buffers
+    // are allocated on first use (queue_lane_ready); the *_host vectors are the copies uploaded per round, which outlive the uploads
+    struct Queue {
+        float *style = nullptr, *audio = nullptr;      // the round's per-slot style / audio [Bmax][...]: what set_window_cond reads
+        std::vector<float> scale_host;                 // ... and its per-slot guidance scale
+        HandoffSlot* slots = nullptr; std::vector<HandoffSlot> slots_host;      // the hand-off table (k_window_handoff_q)
+        EditSlot* edits = nullptr; std::vector<EditSlot> edits_host;            // the edit table (k_clipq_inp_window / k_clipq_x_in)
+        bool edit_init = false;                        // for the rounds of a queue only: sample_prepare starts the round through k_clipq_x_in
+        GatherSlot* gather = nullptr; std::vector<GatherSlot> gather_host;      // the gather table of a session (k_clipq_gather)
+        unsigned char* stage = nullptr; size_t stage_cap = 0;      // a one-shot call's host-side edit tensors, staged (grown when needed)
+    } cq;
+    // the queue session that owns this lane (dsg_queue_open .. dsg_queue_close): while set, owned_by_queue refuses every other sampling call
     struct dsg_queue* owner = nullptr;
-    GatherSlot* q_gather = nullptr; std::vector<GatherSlot> q_gather_host;
     int latency_mode = -1;               // dsg_config.latency_mode: -1 auto, 0 never the LATENCY set, 1 always
 #ifndef DSG_EMU
     dsg_aql::Ctx aql;                    // hand-written AQL submission of the step loop (dsg_aql.h)
@@ -2156,12 +2156,12 @@ static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, cons
     HIPCHK(hipGetLastError());
     return 0;
 }
-// a round of dsg_sample_clip_queue_edit on a lane that runs a job with an init motion: init, length and window index per slot (h->q_edits)
+// a round of dsg_sample_clip_queue_edit on a lane that runs a job with an init motion: init, length and window index per slot (h->cq.edits)
 static int launch_clip_x_in_q(dsg_handle* h, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B, const KernelSel& ks) {
     ClipXInQArgs a;
     a.x = clip_x_in_args(h, 0.f, 0.f, nk, keys, offs, draw, B, ks);
     a.x.init = nullptr; a.x.n_out = 0; a.x.c = 0;      // (per slot, from the table, as do_q and the q_sample pair)
-    a.slots = h->q_edits;
+    a.slots = h->cq.edits;
     const size_t n = (size_t)B * h->T * (h->Jp / 4);
     const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
     if (is_bf16(h)) hipLaunchKernelGGL((k_clipq_x_in<PBF16>), dim3(grid), dim3(256), 0, h->stream, a);
@@ -2322,6 +2322,10 @@ extern "C" int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int 
 // indices stay per call (draw_base, draw_base + 1 + i, a clip's window c from draw_base + c (1 + n_run)).  Host arrays, copied here; the
 // table reaches the device with the `dyn` block of every sampling call (sample_prepare).  Reference counterpart: none (th.randn consumes one
 // global generator, gaussian_diffusion.py:704, :542).
+static void set_noise_key(dsg_handle* h, int b, uint64_t seed, uint64_t stream_id) {      // element b's entry of the key table
+    h->nkeys[4 * b] = (unsigned)(seed & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(seed >> 32);
+    h->nkeys[4 * b + 2] = (unsigned)(stream_id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(stream_id >> 32);
+}
 extern "C" int dsg_set_noise_streams(dsg_handle* h, const uint64_t* seeds, const uint64_t* stream_ids, int B) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
     CHK(owned_by_queue(h));
@@ -2329,11 +2333,7 @@ extern "C" int dsg_set_noise_streams(dsg_handle* h, const uint64_t* seeds, const
     if (B < 1 || B > h->Bmax)
         return fail(DSG_E_INVALID, "dsg_set_noise_streams: batch " + std::to_string(B) + " outside 1 .. max_batch (" + std::to_string(h->Bmax) + ")");
     h->nkeys.assign(4 * (size_t)B, 0u);
-    for (int b = 0; b < B; ++b) {
-        const uint64_t sd = seeds ? seeds[b] : 0, id = stream_ids ? stream_ids[b] : 0;
-        h->nkeys[4 * b] = (unsigned)(sd & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(sd >> 32);
-        h->nkeys[4 * b + 2] = (unsigned)(id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(id >> 32);
-    }
+    for (int b = 0; b < B; ++b) set_noise_key(h, b, seeds ? seeds[b] : 0, stream_ids ? stream_ids[b] : 0);
     h->nk_seeds = seeds != nullptr;
     h->nkB = B;
     return 0;
@@ -2555,7 +2555,7 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     }
     const unsigned* keys_d = keyed ? h->dyn + 8 : nullptr;
     const unsigned* offs_d = keyed ? h->dyn + 8 + 6 * (size_t)h->Bmax : nullptr;      // (the start kernels': GemmArgs::draw_off is the pair table)
-    if (h->q_edit_init)           // (a round of the clip queue on a lane that runs a job with an init motion, or of a call with per-clip skips)
+    if (h->cq.edit_init)          // (a round of the clip queue on a lane that runs a job with an init motion, or of a call with per-clip skips)
         CHK(launch_clip_x_in_q(h, nk, keys_d, offs_d, a->draw_base, B, ksel));
     else if (h->clip_init_c >= 0) // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
         CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
@@ -2755,6 +2755,11 @@ extern "C" int dsg_sample(dsg_handle* h, const dsg_sample_args* a, float* out, i
 // queues' dependent packet chains overlap on the GPU); with HIP launches the lanes' streams are fed step by step.  Every lane
 // runs the kernel set ITS handle selects (dsg_set_kernel_set / the batch): the call changes nothing about the arithmetic, so
 // lane i's sample is bit-identical to dsg_sample(lanes[i], &args[i], ...) on its own.
+struct LanesNow {          // how many lanes share the GPU during a call (select_kernels: block shape of k_ffn; never the arithmetic)
+    dsg_handle** hs; int n;
+    LanesNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) hs[i]->lanes_now = n; }
+    ~LanesNow() { for (int i = 0; i < n; ++i) hs[i]->lanes_now = 1; }
+};
 extern "C" int dsg_sample_multi(dsg_handle** hs, int n, const dsg_sample_args* args, float** outs, int B, void* stream) {
     if (!hs || !args || !outs || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_multi: bad argument");
     for (int i = 0; i < n; ++i) {
@@ -2765,11 +2770,7 @@ extern "C" int dsg_sample_multi(dsg_handle** hs, int n, const dsg_sample_args* a
     }
     if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_multi: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
     std::vector<SampleJob> jobs(n);
-    struct LanesNow {          // how many lanes share the GPU during this call (select_kernels: block shape of k_ffn; never the arithmetic)
-        dsg_handle** hs; int n;
-        LanesNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) hs[i]->lanes_now = n; }
-        ~LanesNow() { for (int i = 0; i < n; ++i) hs[i]->lanes_now = 1; }
-    } lanes_now(hs, n);
+    LanesNow lanes_now(hs, n);
     for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &args[i], B, stream, jobs[i]));
     CHK(run_lanes(hs, n, args, jobs.data()));
     for (int i = 0; i < n; ++i) CHK(sample_finish(hs[i], outs[i], stream, jobs[i]));
@@ -2801,6 +2802,26 @@ static int launch_clip_inp_window(dsg_handle* h, int B, int n_out, int c) {
     const size_t n = (size_t)B * h->T * (h->Jp / 4);
     hipLaunchKernelGGL(k_clip_inp_window, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the two copies of the hand-off's tail, on first use: for the window loop below and for the rounds of a queue
+static int clip_tails_ready(dsg_handle* h) {
+    for (int k = 0; k < 2; ++k)
+        if (!h->clip_tail[k]) CHK(dalloc(h, &h->clip_tail[k], (size_t)h->Bmax * h->J * h->S));
+    return 0;
+}
+// The step loop of a window (of a queue's round) has been issued on lane h: its time goes into clip_ms, what dsg_last_sample_ms reports for
+// the call -- the AQL run's host clock, else the events around the loop, waited for here.  The hand-off follows
+static int clip_window_timed(dsg_handle* h) {
+    HIPCHK(hipEventRecord(h->ev_t1, h->stream));
+    if (h->aql_timing) h->clip_ms += h->aql_ms;
+    else {
+        float ms = 0.f;
+        HIPCHK(hipEventSynchronize(h->ev_t1));
+        HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+        h->clip_ms += ms;
+    }
     return 0;
 }
 
@@ -2850,8 +2871,7 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
     std::vector<float*> clip(n);
     for (int i = 0; i < n; ++i) {
         dsg_handle* h = hs[i];
-        for (int k = 0; k < 2; ++k)
-            if (!h->clip_tail[k]) CHK(dalloc(h, &h->clip_tail[k], (size_t)h->Bmax * J * S));
+        CHK(clip_tails_ready(h));
         if (is_device_ptr(outs[i])) clip[i] = outs[i];      // the hand-off writes the caller's tensor itself
         else {
             if (n_clip > h->clip_out_cap) { CHK(dalloc(h, &h->clip_out, n_clip, false)); h->clip_out_cap = n_clip; }
@@ -2865,11 +2885,7 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
     }
     std::vector<SampleJob> jobs(n);
     std::vector<dsg_sample_args> wargs(args, args + n);
-    struct LanesNow {          // (as in dsg_sample_multi)
-        dsg_handle** hs; int n;
-        LanesNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) hs[i]->lanes_now = n; }
-        ~LanesNow() { for (int i = 0; i < n; ++i) hs[i]->lanes_now = 1; }
-    } lanes_now(hs, n);
+    LanesNow lanes_now(hs, n);
     // Lanes with a clip-level constraint: window c's slice goes into inp32 / inp_mask where the window's conditioning is set -- on the handle's
     // stream, which sample_prepare drains before the first packet, whose acquire covers it like the conditioning; the pointers stay, only the
     // contents change -- and the epilogue's inpainting is on (inpB: StepCtx::inpaint, GKey flag 32) for the windows of this call only: every
@@ -2898,16 +2914,8 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
         for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, jobs[i]));
         CHK(run_lanes(hs, n, wargs.data(), jobs.data()));
         for (int i = 0; i < n; ++i) {
-            dsg_handle* h = hs[i];
-            HIPCHK(hipEventRecord(h->ev_t1, h->stream));
-            if (h->aql_timing) h->clip_ms += h->aql_ms;
-            else {
-                float ms = 0.f;
-                HIPCHK(hipEventSynchronize(h->ev_t1));
-                HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
-                h->clip_ms += ms;
-            }
-            CHK(launch_handoff(h, clip[i], B, n_out, c, K, root_shift, keep_last_tail));
+            CHK(clip_window_timed(hs[i]));
+            CHK(launch_handoff(hs[i], clip[i], B, n_out, c, K, root_shift, keep_last_tail));
         }
     }
     for (int i = 0; i < n; ++i) {
@@ -2932,11 +2940,9 @@ extern "C" int dsg_sample_clip_multi(dsg_handle** lanes, int n, const float* con
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// dsg_sample_clip_queue: clips of different lengths over one batch of slots.  The plan (dsg_clip_queue_plan) gives every clip a slot and a
-// first round; a round is one iteration of sample_clip's window loop for every lane at the constant batch B, with per-slot conditioning,
-// per-slot Philox keys and draw offsets (a slot on window c of its clip draws what dsg_sample_clip draws for window c of that clip alone),
-// and the per-slot hand-off (k_window_handoff_q).  A slot without a clip in a round is dead: it runs on whatever conditioning it holds --
-// rows are independent -- and writes nothing.
+// The clip queue: clips of different lengths over one batch of slots, in rounds.  The round is written once (QueueRound, below); the
+// one-shot call (dsg_sample_clip_queue_steps and the two exports in front of it: all jobs known, placed by a plan) and the session
+// (dsg_queue_*: jobs arrive while it runs) each say what the slots run and how the jobs' tensors reach the lanes.
 // ---------------------------------------------------------------------------------------------------------
 // The placement, written once for both exports: jobs in the order n_run descending (where given), K descending, index ascending; each to the
 // slot with the fewest rounds so far, ties to the lowest slot.  `who`: the export's name, for the messages
@@ -2998,7 +3004,7 @@ extern "C" int dsg_clip_queue_plan_steps(const int32_t* K, const int32_t* n_run,
 
 static int launch_clip_inp_window_q(dsg_handle* h, int B) {
     ClipInpQArgs a;
-    a.slots = h->q_edits; a.inp32 = h->inp32; a.inp_mask = h->inp_mask;
+    a.slots = h->cq.edits; a.inp32 = h->inp32; a.inp_mask = h->inp_mask;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S;
     const size_t n = (size_t)B * h->T * (h->Jp / 4);
     hipLaunchKernelGGL(k_clipq_inp_window, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
@@ -3007,7 +3013,7 @@ static int launch_clip_inp_window_q(dsg_handle* h, int B) {
 }
 static int launch_handoff_q(dsg_handle* h, int B, int round, int root_shift, int keep_last_tail) {
     HandoffQArgs a;
-    a.xs32 = h->xs32; a.tail_in = h->clip_tail[(round + 1) & 1]; a.tail_out = h->clip_tail[round & 1]; a.c_seed = h->c_seed; a.slots = h->q_slots;
+    a.xs32 = h->xs32; a.tail_in = h->clip_tail[(round + 1) & 1]; a.tail_out = h->clip_tail[round & 1]; a.c_seed = h->c_seed; a.slots = h->cq.slots;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S;
     a.root_shift = root_shift ? 1 : 0; a.keep_last_tail = keep_last_tail ? 1 : 0;
     const size_t n = (size_t)B * h->T * (h->Jp / 4);
@@ -3054,14 +3060,186 @@ static int clip_queue_check_job(const dsg_clip_job& q, const dsg_clip_edit* edit
     return 0;
 }
 
-// edits: NULL (dsg_sample_clip_queue), or one dsg_clip_edit per job -- the clip's constraint and / or the clip it is re-denoised from, in the
-// coordinates of the job's `out`.  Host tensors are staged on the lane that runs the job before the rounds start; per round the lane's edit
-// table (EditSlot) goes up beside the hand-off's, k_clipq_inp_window cuts the round's constraint for every slot (lanes that run a constrained
-// job: inpB = B for the rounds of this call) and sample_prepare starts the round through k_clipq_x_in (lanes that run a job with an init).
-// skip_timesteps: NULL (dsg_sample_clip_queue_edit), or one entry per job (< 0: args->skip_timesteps).  When an entry differs from the
-// call's, the rounds follow dsg_clip_queue_plan_steps; round r runs from s_r = the smallest skip alive in it, over all lanes, as dsg_sample
-// does with skip_timesteps = s_r; a slot with a larger skip holds for skip - s_r loop indices (DrawOff::hold) and every lane starts every
-// round through k_clipq_x_in, which reads do_q and the q_sample pair of the slot's own first timestep from the edit table
+// What a slot runs in a round: one window of one clip.  A dead slot is the absence of one -- a null pointer in the round's table
+struct SlotWork {
+    dsg_clip_job job;           // the job, its pointers as they are read: the caller's (host or device), or a session's device copies
+    EditSlot ed;                // motion / mask / init as the device reads them and n_out; QueueRound fills in c and the chain's start
+    float* clip = nullptr;      // [ed.n_out][J] on the device: where the hand-off writes
+    int c = 0;                  // the window the slot stands on
+    int skip = 0, n_run = 0;    // the job's skip_timesteps and the steps of one of its windows (schedule length - skip)
+};
+
+// The lane's device buffers for the rounds of a queue, on first use
+enum { QL_EDITS = 1, QL_GATHER = 2, QL_INP = 4 };      // + the edit table, + the gather table, + the epilogue's inpainting buffers
+static int queue_lane_ready(dsg_handle* h, int flags) {
+    dsg_handle::Queue& q = h->cq;
+    CHK(clip_tails_ready(h));
+    if (!q.style) CHK(dalloc(h, &q.style, (size_t)h->Bmax * h->cfg.style_dim_in));
+    if (!q.audio) CHK(dalloc(h, &q.audio, (size_t)h->Bmax * h->Ta * h->As));
+    if (!q.slots) CHK(dalloc(h, &q.slots, (size_t)h->Bmax));
+    if ((flags & QL_EDITS) && !q.edits) CHK(dalloc(h, &q.edits, (size_t)h->Bmax));
+    if ((flags & QL_GATHER) && !q.gather) CHK(dalloc(h, &q.gather, (size_t)h->Bmax));
+    if (flags & QL_INP) {      // (each pointer on its own, as dsg_set_inpainting)
+        if (!h->inp32) CHK(dalloc(h, &h->inp32, (size_t)h->Bmax * h->T * h->Jp));
+        if (!h->inp_mask) CHK(dalloc(h, &h->inp_mask, (size_t)h->Bmax * h->T * h->Jp));
+    }
+    return 0;
+}
+// ... and the lane as a queue found it: what QueueRound sets on a lane -- lanes_now, the keyed table and its draw offsets, the epilogue's
+// inpainting (inpB), the start through the edit table -- is put back.  Every lane came in unkeyed and with inpB == 0
+// (clip_queue_check_lanes).  Variant 5: the rows of c_seed_last now hold the jobs' snippets, so the lane asks for dsg_set_seed_last again,
+// as a fresh handle does
+static void queue_leave_lane(dsg_handle* h, bool seed_last_written) {
+    h->lanes_now = 1; h->nkB = 0; h->nk_seeds = false; h->nkeys.clear(); h->draw_offs_on = false;
+    h->inpB = 0; h->cq.edit_init = false;
+    if (seed_last_written) h->seed_last_B = 0;
+}
+
+// A job's tensor as the device reads it: where it is when that is device memory (or null), else its copy, made on h's stream, in the
+// `bytes` that room(bytes, &p) hands out -- a piece of the lane's staging (the one-shot call) or a block of the session's
+template <class Room>
+static int staged(dsg_handle* h, const void* src, size_t bytes, Room&& room, const void** dst) {
+    if (!src || is_device_ptr(src)) { *dst = src; return 0; }
+    void* p = nullptr;
+    CHK(room(bytes, &p));
+    HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, h->stream));
+    *dst = p;
+    return 0;
+}
+
+// One round of a clip queue, for every lane: one iteration of sample_clip's window loop at the constant batch B, with per-slot
+// conditioning, Philox keys, draw offsets and hand-off.  Written once, under dsg_sample_clip_queue_steps and the session (dsg_queue_run);
+// the callers decide what every slot runs (`slots`), how a lane's conditioning reaches it (`cond`) and which lanes go through the edit
+// table (`lane_inp`, `lane_init`).  Per lane, in stream order: the hand-off table, the conditioning (cond, set_window_cond), the edit table
+// and the round's constraint (k_clipq_inp_window); then sample_prepare for every lane, the step loops (run_lanes), and per lane the timing
+// and the hand-off (k_window_handoff_q).  The tables go up behind the previous round's hand-off on the lane's stream and in front of the
+// point where sample_prepare drains it: their host copies are free to change in the next round.
+// Round r runs from s_r = the smallest skip alive in it, over all lanes, as dsg_sample does with skip_timesteps = s_r; a slot with a larger
+// skip holds for skip - s_r loop indices (DrawOff::hold).  A slot on window c of its clip draws what dsg_sample_clip draws for window c of
+// that clip alone.  A dead slot runs on whatever conditioning it holds -- rows are independent -- and writes nothing
+struct QueueRound {
+    std::vector<dsg_handle*> hs;
+    int B = 0, guided = 0, root_shift = 0, keep_last_tail = 0;
+    const uint8_t* mask = nullptr;      // mask_local (one row), as set_window_cond takes it
+    dsg_sample_args args;               // the queue's own; wargs: per lane, with the round's skip_timesteps (draw_base is the same for every
+    std::vector<dsg_sample_args> wargs; // clip: the windows are told apart by the draw offsets)
+    std::vector<SampleJob> sjobs;
+    int (*cond)(dsg_handle* h, int B, const SlotWork* const* lane) = nullptr;      // the lane's slots -> style / audio / c_seed / c_seed_last
+    // lane_init[i]: lane i starts its rounds through the edit table (k_clipq_x_in), else through k_x_in; lane_inp[i]: the table's constraint is
+    // cut and the epilogue's inpainting is on (inpB).  lane_inp empty: decided per round, by whether a slot of the lane brings a mask
+    std::vector<char> lane_inp, lane_init;
+    bool seed_last_written = false;     // variant 5: some round has put a job's snippet into c_seed_last
+    int64_t steps_run = 0;              // the step-loop length summed over the rounds since the caller last reset it
+    std::vector<const SlotWork*> lane;
+
+    QueueRound(dsg_handle** hs_, int n, int B_, const uint8_t* mask_, int guided_, const dsg_sample_args& a, int root_shift_, int keep_last_tail_)
+        : hs(hs_, hs_ + n), B(B_), guided(guided_ ? 1 : 0), root_shift(root_shift_ ? 1 : 0), keep_last_tail(keep_last_tail_ ? 1 : 0), mask(mask_),
+          args(a), wargs(n, a), sjobs(n), lane_init(n, 0), lane(B_) {
+        for (dsg_handle* h : hs) {
+            h->cq.slots_host.resize(B); h->cq.edits_host.resize(B);
+            h->cq.scale_host.assign(B, 1.f);
+            h->draw_offs.resize(B); h->draw_starts.resize(B); h->draw_holds.resize(B);
+            h->lanes_now = n;
+        }
+    }
+    // in front of the rounds of one call: they follow whatever `stream` still does to the tensors they read
+    int begin(void* stream) {
+        steps_run = 0;
+        for (dsg_handle* h : hs) { h->clip_ms = 0.0; CHK(order_after(h, stream)); }
+        return 0;
+    }
+    int run(const SlotWork* const* slots, int round, void* stream) {      // slots: [B][lanes] (global slot s: lane s % n, position s / n); round: its parity picks the tail
+        const int n = (int)hs.size(), n_sched = hs[0]->sched.n, variant5 = hs[0]->cfg.variant == 5;
+        int s_r = n_sched;      // (the callers run no round without a live slot)
+        for (int s = 0; s < n * B; ++s) if (slots[s]) s_r = std::min(s_r, slots[s]->skip);
+        steps_run += n_sched - s_r;
+        for (int i = 0; i < n; ++i) {
+            dsg_handle* h = hs[i];
+            dsg_handle::Queue& q = h->cq;
+            wargs[i].skip_timesteps = s_r;
+            h->nkeys.assign(4 * (size_t)B, 0u);
+            bool inp = !lane_inp.empty() && lane_inp[i];
+            for (int b = 0; b < B; ++b) {
+                const SlotWork* w = lane[b] = slots[(size_t)b * n + i];
+                // a dead slot: a slot without edits and with hold 0 -- it starts as k_x_in starts it for the round's skip -- that hands nothing off
+                EditSlot& e = q.edits_host[b];
+                e = w ? w->ed : EditSlot{nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0, 0};
+                // the start of the slot's chain -- do_q and the q_sample pair -- from the schedule of the lane that runs the slot: what k_x_in /
+                // k_clip_x_in get on that lane for the slot's skip_timesteps
+                const int skip = w ? w->skip : s_r, i0 = h->sched.n - skip - 1;
+                e.qa = (float)h->sched.sqrt_ac[i0]; e.qb = (float)h->sched.sqrt_1mac[i0]; e.do_q = skip > 0 ? 1 : 0;
+                q.slots_host[b] = HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0};
+                h->draw_offs[b] = 0u; h->draw_starts[b] = 0u; h->draw_holds[b] = 0;
+                if (!w) continue;
+                const int c = w->c;
+                e.c = c;
+                q.scale_host[b] = w->job.scale;
+                set_noise_key(h, b, w->job.seed, w->job.stream_id);
+                // what dsg_sample_clip alone consumes before window c; its step i is the round's loop index i + hold
+                h->draw_holds[b] = skip - s_r;
+                h->draw_starts[b] = (uint32_t)c * (uint32_t)(1 + w->n_run);
+                h->draw_offs[b] = h->draw_starts[b] - (uint32_t)h->draw_holds[b];
+                q.slots_host[b] = HandoffSlot{w->clip, w->ed.n_out, c, (c == 0 ? HQ_FIRST : 0) | (c == w->job.K - 1 ? HQ_LAST : 0), 0};
+                if (c == 0 && variant5) seed_last_written = true;
+                if (lane_inp.empty() && w->ed.mask) inp = true;
+            }
+            h->nkB = B; h->nk_seeds = true; h->draw_offs_on = true;
+            if (variant5) h->seed_last_B = B;
+            HIPCHK(hipMemcpyAsync(q.slots, q.slots_host.data(), (size_t)B * sizeof(HandoffSlot), hipMemcpyHostToDevice, h->stream));
+            CHK(cond(h, B, lane.data()));
+            CHK(set_window_cond(h, q.style, h->c_seed, q.audio, mask, 1, B, 0, guided ? q.scale_host.data() : nullptr, stream));
+            if (inp || lane_init[i])
+                HIPCHK(hipMemcpyAsync(q.edits, q.edits_host.data(), (size_t)B * sizeof(EditSlot), hipMemcpyHostToDevice, h->stream));
+            h->inpB = 0;
+            if (inp) { CHK(queue_lane_ready(h, QL_INP)); CHK(launch_clip_inp_window_q(h, B)); h->inpB = B; }
+            q.edit_init = lane_init[i] != 0;
+        }
+        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, sjobs[i]));
+        CHK(run_lanes(hs.data(), n, wargs.data(), sjobs.data()));
+        for (int i = 0; i < n; ++i) {
+            CHK(clip_window_timed(hs[i]));
+            CHK(launch_handoff_q(hs[i], B, round, root_shift, keep_last_tail));
+        }
+        return 0;
+    }
+    // behind the rounds of one call (ran: there was one): what dsg_last_sample_ms and its kin report, and `stream` follows the lanes
+    int end(bool ran, void* stream) {
+        for (size_t i = 0; i < hs.size(); ++i) {
+            dsg_handle* h = hs[i];
+            if (ran) { h->last_steps = (int)steps_run; h->timing_valid = true; h->clip_timing = true; h->last_kset = sjobs[i].c.ks.set; }
+            CHK(order_before(h, stream));
+        }
+        return 0;
+    }
+};
+
+// dsg_sample_clip_queue_steps: the rounds of a plan (dsg_clip_queue_plan_steps: every clip a slot and a first round), every job's tensors
+// read from the caller's memory.  What it adds to QueueRound:
+//   slots      the plan's [round][slot] -> job table; a job stands on window c = round - its first round;
+//   inputs     the round's style / audio (and, on a clip's first window, seed0 / seed_last) are copied slot by slot from where the caller keeps
+//              them (cond_from_caller);
+//   edits      NULL (dsg_sample_clip_queue), or one dsg_clip_edit per job -- the clip's constraint and / or the clip it is re-denoised from, in
+//              the coordinates of the job's `out`.  Host tensors are staged on the lane that runs the job before the rounds start.  Lanes that
+//              run a constrained job cut the constraint in every round (lane_inp), lanes that run a job with an init start every round through
+//              the edit table (lane_init); a call without edits uploads no edit table and starts through k_x_in;
+//   skips      skip_timesteps: NULL (dsg_sample_clip_queue_edit), or one entry per job (< 0: args->skip_timesteps).  When an entry differs
+//              from the call's, the plan puts the deep jobs first and every lane starts every round through the edit table, which carries
+//              do_q and the q_sample pair of the slot's own first timestep;
+//   outputs    a host `out` is one copy per job at the end.
+static int cond_from_caller(dsg_handle* h, int B, const SlotWork* const* lane) {
+    const size_t sdi = h->cfg.style_dim_in, n_audio = (size_t)h->Ta * h->As, n_tail = (size_t)h->J * h->S;
+    for (int b = 0; b < B; ++b) {
+        const SlotWork* w = lane[b];
+        if (!w) continue;
+        CHK(upload(h, h->cq.style + b * sdi, w->job.style, sdi * sizeof(float)));
+        CHK(upload(h, h->cq.audio + b * n_audio, w->job.audio + w->c * n_audio, n_audio * sizeof(float)));
+        if (w->c != 0) continue;      // (later windows: the hand-off left y['seed'] in place)
+        if (w->job.seed0) CHK(upload(h, h->c_seed + b * n_tail, w->job.seed0, n_tail * sizeof(float)));
+        else HIPCHK(hipMemsetAsync(h->c_seed + b * n_tail, 0, n_tail * sizeof(float), h->stream));
+        if (h->cfg.variant == 5) CHK(upload(h, h->c_seed_last + b * n_tail, w->job.seed_last, n_tail * sizeof(float)));
+    }
+    return 0;
+}
 extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_clip_job* jobs, const dsg_clip_edit* edits, const int32_t* skip_timesteps,
                                            int n_jobs, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift,
                                            int keep_last_tail, void* stream) {
@@ -3071,19 +3249,22 @@ extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_cli
     CHK(clip_queue_check_lanes(hs, n, B, guided, args));
     const int variant5 = hs[0]->cfg.variant == 5;
     for (int j = 0; j < n_jobs; ++j) CHK(clip_queue_check_job(jobs[j], edits ? &edits[j] : nullptr, j, variant5));
-    const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J, Ta = hs[0]->Ta, As = hs[0]->As, sdi = hs[0]->cfg.style_dim_in;
+    const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J;
     const int n_slots = n * B, keep = T - S;
     const int n_sched = hs[0]->sched.n;
-    std::vector<int32_t> Ks(n_jobs), slot(n_jobs), first(n_jobs), skips(n_jobs, args->skip_timesteps), n_runs(n_jobs);
+    std::vector<int32_t> Ks(n_jobs), slot(n_jobs), first(n_jobs), n_runs(n_jobs);
+    std::vector<SlotWork> work(n_jobs);
     bool own_skips = false;      // some job's skip differs from the call's: otherwise this IS dsg_sample_clip_queue_edit, launch for launch
     for (int j = 0; j < n_jobs; ++j) {
+        SlotWork& w = work[j];
+        w.job = jobs[j];
         Ks[j] = jobs[j].K;
-        if (skip_timesteps && skip_timesteps[j] >= 0) skips[j] = skip_timesteps[j];
-        if (skips[j] < 0 || skips[j] >= n_sched)
-            return fail(DSG_E_INVALID, "dsg_sample_clip_queue: skip_timesteps out of range: job " + std::to_string(j) + " has skip_timesteps " + std::to_string(skips[j]) +
+        w.skip = skip_timesteps && skip_timesteps[j] >= 0 ? skip_timesteps[j] : args->skip_timesteps;
+        if (w.skip < 0 || w.skip >= n_sched)
+            return fail(DSG_E_INVALID, "dsg_sample_clip_queue: skip_timesteps out of range: job " + std::to_string(j) + " has skip_timesteps " + std::to_string(w.skip) +
                                        " outside [0, " + std::to_string(n_sched - 1) + "]");
-        own_skips = own_skips || skips[j] != args->skip_timesteps;
-        n_runs[j] = n_sched - skips[j];
+        own_skips = own_skips || w.skip != args->skip_timesteps;
+        n_runs[j] = w.n_run = n_sched - w.skip;
     }
     int32_t n_rounds = 0;
     CHK(dsg_clip_queue_plan_steps(Ks.data(), own_skips ? n_runs.data() : nullptr, n_jobs, n_slots, slot.data(), first.data(), &n_rounds, nullptr));
@@ -3092,7 +3273,6 @@ extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_cli
         for (int c = 0; c < Ks[j]; ++c) sched[(size_t)(first[j] + c) * n_slots + slot[j]] = j;
     HIPCHK(hipSetDevice(hs[0]->cfg.device));
     // the clips: the caller's tensor where it is device memory, else a piece of ONE device buffer (lane 0's) and one copy per job at the end
-    std::vector<float*> clip(n_jobs);
     std::vector<size_t> n_clip(n_jobs);
     {
         size_t need = 0;
@@ -3104,65 +3284,50 @@ extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_cli
         if (need > h0->clip_out_cap) { CHK(dalloc(h0, &h0->clip_out, need, false)); h0->clip_out_cap = need; }
         size_t at = 0;
         for (int j = 0; j < n_jobs; ++j) {
-            if (is_device_ptr(jobs[j].out)) clip[j] = jobs[j].out;
-            else { clip[j] = h0->clip_out + at; at += n_clip[j]; }
+            if (is_device_ptr(jobs[j].out)) work[j].clip = jobs[j].out;
+            else { work[j].clip = h0->clip_out + at; at += n_clip[j]; }
+            work[j].ed = EditSlot{nullptr, nullptr, nullptr, (int)(n_clip[j] / J), 0, 0.f, 0.f, 0, 0};
         }
     }
-    for (int i = 0; i < n; ++i) {
-        dsg_handle* h = hs[i];
-        for (int k = 0; k < 2; ++k)
-            if (!h->clip_tail[k]) CHK(dalloc(h, &h->clip_tail[k], (size_t)h->Bmax * J * S));
-        if (!h->q_style) CHK(dalloc(h, &h->q_style, (size_t)h->Bmax * sdi));
-        if (!h->q_audio) CHK(dalloc(h, &h->q_audio, (size_t)h->Bmax * Ta * As));
-        if (!h->q_slots) CHK(dalloc(h, &h->q_slots, (size_t)h->Bmax));
-        h->q_slots_host.assign(B, HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0});
-        h->q_scale_host.assign(B, 1.f);
-        h->draw_offs.assign(B, 0u); h->draw_starts.assign(B, 0u); h->draw_holds.assign(B, 0);
-        CHK(order_after(h, stream));
-    }
+    QueueRound rd(hs, n, B, mask_local, guided, *args, root_shift, keep_last_tail);
+    struct QueueNow {      // the lanes leave the queue on every return path
+        QueueRound& rd;
+        ~QueueNow() { for (dsg_handle* h : rd.hs) queue_leave_lane(h, rd.seed_last_written); }
+    } queue_now{rd};
+    rd.cond = cond_from_caller;
+    rd.lane_inp.assign(n, 0);
+    rd.lane_init.assign(n, own_skips ? 1 : 0);      // (per-clip skips: every lane starts every round through the table)
+    for (int i = 0; i < n; ++i) CHK(queue_lane_ready(hs[i], own_skips ? QL_EDITS : 0));
+    CHK(rd.begin(stream));
     // the edits: where each job's tensors are read on the device -- the caller's where they are device memory, else a piece of the staging of
     // the lane that runs the job (slot[j] % n), uploaded here on that lane's stream (the first round's sample_prepare drains it)
-    const size_t r16 = 15;
-    std::vector<EditSlot> ed(n_jobs, EditSlot{nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0, 0});
-    // the start of a slot's chain -- do_q and the q_sample pair -- is filled in per round, from the schedule of the lane that runs the slot:
-    // what k_x_in / k_clip_x_in get on that lane for the slot's skip_timesteps
-    auto chain_start = [](const dsg_handle* h, int skip, EditSlot& e) {
-        const int i0 = h->sched.n - skip - 1;
-        e.qa = (float)h->sched.sqrt_ac[i0]; e.qb = (float)h->sched.sqrt_1mac[i0]; e.do_q = skip > 0 ? 1 : 0;
-    };
-    std::vector<char> lane_inp(n, 0), lane_init(n, own_skips ? 1 : 0);      // (per-clip skips: every lane starts every round through the table)
-    if (own_skips)
-        for (int i = 0; i < n; ++i) if (!hs[i]->q_edits) CHK(dalloc(hs[i], &hs[i]->q_edits, (size_t)hs[i]->Bmax));
     if (edits) {
+        const size_t r16 = 15;
         std::vector<size_t> need(n, 0);
         for (int j = 0; j < n_jobs; ++j) {
             const dsg_clip_edit& e = edits[j];
             const int i = slot[j] % n;
-            if (e.inp_mask) lane_inp[i] = 1;
-            if (e.init_motion) lane_init[i] = 1;
+            if (e.inp_mask) rd.lane_inp[i] = 1;
+            if (e.init_motion) rd.lane_init[i] = 1;
             if (e.inp_motion && !is_device_ptr(e.inp_motion)) need[i] += (n_clip[j] * sizeof(float) + r16) & ~r16;
             if (e.inp_mask && !is_device_ptr(e.inp_mask)) need[i] += (n_clip[j] + r16) & ~r16;
             if (e.init_motion && !is_device_ptr(e.init_motion)) need[i] += (n_clip[j] * sizeof(float) + r16) & ~r16;
         }
         for (int i = 0; i < n; ++i) {
             dsg_handle* h = hs[i];
-            if (!lane_inp[i] && !lane_init[i]) continue;
-            if (!h->q_edits) CHK(dalloc(h, &h->q_edits, (size_t)h->Bmax));
-            if (lane_inp[i]) {      // (each pointer on its own, as dsg_set_inpainting)
-                if (!h->inp32) CHK(dalloc(h, &h->inp32, (size_t)h->Bmax * T * h->Jp));
-                if (!h->inp_mask) CHK(dalloc(h, &h->inp_mask, (size_t)h->Bmax * T * h->Jp));
-            }
-            if (need[i] > h->q_stage_cap) {
+            if (!rd.lane_inp[i] && !rd.lane_init[i]) continue;
+            CHK(queue_lane_ready(h, QL_EDITS));
+            if (need[i] > h->cq.stage_cap) {
                 // grown: the old staging goes back at once (nothing on the handle's stream may still read it)
                 HIPCHK(hipStreamSynchronize(h->stream));
-                if (h->q_stage) {
-                    void* old = h->q_stage;
-                    h->q_stage = nullptr; h->q_stage_cap = 0;
+                if (h->cq.stage) {
+                    void* old = h->cq.stage;
+                    h->cq.stage = nullptr; h->cq.stage_cap = 0;
                     h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), old), h->allocs.end());
                     (void)hipFree(old);
                 }
-                CHK(dalloc(h, &h->q_stage, need[i], false));
-                h->q_stage_cap = need[i];
+                CHK(dalloc(h, &h->cq.stage, need[i], false));
+                h->cq.stage_cap = need[i];
             }
         }
         std::vector<size_t> at(n, 0);
@@ -3170,116 +3335,25 @@ extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_cli
             const dsg_clip_edit& e = edits[j];
             dsg_handle* h = hs[slot[j] % n];
             size_t& p = at[slot[j] % n];
-            auto staged = [&](const void* src, size_t bytes, const void** dst) -> int {
-                if (!src || is_device_ptr(src)) { *dst = src; return 0; }
-                CHK(upload(h, h->q_stage + p, src, bytes));
-                *dst = h->q_stage + p;
-                p += (bytes + r16) & ~r16;
-                return 0;
-            };
-            CHK(staged(e.inp_motion, n_clip[j] * sizeof(float), (const void**)&ed[j].motion));
-            CHK(staged(e.init_motion, n_clip[j] * sizeof(float), (const void**)&ed[j].init));
-            CHK(staged(e.inp_mask, n_clip[j], (const void**)&ed[j].mask));
-            ed[j].n_out = (int)(n_clip[j] / J);
+            auto room = [&](size_t bytes, void** out) { *out = h->cq.stage + p; p += (bytes + r16) & ~r16; return 0; };
+            EditSlot& ed = work[j].ed;
+            CHK(staged(h, e.inp_motion, n_clip[j] * sizeof(float), room, (const void**)&ed.motion));
+            CHK(staged(h, e.init_motion, n_clip[j] * sizeof(float), room, (const void**)&ed.init));
+            CHK(staged(h, e.inp_mask, n_clip[j], room, (const void**)&ed.mask));
         }
     }
-    // What the call sets on a lane for its rounds -- the keyed table and its draw offsets, lanes_now, (variant 5) the batch of seed_last, with
-    // edits the epilogue's inpainting (inpB) and the start through the edit table (q_edit_init) -- is put back on every return path.  Every
-    // lane came in unkeyed and with inpB == 0 (checked above).  Variant 5: the rows of c_seed_last now hold the jobs' snippets,
-    // so the lane asks for dsg_set_seed_last again, as a fresh handle does
-    struct QueueNow {
-        dsg_handle** hs; int n; bool seed_last_written = false;
-        QueueNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) { hs[i]->lanes_now = n; hs[i]->clip_ms = 0.0; } }
-        ~QueueNow() {
-            for (int i = 0; i < n; ++i) {
-                dsg_handle* h = hs[i];
-                h->lanes_now = 1; h->nkB = 0; h->nk_seeds = false; h->nkeys.clear(); h->draw_offs_on = false;
-                h->inpB = 0; h->q_edit_init = false;
-                if (seed_last_written) h->seed_last_B = 0;
-            }
+    std::vector<const SlotWork*> slots(n_slots);
+    for (int r = 0; r < n_rounds; ++r) {      // (some slot is alive in every round of the plan)
+        for (int s = 0; s < n_slots; ++s) {
+            const int j = sched[(size_t)r * n_slots + s];
+            slots[s] = j < 0 ? nullptr : &work[j];
+            if (j >= 0) work[j].c = r - first[j];
         }
-    } queue_now(hs, n);
-    std::vector<SampleJob> sjobs(n);
-    std::vector<dsg_sample_args> wargs(n, *args);      // (draw_base is args->draw_base for every clip: the windows are told apart by the offsets)
-    const size_t n_tail = (size_t)J * S;
-    int64_t steps_run = 0;
-    for (int r = 0; r < n_rounds; ++r) {
-        // the round's first timestep: the smallest skip alive in it, over all lanes (some slot is alive in every round of the plan)
-        int s_r = n_sched;
-        for (int s = 0; s < n_slots; ++s) { const int j = sched[(size_t)r * n_slots + s]; if (j >= 0) s_r = std::min(s_r, (int)skips[j]); }
-        const int n_run = n_sched - s_r;
-        steps_run += n_run;
-        for (int i = 0; i < n; ++i) {
-            dsg_handle* h = hs[i];
-            wargs[i].skip_timesteps = s_r;
-            h->nkeys.assign(4 * (size_t)B, 0u);
-            // a dead slot: a slot without edits and with hold 0 -- it starts as k_x_in starts it for the round's skip
-            EditSlot ed_dead = {nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0, 0};
-            chain_start(h, s_r, ed_dead);
-            h->q_edits_host.assign(B, ed_dead);
-            for (int b = 0; b < B; ++b) {
-                const int j = sched[(size_t)r * n_slots + (size_t)b * n + i];      // global slot s: lane s % n, position s / n
-                HandoffSlot& hq = h->q_slots_host[b];
-                h->draw_offs[b] = 0u; h->draw_starts[b] = 0u; h->draw_holds[b] = 0;
-                if (j < 0) { hq = HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0}; continue; }
-                const dsg_clip_job& q = jobs[j];
-                const int c = r - first[j];
-                CHK(upload(h, h->q_style + (size_t)b * sdi, q.style, (size_t)sdi * sizeof(float)));
-                CHK(upload(h, h->q_audio + (size_t)b * Ta * As, q.audio + (size_t)c * Ta * As, (size_t)Ta * As * sizeof(float)));
-                h->q_scale_host[b] = q.scale;
-                if (c == 0) {
-                    if (q.seed0) CHK(upload(h, h->c_seed + b * n_tail, q.seed0, n_tail * sizeof(float)));
-                    else HIPCHK(hipMemsetAsync(h->c_seed + b * n_tail, 0, n_tail * sizeof(float), h->stream));
-                    if (variant5) {
-                        queue_now.seed_last_written = true;
-                        CHK(upload(h, h->c_seed_last + b * n_tail, q.seed_last, n_tail * sizeof(float)));
-                    }
-                }
-                h->nkeys[4 * b] = (unsigned)(q.seed & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(q.seed >> 32);
-                h->nkeys[4 * b + 2] = (unsigned)(q.stream_id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(q.stream_id >> 32);
-                // what dsg_sample_clip alone consumes before window c; its step i is the round's loop index i + hold
-                h->draw_holds[b] = skips[j] - s_r;
-                h->draw_starts[b] = (uint32_t)c * (uint32_t)(1 + n_runs[j]);
-                h->draw_offs[b] = h->draw_starts[b] - (uint32_t)h->draw_holds[b];
-                hq = HandoffSlot{clip[j], (int)(n_clip[j] / J), c, (c == 0 ? HQ_FIRST : 0) | (c == Ks[j] - 1 ? HQ_LAST : 0), 0};
-                h->q_edits_host[b] = ed[j]; h->q_edits_host[b].c = c;
-                chain_start(h, skips[j], h->q_edits_host[b]);
-            }
-            h->nkB = B; h->nk_seeds = true; h->draw_offs_on = true;
-            if (variant5) h->seed_last_B = B;
-            // the round's hand-off table, uploaded here: behind the previous round's hand-off on the stream, and in front of the point where
-            // sample_prepare drains the stream -- so the host copy is free to change in the next round
-            HIPCHK(hipMemcpyAsync(h->q_slots, h->q_slots_host.data(), (size_t)B * sizeof(HandoffSlot), hipMemcpyHostToDevice, h->stream));
-            CHK(set_window_cond(h, h->q_style, h->c_seed, h->q_audio, mask_local, 1, B, 0, guided ? h->q_scale_host.data() : nullptr, stream));
-            if (lane_inp[i] || lane_init[i])      // the round's edit table: where the hand-off table goes up, for the same reason
-                HIPCHK(hipMemcpyAsync(h->q_edits, h->q_edits_host.data(), (size_t)B * sizeof(EditSlot), hipMemcpyHostToDevice, h->stream));
-            if (lane_inp[i]) { CHK(launch_clip_inp_window_q(h, B)); h->inpB = B; }
-            h->q_edit_init = lane_init[i] != 0;
-        }
-        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, sjobs[i]));
-        CHK(run_lanes(hs, n, wargs.data(), sjobs.data()));
-        for (int i = 0; i < n; ++i) {
-            dsg_handle* h = hs[i];
-            HIPCHK(hipEventRecord(h->ev_t1, h->stream));
-            if (h->aql_timing) h->clip_ms += h->aql_ms;
-            else {
-                float ms = 0.f;
-                HIPCHK(hipEventSynchronize(h->ev_t1));
-                HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
-                h->clip_ms += ms;
-            }
-            CHK(launch_handoff_q(h, B, r, root_shift, keep_last_tail));
-        }
+        CHK(rd.run(slots.data(), r, stream));
     }
     for (int j = 0; j < n_jobs; ++j)
-        if (clip[j] != jobs[j].out) CHK(from_dev(hs[slot[j] % n], jobs[j].out, clip[j], n_clip[j]));      // (on the stream of the lane that wrote it)
-    for (int i = 0; i < n; ++i) {
-        dsg_handle* h = hs[i];
-        h->last_steps = (int)steps_run; h->timing_valid = true; h->clip_timing = true;
-        h->last_kset = sjobs[i].c.ks.set;
-        CHK(order_before(h, stream));
-    }
-    return 0;
+        if (work[j].clip != jobs[j].out) CHK(from_dev(hs[slot[j] % n], jobs[j].out, work[j].clip, n_clip[j]));      // (on the stream of the lane that wrote it)
+    return rd.end(true, stream);
 }
 
 extern "C" int dsg_sample_clip_queue_edit(dsg_handle** hs, int n, const dsg_clip_job* jobs, const dsg_clip_edit* edits, int n_jobs, int B,
@@ -3293,39 +3367,31 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Queue session (dsg_queue_*): the clip queue as an object that lives between rounds.  Jobs are submitted while it runs, every round is a
-// round of dsg_sample_clip_queue_steps -- the same tables, set_window_cond, sample_prepare, run_lanes, launch_handoff_q -- and a job's rows
-// are in the caller's memory after the round that made them final.  What differs from the one-shot call:
-//   placement  first come, first served: at the start of a round the free slots, lowest first, take the pending jobs, oldest ticket first
-//              (dsg_queue_place is the same rule on the host);
+// Queue session (dsg_queue_*): the clip queue as an object that lives between rounds.  Jobs are submitted while it runs and a job's rows
+// are in the caller's memory after the round that made them final.  What it adds to QueueRound:
+//   slots      first come, first served: at the start of a round the free slots, lowest first, take the pending jobs, oldest ticket first
+//              (dsg_queue_place is the same rule on the host); a job stands on the window behind those it has done;
 //   inputs     a job's host tensors are copied into session-owned device memory at submit; the round's per-slot conditioning is gathered on
-//              the device (k_clipq_gather, one launch per lane) instead of copied slot by slot from the caller's memory;
-//   start      every lane starts every round through the edit table (k_clipq_x_in), as the one-shot call does with per-job skips: a job
-//              with its own skip or an init motion may arrive in any round;
+//              the device (cond_gathered: k_clipq_gather, one launch per lane);
+//   edits      every lane starts every round through the edit table (k_clipq_x_in): a job with its own skip or an init motion may arrive in
+//              any round.  The constraint is cut in the rounds in which a slot of the lane brings one;
 //   outputs    a host `out` is fed from a session-owned device clip, the rows that became final copied after every round.
 // ---------------------------------------------------------------------------------------------------------
 struct QBlock { void* p; size_t cap; };
 struct QJob {
-    dsg_clip_job job;                 // the pointers as the device reads them: the caller's device tensors, or staging
-    EditSlot ed;                      // motion / mask / init as the device reads them, n_out
+    SlotWork w;                       // every pointer as the device reads it: the caller's device tensors, or staging.  w.c: the windows done
     float* host_out = nullptr;        // the caller's host `out` (null: a device `out`, written by the hand-off itself)
-    float* clip = nullptr;            // [n_out][J] on the device
-    int n_out = 0, skip = 0, n_run = 0;
-    int state = DSG_JOB_PENDING, windows_done = 0, rows_ready = 0, rows_copied = 0, slot = -1, first_round = -1;
+    int state = DSG_JOB_PENDING, rows_ready = 0, rows_copied = 0, slot = -1, first_round = -1;
     std::vector<QBlock> blocks;       // the staging the job holds; back to the session's free list when it is done or cancelled
 };
 struct dsg_queue {
-    std::vector<dsg_handle*> hs;
-    int n = 0, B = 0, guided = 0, root_shift = 0, keep_last_tail = 0;
-    dsg_sample_args args;
-    unsigned char* mask_d = nullptr;  // the session's copy of mask_local (null: none was given)
+    QueueRound rd;                    // the lanes, B, guided, args, root_shift, keep_last_tail; rd.mask: the session's device copy of mask_local
     std::vector<QJob> jobs;           // index = ticket
     std::vector<int64_t> slot_job;    // [n * B] -> ticket, -1: free
     size_t next_pending = 0;          // no ticket below it is pending
     int64_t rounds_total = 0;
     std::multimap<size_t, void*> free_blocks;      // recycled staging, by capacity
     std::vector<void*> all_blocks;                 // every staging block ever allocated: released at close
-    bool seed_last_written = false;
 };
 // staging: blocks in power-of-two size classes (>= 256 bytes), recycled within the session, never freed between rounds (hipFree synchronises)
 static int queue_take(dsg_queue* q, size_t bytes, QJob& jb, void** out) {
@@ -3350,12 +3416,12 @@ static void queue_give(dsg_queue* q, QJob& jb) {
     jb.blocks.clear();
 }
 static int queue_rows_ready(const dsg_queue* q, const QJob& jb) {
-    const int keep = q->hs[0]->T - q->hs[0]->S, S = q->hs[0]->S;
-    if (jb.windows_done >= jb.job.K) return jb.n_out;
+    const int S = q->rd.hs[0]->S, keep = q->rd.hs[0]->T - S, n_out = jb.w.ed.n_out;
+    if (jb.w.c >= jb.w.job.K) return n_out;
     // window c leaves rows [c * keep - S, (c + 1) * keep - S) final (handoff_row), with keep_last_tail too: there only the LAST window writes
     // its closing S frames, and a job past its last window reports n_out above
-    const int64_t r = (int64_t)jb.windows_done * keep - S;
-    return (int)std::max<int64_t>(0, std::min<int64_t>(jb.n_out, r));
+    const int64_t r = (int64_t)jb.w.c * keep - S;
+    return (int)std::max<int64_t>(0, std::min<int64_t>(n_out, r));
 }
 
 extern "C" int dsg_queue_place(const int32_t* K, const int32_t* arrive_round, int n_jobs, int n_slots, int32_t* slot, int32_t* first_round,
@@ -3388,6 +3454,26 @@ extern "C" int dsg_queue_place(const int32_t* K, const int32_t* arrive_round, in
     return 0;
 }
 
+// the round's conditioning of a lane, gathered on the device from where the session keeps its jobs' tensors: the table, one launch
+static int cond_gathered(dsg_handle* h, int B, const SlotWork* const* lane) {
+    dsg_handle::Queue& q = h->cq;
+    const size_t n_audio = (size_t)h->Ta * h->As;
+    q.gather_host.resize(B);
+    for (int b = 0; b < B; ++b) {
+        const SlotWork* w = lane[b];
+        q.gather_host[b] = w ? GatherSlot{w->job.style, w->job.audio + w->c * n_audio, w->job.seed0, w->job.seed_last, GQ_LIVE | (w->c == 0 ? GQ_FIRST : 0), 0}
+                             : GatherSlot{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    }
+    HIPCHK(hipMemcpyAsync(q.gather, q.gather_host.data(), (size_t)B * sizeof(GatherSlot), hipMemcpyHostToDevice, h->stream));
+    GatherQArgs a;
+    a.slots = q.gather; a.q_style = q.style; a.q_audio = q.audio; a.c_seed = h->c_seed; a.c_seed_last = h->c_seed_last;
+    a.B = B; a.sdi = h->cfg.style_dim_in; a.n_audio = h->Ta * h->As; a.n_seed = h->J * h->S; a.variant5 = h->cfg.variant == 5 ? 1 : 0;
+    const size_t n = (size_t)B * ((a.sdi + 3) / 4 + (a.n_audio + 3) / 4 + (size_t)(a.variant5 ? 2 : 1) * ((a.n_seed + 3) / 4));
+    hipLaunchKernelGGL(k_clipq_gather, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int dsg_queue_open(dsg_handle** hs, int n, int B, const uint8_t* mask_local, int guided, const dsg_sample_args* args, int root_shift,
                               int keep_last_tail, dsg_queue** out) {
     if (!hs || !args || !out || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: bad argument");
@@ -3397,46 +3483,29 @@ extern "C" int dsg_queue_open(dsg_handle** hs, int n, int B, const uint8_t* mask
         return fail(DSG_E_INVALID, "dsg_sample_clip_queue: skip_timesteps out of range: args has skip_timesteps " + std::to_string(args->skip_timesteps) +
                                    " outside [0, " + std::to_string(hs[0]->sched.n - 1) + "]");
     HIPCHK(hipSetDevice(hs[0]->cfg.device));
-    const int T = hs[0]->T, S = hs[0]->S, J = hs[0]->J, Ta = hs[0]->Ta, As = hs[0]->As, sdi = hs[0]->cfg.style_dim_in;
-    for (int i = 0; i < n; ++i) {
-        dsg_handle* h = hs[i];
-        for (int k = 0; k < 2; ++k)
-            if (!h->clip_tail[k]) CHK(dalloc(h, &h->clip_tail[k], (size_t)h->Bmax * J * S));
-        if (!h->q_style) CHK(dalloc(h, &h->q_style, (size_t)h->Bmax * sdi));
-        if (!h->q_audio) CHK(dalloc(h, &h->q_audio, (size_t)h->Bmax * Ta * As));
-        if (!h->q_slots) CHK(dalloc(h, &h->q_slots, (size_t)h->Bmax));
-        if (!h->q_edits) CHK(dalloc(h, &h->q_edits, (size_t)h->Bmax));
-        if (!h->q_gather) CHK(dalloc(h, &h->q_gather, (size_t)h->Bmax));
-    }
-    dsg_queue* q = new dsg_queue();
-    q->hs.assign(hs, hs + n);
-    q->n = n; q->B = B; q->guided = guided ? 1 : 0; q->root_shift = root_shift ? 1 : 0; q->keep_last_tail = keep_last_tail ? 1 : 0;
-    q->args = *args;
-    q->slot_job.assign((size_t)n * B, -1);
+    for (int i = 0; i < n; ++i) CHK(queue_lane_ready(hs[i], QL_EDITS | QL_GATHER));
+    unsigned char* mask_d = nullptr;      // the session's copy of mask_local (null: none was given)
     if (mask_local) {
-        if (hipMalloc((void**)&q->mask_d, (size_t)T) != hipSuccess) { (void)hipGetLastError(); delete q; return fail(DSG_E_RUNTIME, "dsg_queue_open: out of device memory"); }
-        const hipError_t e = hipMemcpy(q->mask_d, mask_local, (size_t)T, is_device_ptr(mask_local) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(q->mask_d); delete q; HIPCHK(e); }
+        const size_t T = (size_t)hs[0]->T;
+        if (hipMalloc((void**)&mask_d, T) != hipSuccess) { (void)hipGetLastError(); return fail(DSG_E_RUNTIME, "dsg_queue_open: out of device memory"); }
+        const hipError_t e = hipMemcpy(mask_d, mask_local, T, is_device_ptr(mask_local) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(mask_d); HIPCHK(e); }
     }
-    for (int i = 0; i < n; ++i) {
-        dsg_handle* h = hs[i];
-        h->q_slots_host.assign(B, HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0});
-        h->q_gather_host.assign(B, GatherSlot{nullptr, nullptr, nullptr, nullptr, 0, 0});
-        h->q_scale_host.assign(B, 1.f);
-        h->draw_offs.assign(B, 0u); h->draw_starts.assign(B, 0u); h->draw_holds.assign(B, 0);
-        h->lanes_now = n; h->clip_ms = 0.0;
-        h->owner = q;
-    }
+    dsg_queue* q = new dsg_queue{QueueRound(hs, n, B, mask_d, guided, *args, root_shift, keep_last_tail)};
+    q->rd.cond = cond_gathered;
+    q->rd.lane_init.assign(n, 1);      // (lane_inp stays empty: per round)
+    q->slot_job.assign((size_t)n * B, -1);
+    for (int i = 0; i < n; ++i) hs[i]->owner = q;
     *out = q;
     return 0;
 }
 
 extern "C" int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg_clip_edit* edit, int skip_timesteps, int64_t* ticket, void* stream) {
     if (!q || !job || !ticket) return fail(DSG_E_INVALID, "dsg_queue_submit: null argument");
-    dsg_handle* h0 = q->hs[0];
+    dsg_handle* h0 = q->rd.hs[0];
     const int64_t t = (int64_t)q->jobs.size();
     CHK(clip_queue_check_job(*job, edit, t, h0->cfg.variant == 5));
-    const int n_sched = h0->sched.n, skip = skip_timesteps >= 0 ? skip_timesteps : q->args.skip_timesteps;
+    const int n_sched = h0->sched.n, skip = skip_timesteps >= 0 ? skip_timesteps : q->rd.args.skip_timesteps;
     if (skip < 0 || skip >= n_sched)
         return fail(DSG_E_INVALID, "dsg_sample_clip_queue: skip_timesteps out of range: job " + std::to_string(t) + " has skip_timesteps " + std::to_string(skip) +
                                    " outside [0, " + std::to_string(n_sched - 1) + "]");
@@ -3445,77 +3514,56 @@ extern "C" int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg
     if ((int64_t)job->K * keep > 0x7fffffff) return fail(DSG_E_INVALID, "dsg_queue_submit: job " + std::to_string(t) + " has more than 2^31 - 1 rows");
     HIPCHK(hipSetDevice(h0->cfg.device));
     QJob jb;
-    jb.job = *job;
-    jb.n_out = job->K * keep - (q->keep_last_tail ? 0 : S);
-    jb.skip = skip; jb.n_run = n_sched - skip;
-    const size_t n_clip = (size_t)jb.n_out * J;
-    jb.ed = EditSlot{nullptr, nullptr, nullptr, jb.n_out, 0, 0.f, 0.f, 0, 0};
+    SlotWork& w = jb.w;
+    w.job = *job;
+    const int n_out = job->K * keep - (q->rd.keep_last_tail ? 0 : S);
+    w.skip = skip; w.n_run = n_sched - skip;
+    const size_t n_clip = (size_t)n_out * J;
+    w.ed = EditSlot{nullptr, nullptr, nullptr, n_out, 0, 0.f, 0.f, 0, 0};
     // a recycled block may still be read by a round in flight on some lane (HIP launches return early): the lanes are drained before the
     // first host tensor is written over one.  They are idle whenever the step loop went through the AQL queues, so this waits for nothing
     bool drained = false;
-    auto staged = [&](const void* src, size_t bytes, const void** dst) -> int {
-        if (!src || is_device_ptr(src)) { *dst = src; return 0; }
-        if (!drained) { for (dsg_handle* h : q->hs) HIPCHK(hipStreamSynchronize(h->stream)); drained = true; }
-        void* p = nullptr;
-        CHK(queue_take(q, bytes, jb, &p));
-        HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, h0->stream));
-        *dst = p;
-        return 0;
+    auto room = [&](size_t bytes, void** p) -> int {
+        if (!drained) { for (dsg_handle* h : q->rd.hs) HIPCHK(hipStreamSynchronize(h->stream)); drained = true; }
+        return queue_take(q, bytes, jb, p);
     };
     int rc = 0;
-    if (!rc) rc = staged(job->style, (size_t)h0->cfg.style_dim_in * sizeof(float), (const void**)&jb.job.style);
-    if (!rc) rc = staged(job->seed0, n_tail * sizeof(float), (const void**)&jb.job.seed0);
-    if (!rc) rc = staged(job->seed_last, n_tail * sizeof(float), (const void**)&jb.job.seed_last);
-    if (!rc) rc = staged(job->audio, (size_t)job->K * n_audio * sizeof(float), (const void**)&jb.job.audio);
+    if (!rc) rc = staged(h0, job->style, (size_t)h0->cfg.style_dim_in * sizeof(float), room, (const void**)&w.job.style);
+    if (!rc) rc = staged(h0, job->seed0, n_tail * sizeof(float), room, (const void**)&w.job.seed0);
+    if (!rc) rc = staged(h0, job->seed_last, n_tail * sizeof(float), room, (const void**)&w.job.seed_last);
+    if (!rc) rc = staged(h0, job->audio, (size_t)job->K * n_audio * sizeof(float), room, (const void**)&w.job.audio);
     if (!rc && edit) {
-        rc = staged(edit->inp_motion, n_clip * sizeof(float), (const void**)&jb.ed.motion);
-        if (!rc) rc = staged(edit->init_motion, n_clip * sizeof(float), (const void**)&jb.ed.init);
-        if (!rc) rc = staged(edit->inp_mask, n_clip, (const void**)&jb.ed.mask);
+        rc = staged(h0, edit->inp_motion, n_clip * sizeof(float), room, (const void**)&w.ed.motion);
+        if (!rc) rc = staged(h0, edit->init_motion, n_clip * sizeof(float), room, (const void**)&w.ed.init);
+        if (!rc) rc = staged(h0, edit->inp_mask, n_clip, room, (const void**)&w.ed.mask);
     }
     if (!rc) {
-        if (is_device_ptr(job->out)) jb.clip = job->out;
+        if (is_device_ptr(job->out)) w.clip = job->out;
         else {
             void* p = nullptr;
             rc = queue_take(q, n_clip * sizeof(float), jb, &p);
-            jb.clip = (float*)p; jb.host_out = job->out;
+            w.clip = (float*)p; jb.host_out = job->out;
         }
     }
     // the caller's host buffers are free on return: the copies above have landed
     if (!rc && drained && hipStreamSynchronize(h0->stream) != hipSuccess) { (void)hipGetLastError(); rc = fail(DSG_E_RUNTIME, "dsg_queue_submit: staging copy failed"); }
     if (rc) { queue_give(q, jb); return rc; }      // the session is as it was (the blocks taken so far wait in its free list)
     // device tensors of the job are read where they are: whatever `stream` still does to them comes first on every lane
-    for (dsg_handle* h : q->hs) CHK(order_after(h, stream));
+    for (dsg_handle* h : q->rd.hs) CHK(order_after(h, stream));
     q->jobs.push_back(std::move(jb));
     *ticket = t;
-    return 0;
-}
-
-static int launch_gather_q(dsg_handle* h, int B) {
-    GatherQArgs a;
-    a.slots = h->q_gather; a.q_style = h->q_style; a.q_audio = h->q_audio; a.c_seed = h->c_seed; a.c_seed_last = h->c_seed_last;
-    a.B = B; a.sdi = h->cfg.style_dim_in; a.n_audio = h->Ta * h->As; a.n_seed = h->J * h->S; a.variant5 = h->cfg.variant == 5 ? 1 : 0;
-    const size_t n = (size_t)B * ((a.sdi + 3) / 4 + (a.n_audio + 3) / 4 + (size_t)(a.variant5 ? 2 : 1) * ((a.n_seed + 3) / 4));
-    hipLaunchKernelGGL(k_clipq_gather, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void* stream) {
     if (rounds_run) *rounds_run = 0;
     if (!q) return fail(DSG_E_INVALID, "dsg_queue_run: null queue");
-    dsg_handle** hs = q->hs.data();
-    const int n = q->n, B = q->B, n_slots = n * B;
-    const int J = hs[0]->J, n_sched = hs[0]->sched.n, variant5 = hs[0]->cfg.variant == 5;
-    const size_t n_audio = (size_t)hs[0]->Ta * hs[0]->As;
+    QueueRound& rd = q->rd;
+    dsg_handle** hs = rd.hs.data();
+    const int n = (int)rd.hs.size(), n_slots = n * rd.B, J = hs[0]->J;
     HIPCHK(hipSetDevice(hs[0]->cfg.device));
-    for (int i = 0; i < n; ++i) { hs[i]->clip_ms = 0.0; CHK(order_after(hs[i], stream)); }
-    auto chain_start = [](const dsg_handle* h, int skip, EditSlot& e) {      // (as in dsg_sample_clip_queue_steps)
-        const int i0 = h->sched.n - skip - 1;
-        e.qa = (float)h->sched.sqrt_ac[i0]; e.qb = (float)h->sched.sqrt_1mac[i0]; e.do_q = skip > 0 ? 1 : 0;
-    };
-    std::vector<SampleJob> sjobs(n);
-    std::vector<dsg_sample_args> wargs(n, q->args);
-    int64_t steps_run = 0;
+    CHK(rd.begin(stream));
+    std::vector<const SlotWork*> slots(n_slots);
     int done = 0;
     while (max_rounds <= 0 || done < max_rounds) {
         // placement: the free slots, lowest first, take the pending jobs, oldest ticket first
@@ -3527,73 +3575,13 @@ extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void
             jb.state = DSG_JOB_RUNNING; jb.slot = s; jb.first_round = (int)q->rounds_total;
             q->slot_job[s] = (int64_t)q->next_pending++;
         }
-        // the round's first timestep: the smallest skip alive in it, over all lanes
-        int s_r = n_sched;
-        for (int s = 0; s < n_slots; ++s) if (q->slot_job[s] >= 0) s_r = std::min(s_r, q->jobs[q->slot_job[s]].skip);
-        if (s_r == n_sched) break;      // nothing alive, nothing pending
-        const int r = (int)(q->rounds_total & 0x7fffffff);      // (the hand-off uses its parity alone)
-        steps_run += n_sched - s_r;
-        for (int i = 0; i < n; ++i) {
-            dsg_handle* h = hs[i];
-            wargs[i].skip_timesteps = s_r;
-            h->nkeys.assign(4 * (size_t)B, 0u);
-            EditSlot ed_dead = {nullptr, nullptr, nullptr, 0, 0, 0.f, 0.f, 0, 0};      // a dead slot: no edits, hold 0, the round's own start
-            chain_start(h, s_r, ed_dead);
-            h->q_edits_host.assign(B, ed_dead);
-            bool lane_inp = false;
-            for (int b = 0; b < B; ++b) {
-                const int64_t t = q->slot_job[(size_t)b * n + i];      // global slot s: lane s % n, position s / n
-                HandoffSlot& hq = h->q_slots_host[b];
-                h->draw_offs[b] = 0u; h->draw_starts[b] = 0u; h->draw_holds[b] = 0;
-                h->q_gather_host[b] = GatherSlot{nullptr, nullptr, nullptr, nullptr, 0, 0};
-                if (t < 0) { hq = HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0}; continue; }
-                const QJob& jb = q->jobs[t];
-                const dsg_clip_job& cj = jb.job;
-                const int c = jb.windows_done;
-                h->q_gather_host[b] = GatherSlot{cj.style, cj.audio + (size_t)c * n_audio, cj.seed0, cj.seed_last, GQ_LIVE | (c == 0 ? GQ_FIRST : 0), 0};
-                if (c == 0 && variant5) q->seed_last_written = true;
-                h->q_scale_host[b] = cj.scale;
-                h->nkeys[4 * b] = (unsigned)(cj.seed & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(cj.seed >> 32);
-                h->nkeys[4 * b + 2] = (unsigned)(cj.stream_id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(cj.stream_id >> 32);
-                h->draw_holds[b] = jb.skip - s_r;
-                h->draw_starts[b] = (uint32_t)c * (uint32_t)(1 + jb.n_run);
-                h->draw_offs[b] = h->draw_starts[b] - (uint32_t)h->draw_holds[b];
-                hq = HandoffSlot{jb.clip, jb.n_out, c, (c == 0 ? HQ_FIRST : 0) | (c == cj.K - 1 ? HQ_LAST : 0), 0};
-                h->q_edits_host[b] = jb.ed; h->q_edits_host[b].c = c;
-                chain_start(h, jb.skip, h->q_edits_host[b]);
-                lane_inp = lane_inp || jb.ed.mask != nullptr;
-            }
-            if (lane_inp) {      // (each pointer on its own, as dsg_set_inpainting)
-                if (!h->inp32) CHK(dalloc(h, &h->inp32, (size_t)h->Bmax * h->T * h->Jp));
-                if (!h->inp_mask) CHK(dalloc(h, &h->inp_mask, (size_t)h->Bmax * h->T * h->Jp));
-            }
-            h->nkB = B; h->nk_seeds = true; h->draw_offs_on = true;
-            if (variant5) h->seed_last_B = B;
-            // the round's tables, uploaded here: behind the previous round's hand-off on the stream, and in front of the point where
-            // sample_prepare drains the stream -- so the host copies are free to change in the next round
-            HIPCHK(hipMemcpyAsync(h->q_slots, h->q_slots_host.data(), (size_t)B * sizeof(HandoffSlot), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->q_gather, h->q_gather_host.data(), (size_t)B * sizeof(GatherSlot), hipMemcpyHostToDevice, h->stream));
-            CHK(launch_gather_q(h, B));
-            CHK(set_window_cond(h, h->q_style, h->c_seed, h->q_audio, q->mask_d, 1, B, 0, q->guided ? h->q_scale_host.data() : nullptr, stream));
-            HIPCHK(hipMemcpyAsync(h->q_edits, h->q_edits_host.data(), (size_t)B * sizeof(EditSlot), hipMemcpyHostToDevice, h->stream));
-            h->inpB = 0;
-            if (lane_inp) { CHK(launch_clip_inp_window_q(h, B)); h->inpB = B; }
-            h->q_edit_init = true;
+        bool alive = false;
+        for (int s = 0; s < n_slots; ++s) {
+            slots[s] = q->slot_job[s] < 0 ? nullptr : &q->jobs[q->slot_job[s]].w;
+            alive = alive || slots[s];
         }
-        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, sjobs[i]));
-        CHK(run_lanes(hs, n, wargs.data(), sjobs.data()));
-        for (int i = 0; i < n; ++i) {
-            dsg_handle* h = hs[i];
-            HIPCHK(hipEventRecord(h->ev_t1, h->stream));
-            if (h->aql_timing) h->clip_ms += h->aql_ms;
-            else {
-                float ms = 0.f;
-                HIPCHK(hipEventSynchronize(h->ev_t1));
-                HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
-                h->clip_ms += ms;
-            }
-            CHK(launch_handoff_q(h, B, r, q->root_shift, q->keep_last_tail));
-        }
+        if (!alive) break;      // nothing alive, nothing pending
+        CHK(rd.run(slots.data(), (int)(q->rounds_total & 0x7fffffff), stream));
         // the round's windows are handed off: the rows that became final go to the callers' host memory, on the stream of the lane that
         // wrote them; finished jobs leave their slots
         std::vector<char> copied(n, 0);
@@ -3601,11 +3589,11 @@ extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void
             const int64_t t = q->slot_job[s];
             if (t < 0) continue;
             QJob& jb = q->jobs[t];
-            ++jb.windows_done;
+            ++jb.w.c;
             jb.rows_ready = queue_rows_ready(q, jb);
             if (jb.host_out && jb.rows_ready > jb.rows_copied) {
                 const size_t at = (size_t)jb.rows_copied * J, cnt = (size_t)(jb.rows_ready - jb.rows_copied) * J;
-                HIPCHK(hipMemcpyAsync(jb.host_out + at, jb.clip + at, cnt * sizeof(float), hipMemcpyDeviceToHost, hs[s % n]->stream));
+                HIPCHK(hipMemcpyAsync(jb.host_out + at, jb.w.clip + at, cnt * sizeof(float), hipMemcpyDeviceToHost, hs[s % n]->stream));
                 jb.rows_copied = jb.rows_ready;
                 copied[s % n] = 1;
             }
@@ -3613,18 +3601,14 @@ extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void
         for (int i = 0; i < n; ++i) if (copied[i]) HIPCHK(hipStreamSynchronize(hs[i]->stream));
         for (int s = 0; s < n_slots; ++s) {
             const int64_t t = q->slot_job[s];
-            if (t < 0 || q->jobs[t].windows_done < q->jobs[t].job.K) continue;
+            if (t < 0 || q->jobs[t].w.c < q->jobs[t].w.job.K) continue;
             q->jobs[t].state = DSG_JOB_DONE;
             queue_give(q, q->jobs[t]);
             q->slot_job[s] = -1;
         }
         ++q->rounds_total; ++done;
     }
-    for (int i = 0; i < n; ++i) {
-        dsg_handle* h = hs[i];
-        if (done > 0) { h->last_steps = (int)steps_run; h->timing_valid = true; h->clip_timing = true; h->last_kset = sjobs[i].c.ks.set; }
-        CHK(order_before(h, stream));
-    }
+    CHK(rd.end(done > 0, stream));
     if (rounds_run) *rounds_run = done;
     return 0;
 }
@@ -3634,7 +3618,7 @@ extern "C" int dsg_queue_job(dsg_queue* q, int64_t ticket, dsg_queue_job_info* i
     if (ticket < 0 || ticket >= (int64_t)q->jobs.size()) return fail(DSG_E_INVALID, "dsg_queue_job: no such ticket: " + std::to_string(ticket));
     const QJob& jb = q->jobs[ticket];
     memset(info, 0, sizeof *info);
-    info->state = jb.state; info->windows_done = jb.windows_done; info->rows_ready = jb.rows_ready; info->slot = jb.slot; info->first_round = jb.first_round;
+    info->state = jb.state; info->windows_done = jb.w.c; info->rows_ready = jb.rows_ready; info->slot = jb.slot; info->first_round = jb.first_round;
     return 0;
 }
 extern "C" int dsg_queue_info(dsg_queue* q, int64_t* rounds_total, int* n_pending, int* n_running) {
@@ -3659,17 +3643,14 @@ extern "C" int dsg_queue_cancel(dsg_queue* q, int64_t ticket) {
 }
 extern "C" int dsg_queue_close(dsg_queue* q) {
     if (!q) return 0;
-    (void)hipSetDevice(q->hs[0]->cfg.device);
-    for (dsg_handle* h : q->hs) {
+    (void)hipSetDevice(q->rd.hs[0]->cfg.device);
+    for (dsg_handle* h : q->rd.hs) {
         (void)hipStreamSynchronize(h->stream);
-        // as the one-shot call leaves its lanes on every return path
-        h->lanes_now = 1; h->nkB = 0; h->nk_seeds = false; h->nkeys.clear(); h->draw_offs_on = false;
-        h->inpB = 0; h->q_edit_init = false;
-        if (q->seed_last_written) h->seed_last_B = 0;
+        queue_leave_lane(h, q->rd.seed_last_written);
         h->owner = nullptr;
     }
     for (void* p : q->all_blocks) (void)hipFree(p);
-    if (q->mask_d) (void)hipFree(q->mask_d);
+    if (q->rd.mask) (void)hipFree((void*)q->rd.mask);
     delete q;
     return 0;
 }
