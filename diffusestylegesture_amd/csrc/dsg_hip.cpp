@@ -129,6 +129,16 @@ static Core classify_core(int D, int H, int Tp) {
     return Core::OTHER;
 }
 
+// The per-element noise streams of one step loop, as `dyn` takes them: B keys {seed lo, seed hi, stream lo, stream hi} at word 8 (seeds ==
+// false: the seed words come from args->seed; const_noise: element 0's key for everyone), pairs {offset, hold} (GemmArgs::draw_off, DrawOff)
+// at 8 + 4 max_batch, the start kernels' offsets at 8 + 6 max_batch.  offs / starts / holds are a clip queue's: with per-clip skip_timesteps
+// a slot that starts `hold` loop indices into the round draws its steps at offs = starts - hold and its start at starts.  Null in every other
+// keyed call: zeros, written with every keyed upload, so nothing of a queue's round outlives it on the device.  Host storage of the builder's
+struct NoiseTable {
+    int B = 0; bool seeds = false;      // B == 0: unkeyed
+    const unsigned *keys = nullptr, *offs = nullptr, *starts = nullptr;
+    const int* holds = nullptr;
+};
 struct dsg_handle {
     dsg_config cfg;
     int prec = 0, es = 4, kbk = 16;      // element size / k-block of the precision policy
@@ -156,7 +166,7 @@ struct dsg_handle {
     unsigned char* mask = nullptr; int mb = 1; int nomask = 0;
     // classifier-free guidance (dsg_set_window_cond_cfg): cfgB user batch elements + their unconditional twins = condB rows
     int cfgB = 0; float* cfg_scale = nullptr;
-    // inpainting constraint (dsg_set_inpainting): inpB user batch elements in the state's layout [inpB][T][Jp]; 0 = off.  Allocated on first use
+    // inpainting constraint (dsg_set_inpainting, the only writer of inpB): inpB user batch elements in the state's layout [inpB][T][Jp]; 0 = off.  Allocated on first use
     int inpB = 0; float* inp32 = nullptr; unsigned char *inp_mask = nullptr, *inp_stage = nullptr;
     // window hand-off of dsg_sample_clip (k_window_handoff): the previous window's last S frames [B][S][J], two copies used in turn (a hand-off reads
     // one and writes the other), and the stitched clip when the caller's `out` is host memory.  Allocated on first use
@@ -164,13 +174,11 @@ struct dsg_handle {
     bool clip_timing = false; double clip_ms = 0.0;      // the last sampling call was dsg_sample_clip: dsg_last_sample_ms reports the sum over its windows
     // clip-level inpainting constraint (dsg_set_clip_inpainting): the library's own copy in the stitched clip's coordinates [cinpB][cinp_frames][J];
     // cinpB == 0: off.  Allocated on first use, grown when needed (cinp_cap elements).  dsg_sample_clip cuts window c's constraint out of it into
-    // inp32 / inp_mask (k_clip_inp_window); inpB stays 0 outside that call
+    // inp32 / inp_mask (k_clip_inp_window)
     int cinpB = 0, cinp_frames = 0; float* cinp_motion = nullptr; unsigned char* cinp_mask = nullptr; size_t cinp_cap = 0;
     // clip-level init motion (dsg_set_clip_init): the library's own copy [cinitB][cinit_frames][J] in the stitched clip's coordinates; cinitB == 0:
-    // off.  Allocated on first use, grown when needed (cinit_cap elements).  Only dsg_sample_clip reads it: clip_init_c >= 0 (the window being
-    // started, for the windows of that call only) makes sample_prepare launch k_clip_x_in in place of k_x_in
+    // off.  Allocated on first use, grown when needed (cinit_cap elements).  Only dsg_sample_clip reads it (k_clip_x_in)
     int cinitB = 0, cinit_frames = 0; float* cinit_motion = nullptr; size_t cinit_cap = 0;
-    int clip_init_c = -1, clip_init_n_out = 0;
     int last_path = -1;                  // submission path of the last dsg_sample: 0 HIP launches, 1 AQL packets, 2 hipGraph replay
     bool last_nofence = false;           // ... and whether its packets went without fences
     int kset_req = DSG_KSET_AUTO;        // dsg_set_kernel_set: the kernel set every step of this handle runs (AUTO: by batch, select_kernels)
@@ -180,7 +188,6 @@ struct dsg_handle {
           *X1 = nullptr, *fwd_out = nullptr, *io_tmp = nullptr, *io_tmp2 = nullptr, *ext_noise = nullptr;
     size_t ext_noise_cap = 0;
     void *xsA = nullptr, *X0a = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *attn = nullptr, *hidden = nullptr;
-    int lanes_now = 1;                               // lanes of the dsg_sample_multi call in progress (1: dsg_sample / dsg_forward)
     float* ffn_part = nullptr; size_t ffn_slab = 0;      // [4][ffn_slab] partial linear2 results of k_ffn_part
     void* X1a = nullptr;                 // LayerNorm1 rows in the GEMM type, fragment-major (k_attn_op -> linear1)
     int* ctr = nullptr;                  // scratch counter for diagnostics
@@ -188,14 +195,8 @@ struct dsg_handle {
     int* t_arr = nullptr; unsigned* dyn = nullptr;
     // per-element noise streams (dsg_set_noise_streams): nkB user batch elements, 0 = off; nkeys = their keys {seed lo, seed hi, stream lo,
     // stream hi} (nk_seeds == false: the seed words come from args->seed, per call).  dyn_host: the staging copy of `dyn`
-    // (8 + 5 * max_batch words: + the draw offsets) every sampling call uploads
+    // (8 + 7 * max_batch words: + the draw offsets, see NoiseTable) every sampling call uploads
     int nkB = 0; bool nk_seeds = false; std::vector<unsigned> nkeys, dyn_host;
-    // per-element draw offsets of keyed noise (GemmArgs::draw_off; words 8 + 4 max_batch .. of `dyn`): dsg_sample_clip_queue sets them per round
-    // (draw_offs_on, for the rounds of that call only); every other keyed call uploads zeros.  On the device they are pairs {offset, hold}
-    // (DrawOff) for the pose head, and behind them (words 8 + 6 max_batch ..) the offsets of the start kernels once more: with per-clip
-    // skip_timesteps (dsg_sample_clip_queue_steps) a slot that starts `hold` loop indices into the round draws its steps at offset - hold
-    // (draw_offs) and its start at the offset itself (draw_starts); everywhere else hold is 0 and the two agree
-    bool draw_offs_on = false; std::vector<unsigned> draw_offs, draw_starts; std::vector<int> draw_holds;
     // What a lane holds for the rounds of a clip queue (dsg_sample_clip_queue*, dsg_queue_*; QueueRound fills all of it).  The device buffers
     // are allocated on first use (queue_lane_ready); the *_host vectors are the copies uploaded per round, which outlive the uploads
     struct Queue {
@@ -203,7 +204,6 @@ struct dsg_handle {
         std::vector<float> scale_host;                 // ... and its per-slot guidance scale
         HandoffSlot* slots = nullptr; std::vector<HandoffSlot> slots_host;      // the hand-off table (k_window_handoff_q)
         EditSlot* edits = nullptr; std::vector<EditSlot> edits_host;            // the edit table (k_clipq_inp_window / k_clipq_x_in)
-        bool edit_init = false;                        // for the rounds of a queue only: sample_prepare starts the round through k_clipq_x_in
         GatherSlot* gather = nullptr; std::vector<GatherSlot> gather_host;      // the gather table of a session (k_clipq_gather)
         unsigned char* stage = nullptr; size_t stage_cap = 0;      // a one-shot call's host-side edit tensors, staged (grown when needed)
     } cq;
@@ -442,6 +442,18 @@ static int dalloc(dsg_handle* h, T** p, size_t n_elems, bool zero = true) {
     else h->allocs.push_back(d);
     *p = (T*)d;
     return 0;
+}
+// A per-lane block that grows with its use (the clip-level copies, the queue's staging): the old one goes back at once -- the stream is
+// drained, nothing on it may still read it -- and *p becomes n_elems long, not zeroed.  The caller keeps the capacity
+template <class T>
+static int regrow(dsg_handle* h, T** p, size_t n_elems) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (void* old = *p) {
+        *p = nullptr;
+        h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), old), h->allocs.end());
+        (void)hipFree(old);
+    }
+    return dalloc(h, p, n_elems, false);
 }
 static int dalloc_bytes(dsg_handle* h, void** p, size_t bytes) {
     unsigned char* d = nullptr;
@@ -1170,7 +1182,8 @@ static int check_set(const dsg_handle* h, int set) {
         return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2: kernel sets LATENCY (latent_dim <= 256), TILE and ROWS (latent_dim 128 / 256) only");
     return 0;
 }
-static int select_kernels(const dsg_handle* h, int B, KernelSel& k) {
+// lanes: how many lanes share the GPU in this call (RunMode::lanes) -- the block shape of k_ffn, never the set or the arithmetic
+static int select_kernels(const dsg_handle* h, int B, int lanes, KernelSel& k) {
     int set = h->kset_req;
     if (set == DSG_KSET_AUTO) set = resolve_auto_set(h, B, 1);
     CHK(check_set(h, set));
@@ -1183,7 +1196,7 @@ static int select_kernels(const dsg_handle* h, int B, KernelSel& k) {
     const bool clip = have_attn_op_narrow(h) && h->env_clip_attn != 0;      // (A/B: DSG_CLIP_ATTN=0 = QKV GEMM + k_attn_op, round 4)
     // k_ffn on 64-row blocks: 4 lanes x >= 4000 token rows (4 x 64 clips: 981 -> 903 us per step of the 4 lanes; 1 x 64: 376 -> 432, 4 x 16: 334 -> 392,
     // 4 x 32 even -- profiles/r04_y2_sweep_ffn_rt4_*.log).  DSG_FFN_RT4=<rows> (test hook / A/B): from that many token rows at any lane count; 0: never
-    const bool rt4 = h->core == Core::C256 && (e >= 0 ? (e > 0 && rows >= e) : (h->lanes_now >= 4 && rows >= 4000));
+    const bool rt4 = h->core == Core::C256 && (e >= 0 ? (e > 0 && rows >= e) : (lanes >= 4 && rows >= 4000));
     switch (set) {
         case DSG_KSET_LATENCY:
             k.form = Form::MID;
@@ -1208,7 +1221,7 @@ static int select_kernels(const dsg_handle* h, int B, KernelSel& k) {
             // tiles of all lanes fit the 256 CUs in one round
             if (rows_wide_ok(h)) {      // (>= 3 lanes whose row tiles together exceed one round of the CUs: 32-row blocks, see layer_clip_w_ffn)
                 k.form = Form::CLIP_W_FFN;
-                k.ffn_rows = h->lanes_now >= 3 && h->lanes_now * cdiv(rows, 16) > 256 ? 32 : 16;
+                k.ffn_rows = lanes >= 3 && lanes * cdiv(rows, 16) > 256 ? 32 : 16;
             } else if (w2 || clip) {
                 k.form = Form::CLIP_FFN;
                 k.ffn_rows = 16;
@@ -2120,6 +2133,14 @@ static int run_step_p(dsg_handle* h, const StepCtx& c) {
     return run_step<PBF16>(h, c);
 }
 
+// the launch of a kernel that walks the state's [B][T][Jp / 4] quads grid-stride (the start kernels, the hand-offs, the constraint cuts)
+template <class Args>
+static int launch_state(dsg_handle* h, void (*kernel)(Args), int B, const Args& a) {
+    const size_t n = (size_t)B * h->T * (h->Jp / 4);
+    hipLaunchKernelGGL(kernel, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 static int launch_x_in(dsg_handle* h, const float* x, const float* init, int do_q, float qa, float qb, int use_philox,
                        NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B, const KernelSel& ks) {
     XInArgs a;
@@ -2128,46 +2149,31 @@ static int launch_x_in(dsg_handle* h, const float* x, const float* init, int do_
     a.x = x; a.init = init; a.do_q = do_q; a.qa = qa; a.qb = qb; a.use_philox = use_philox; a.nkey = nk; a.draw = draw;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.xs32 = h->xs32;
     a.xsA = is_bf16(h) ? h->xsA : nullptr;
-    const size_t n = (size_t)B * h->T * (h->Jp / 4);
-    const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
-    if (is_bf16(h)) hipLaunchKernelGGL((k_x_in<PBF16>), dim3(grid), dim3(256), 0, h->stream, a);
-    else hipLaunchKernelGGL((k_x_in<PF32>), dim3(grid), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_state(h, is_bf16(h) ? k_x_in<PBF16> : k_x_in<PF32>, B, a);
 }
-// window h->clip_init_c of a clip that starts from the handle's clip-level init motion (dsg_sample_clip): cut + q_sample + state write
-static ClipXInArgs clip_x_in_args(dsg_handle* h, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B,
-                                  const KernelSel& ks) {
+// window c of a clip of n_out frames that starts from the handle's clip-level init motion (dsg_sample_clip): cut + q_sample + state write
+static ClipXInArgs clip_x_in_args(dsg_handle* h, int c, int n_out, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs,
+                                  unsigned draw, int B, const KernelSel& ks) {
     ClipXInArgs a;
     a.keys = keys; a.offs = offs;
     a.init = h->cinit_motion; a.c_seed = h->c_seed; a.qa = qa; a.qb = qb; a.nkey = nk; a.draw = draw;
-    a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.S = h->S; a.n_out = h->clip_init_n_out; a.c = h->clip_init_c;
+    a.B = B; a.J = h->J; a.Jp = h->Jp; a.Jq = h->Jq; a.T = h->T; a.S = h->S; a.n_out = n_out; a.c = c;
     a.xs32 = h->xs32; a.xsA = is_bf16(h) ? h->xsA : nullptr;
     a.dupB = h->cfgB; a.xs_frag = ks.xs_frag ? 1 : 0;
     return a;
 }
-static int launch_clip_x_in(dsg_handle* h, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B,
-                            const KernelSel& ks) {
-    const ClipXInArgs a = clip_x_in_args(h, qa, qb, nk, keys, offs, draw, B, ks);
-    const size_t n = (size_t)B * h->T * (h->Jp / 4);
-    const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
-    if (is_bf16(h)) hipLaunchKernelGGL((k_clip_x_in<PBF16>), dim3(grid), dim3(256), 0, h->stream, a);
-    else hipLaunchKernelGGL((k_clip_x_in<PF32>), dim3(grid), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+static int launch_clip_x_in(dsg_handle* h, int c, int n_out, float qa, float qb, NoiseKey nk, const unsigned* keys, const unsigned* offs,
+                            unsigned draw, int B, const KernelSel& ks) {
+    const ClipXInArgs a = clip_x_in_args(h, c, n_out, qa, qb, nk, keys, offs, draw, B, ks);
+    return launch_state(h, is_bf16(h) ? k_clip_x_in<PBF16> : k_clip_x_in<PF32>, B, a);
 }
 // a round of dsg_sample_clip_queue_edit on a lane that runs a job with an init motion: init, length and window index per slot (h->cq.edits)
 static int launch_clip_x_in_q(dsg_handle* h, NoiseKey nk, const unsigned* keys, const unsigned* offs, unsigned draw, int B, const KernelSel& ks) {
     ClipXInQArgs a;
-    a.x = clip_x_in_args(h, 0.f, 0.f, nk, keys, offs, draw, B, ks);
-    a.x.init = nullptr; a.x.n_out = 0; a.x.c = 0;      // (per slot, from the table, as do_q and the q_sample pair)
+    a.x = clip_x_in_args(h, 0, 0, 0.f, 0.f, nk, keys, offs, draw, B, ks);
+    a.x.init = nullptr;      // (per slot, from the table, as n_out, c, do_q and the q_sample pair)
     a.slots = h->cq.edits;
-    const size_t n = (size_t)B * h->T * (h->Jp / 4);
-    const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
-    if (is_bf16(h)) hipLaunchKernelGGL((k_clipq_x_in<PBF16>), dim3(grid), dim3(256), 0, h->stream, a);
-    else hipLaunchKernelGGL((k_clipq_x_in<PF32>), dim3(grid), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_state(h, is_bf16(h) ? k_clipq_x_in<PBF16> : k_clipq_x_in<PF32>, B, a);
 }
 static int launch_x_out(dsg_handle* h, float* dst_dev, int B) {
     const size_t n = (size_t)B * h->J * h->T;
@@ -2262,14 +2268,9 @@ extern "C" int dsg_set_clip_inpainting(dsg_handle* h, const uint8_t* mask, const
     h->cinpB = 0; h->cinp_frames = 0;      // (a call that fails below leaves the constraint off, not half written)
     const size_t n = (size_t)B * n_frames * h->J;
     if (n > h->cinp_cap) {
-        // grown: the old copy goes back at once (nothing on the handle's stream may still read it)
-        HIPCHK(hipStreamSynchronize(h->stream));
-        void* old[2] = {h->cinp_motion, h->cinp_mask};
-        h->cinp_motion = nullptr; h->cinp_mask = nullptr; h->cinp_cap = 0;
-        for (void* p : old)
-            if (p) { h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), p), h->allocs.end()); (void)hipFree(p); }
-        CHK(dalloc(h, &h->cinp_motion, n, false));
-        CHK(dalloc(h, &h->cinp_mask, n, false));
+        h->cinp_cap = 0;
+        CHK(regrow(h, &h->cinp_motion, n));
+        CHK(regrow(h, &h->cinp_mask, n));
         h->cinp_cap = n;
     }
     // (each pointer on its own, as dsg_set_inpainting)
@@ -2297,15 +2298,8 @@ extern "C" int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int 
     h->cinitB = 0; h->cinit_frames = 0;      // (a call that fails below leaves it off, not half written)
     const size_t n = (size_t)B * n_frames * h->J;
     if (n > h->cinit_cap) {
-        // grown: the old copy goes back at once (nothing on the handle's stream may still read it)
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->cinit_motion) {
-            void* old = h->cinit_motion;
-            h->cinit_motion = nullptr; h->cinit_cap = 0;
-            h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), old), h->allocs.end());
-            (void)hipFree(old);
-        }
-        CHK(dalloc(h, &h->cinit_motion, n, false));
+        h->cinit_cap = 0;
+        CHK(regrow(h, &h->cinit_motion, n));
         h->cinit_cap = n;
     }
     CHK(order_after(h, stream));
@@ -2322,9 +2316,9 @@ extern "C" int dsg_set_clip_init(dsg_handle* h, const float* motion, int B, int 
 // indices stay per call (draw_base, draw_base + 1 + i, a clip's window c from draw_base + c (1 + n_run)).  Host arrays, copied here; the
 // table reaches the device with the `dyn` block of every sampling call (sample_prepare).  Reference counterpart: none (th.randn consumes one
 // global generator, gaussian_diffusion.py:704, :542).
-static void set_noise_key(dsg_handle* h, int b, uint64_t seed, uint64_t stream_id) {      // element b's entry of the key table
-    h->nkeys[4 * b] = (unsigned)(seed & 0xffffffffu); h->nkeys[4 * b + 1] = (unsigned)(seed >> 32);
-    h->nkeys[4 * b + 2] = (unsigned)(stream_id & 0xffffffffu); h->nkeys[4 * b + 3] = (unsigned)(stream_id >> 32);
+static void set_noise_key(unsigned* key, uint64_t seed, uint64_t stream_id) {      // an element's entry of a key table
+    key[0] = (unsigned)(seed & 0xffffffffu); key[1] = (unsigned)(seed >> 32);
+    key[2] = (unsigned)(stream_id & 0xffffffffu); key[3] = (unsigned)(stream_id >> 32);
 }
 extern "C" int dsg_set_noise_streams(dsg_handle* h, const uint64_t* seeds, const uint64_t* stream_ids, int B) {
     if (!h) return fail(DSG_E_INVALID, "null handle");
@@ -2333,7 +2327,7 @@ extern "C" int dsg_set_noise_streams(dsg_handle* h, const uint64_t* seeds, const
     if (B < 1 || B > h->Bmax)
         return fail(DSG_E_INVALID, "dsg_set_noise_streams: batch " + std::to_string(B) + " outside 1 .. max_batch (" + std::to_string(h->Bmax) + ")");
     h->nkeys.assign(4 * (size_t)B, 0u);
-    for (int b = 0; b < B; ++b) set_noise_key(h, b, seeds ? seeds[b] : 0, stream_ids ? stream_ids[b] : 0);
+    for (int b = 0; b < B; ++b) set_noise_key(&h->nkeys[4 * b], seeds ? seeds[b] : 0, stream_ids ? stream_ids[b] : 0);
     h->nk_seeds = seeds != nullptr;
     h->nkB = B;
     return 0;
@@ -2365,7 +2359,7 @@ extern "C" int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, floa
     CHK(to_dev(h, x, h->io_tmp, n, &xd));
     NoiseKey nk = {0, 0, 0, 0};
     StepCtx c; c.B = rows; c.out_mode = OUT_FORWARD; c.use_ctr = false; c.ext_noise = nullptr; c.const_noise = 0;
-    CHK(select_kernels(h, rows, c.ks));
+    CHK(select_kernels(h, rows, 1, c.ks));
     CHK(ensure_set_buffers(h, c.ks));
     CHK(launch_x_in(h, xd, nullptr, 0, 0.f, 0.f, 0, nk, nullptr, nullptr, 0, B, c.ks));
     CHK(run_step_p(h, c));
@@ -2421,6 +2415,24 @@ static int build_step_tables(dsg_handle* h, int mode, int skip, float eta, int* 
 // dsg_sample_multi runs the step loops of several handles ("lanes": own HSA queue each, shared weights) concurrently from one
 // host thread.
 // ---------------------------------------------------------------------------------------------------------
+// How one step loop is started and run: what sample_prepare is told beside the caller's dsg_sample_args.  Built by the caller for the call
+// (a window, a round) and gone with it: nothing of it is kept on the handle
+struct RunMode {
+    int lanes = 1;                     // the lanes that share the GPU in this call (select_kernels)
+    enum { X_IN, CLIP_X_IN, CLIPQ_X_IN } start = X_IN;      // k_x_in on the call's init_noise / init_image; k_clip_x_in on window c of the handle's
+    int c = 0, n_out = 0;                                    // clip-level init motion, a clip of n_out frames; k_clipq_x_in through the lane's edit table
+    int inpaint = 0;                   // > 0: the pose head's epilogue reads inp32 / inp_mask, which hold a constraint for that batch
+    NoiseTable noise;
+};
+// ... from the handle's user state: the sticky dsg_set_inpainting and dsg_set_noise_streams.  What dsg_sample / _multi run as it is and
+// dsg_sample_clip starts every window from
+static RunMode user_run_mode(const dsg_handle* h, int lanes) {
+    RunMode m;
+    m.lanes = lanes; m.inpaint = h->inpB;
+    m.noise.B = h->nkB; m.noise.seeds = h->nk_seeds; m.noise.keys = h->nkeys.data();
+    return m;
+}
+
 struct SampleJob {
     StepCtx c;
     int n_run = 0, B = 0, done = 0;      // n_run: steps THIS call runs; done: how many of them have been issued
@@ -2494,14 +2506,16 @@ static HostProf g_hp;
 #define HP_START() ((void)0)
 #define HP_LAP(i) ((void)0)
 #endif
-static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* stream, SampleJob& job) {
+static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, const RunMode& m, int B, void* stream, SampleJob& job) {
     if (!h || !a) return fail(DSG_E_INVALID, "dsg_sample: null argument");
     if (!h->finalized || !h->cond_set) return fail(DSG_E_STATE, "dsg_sample before finalize / set_window_cond");
     int rows = 0;
     CHK(rows_for(h, B, &rows));
-    if (h->inpB > 0 && h->inpB != B) return fail(DSG_E_INVALID, "batch differs from the batch of dsg_set_inpainting");
-    if (h->nkB > 0 && h->nkB != B)
-        return fail(DSG_E_INVALID, "batch " + std::to_string(B) + " differs from the batch of dsg_set_noise_streams (" + std::to_string(h->nkB) + ")");
+    const NoiseTable& nt = m.noise;
+    // (the user's batches: what user_run_mode took over; a window's cut and a queue's round bring the call's own B)
+    if (m.inpaint > 0 && m.inpaint != B) return fail(DSG_E_INVALID, "batch differs from the batch of dsg_set_inpainting");
+    if (nt.B > 0 && nt.B != B)
+        return fail(DSG_E_INVALID, "batch " + std::to_string(B) + " differs from the batch of dsg_set_noise_streams (" + std::to_string(nt.B) + ")");
     if (a->mode != DSG_MODE_DDPM && a->mode != DSG_MODE_DDIM) return fail(DSG_E_INVALID, "mode");
     // (dump points are allowed with DDIM: ddim_sample_loop_progressive is built on them; the Python ddim_sample_loop itself
     // refuses dump_steps like the reference, gaussian_diffusion.py:913-916)
@@ -2530,35 +2544,31 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     const int do_q = (first == 0 && (a->skip_timesteps > 0 || a->init_image)) ? 1 : 0;      // (a resumed chain starts from x_t as handed over)
     const int i0 = n_run - 1;
     KernelSel ksel;
-    CHK(select_kernels(h, rows, ksel));      // (first: the layout of the state shadow belongs to the kernel set)
+    CHK(select_kernels(h, rows, m.lanes, ksel));      // (first: the layout of the state shadow belongs to the kernel set)
     CHK(ensure_set_buffers(h, ksel));
     // what the loop reads from device memory instead of its arguments: the call's key, the draw index of step 0 and, with per-element noise
-    // streams, the key table (const_noise: element 0's stream for everyone) -- uploaded here because the start kernels read the table too
-    const int keyed = h->nkB > 0 ? 1 : 0;
+    // streams, the table (NoiseTable) -- uploaded here because the start kernels read the table too
+    const int keyed = nt.B > 0 ? 1 : 0;
     {
         unsigned* dyn = h->dyn_host.data();
         dyn[0] = nk.k0; dyn[1] = nk.k1; dyn[2] = nk.s0; dyn[3] = nk.s1; dyn[4] = a->draw_base + 1u;
-        for (int b = 0; b < h->nkB; ++b) {
-            const unsigned* k = h->nkeys.data() + 4 * (a->const_noise ? 0 : b);
-            dyn[8 + 4 * b] = h->nk_seeds ? k[0] : nk.k0; dyn[9 + 4 * b] = h->nk_seeds ? k[1] : nk.k1;
-            dyn[10 + 4 * b] = k[2]; dyn[11 + 4 * b] = k[3];
-        }
-        // the draw offsets behind the table: the queue's (dsg_sample_clip_queue, per round), zeros in every other keyed call -- written with
-        // every keyed upload, so that nothing of a queue call can outlive it on the device
         const size_t off0 = 8 + 4 * (size_t)h->Bmax, start0 = 8 + 6 * (size_t)h->Bmax;
-        for (int b = 0; b < h->nkB; ++b) {
-            dyn[off0 + 2 * b] = h->draw_offs_on ? h->draw_offs[b] : 0u;
-            dyn[off0 + 2 * b + 1] = h->draw_offs_on ? (unsigned)h->draw_holds[b] : 0u;
-            dyn[start0 + b] = h->draw_offs_on ? h->draw_starts[b] : 0u;
+        for (int b = 0; b < nt.B; ++b) {
+            const unsigned* k = nt.keys + 4 * (a->const_noise ? 0 : b);
+            dyn[8 + 4 * b] = nt.seeds ? k[0] : nk.k0; dyn[9 + 4 * b] = nt.seeds ? k[1] : nk.k1;
+            dyn[10 + 4 * b] = k[2]; dyn[11 + 4 * b] = k[3];
+            dyn[off0 + 2 * b] = nt.offs ? nt.offs[b] : 0u;
+            dyn[off0 + 2 * b + 1] = nt.holds ? (unsigned)nt.holds[b] : 0u;
+            dyn[start0 + b] = nt.starts ? nt.starts[b] : 0u;
         }
-        HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? start0 + (size_t)h->nkB : 5) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? start0 + (size_t)nt.B : 5) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
     }
     const unsigned* keys_d = keyed ? h->dyn + 8 : nullptr;
     const unsigned* offs_d = keyed ? h->dyn + 8 + 6 * (size_t)h->Bmax : nullptr;      // (the start kernels': GemmArgs::draw_off is the pair table)
-    if (h->cq.edit_init)          // (a round of the clip queue on a lane that runs a job with an init motion, or of a call with per-clip skips)
+    if (m.start == RunMode::CLIPQ_X_IN)      // (a round of the clip queue on a lane that runs a job with an init motion, or of a call with per-clip skips)
         CHK(launch_clip_x_in_q(h, nk, keys_d, offs_d, a->draw_base, B, ksel));
-    else if (h->clip_init_c >= 0) // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
-        CHK(launch_clip_x_in(h, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
+    else if (m.start == RunMode::CLIP_X_IN)  // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
+        CHK(launch_clip_x_in(h, m.c, m.n_out, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
     else
         CHK(launch_x_in(h, noise_d, init_d, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0],
                         noise_d ? 0 : 1, nk, keys_d, offs_d, a->draw_base, B, ksel));
@@ -2582,7 +2592,7 @@ static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, int B, void* 
     c.B = rows; c.out_mode = a->mode == DSG_MODE_DDPM ? OUT_DDPM : OUT_DDIM; c.use_ctr = true; c.ext_noise = ext;
     c.const_noise = a->const_noise; c.keyed = keyed; c.clip_x0 = a->clip_denoised ? 1 : 0;
     c.no_noise = (a->mode == DSG_MODE_DDIM && a->eta == 0.f && !ext) ? 1 : 0;
-    c.inpaint = h->inpB > 0 ? 1 : 0;      // (the AQL argument blocks are recorded anew below for every call: on / off needs no invalidation)
+    c.inpaint = m.inpaint > 0 ? 1 : 0;     // (the AQL argument blocks are recorded anew below for every call: on / off needs no invalidation)
     c.ks = ksel;
     n_run = n_iter;                          // from here on: the steps of this call (the tables keep the whole chain: h->n_run)
     job.n_run = n_iter; job.B = B; job.done = 0; job.first = first;
@@ -2745,7 +2755,7 @@ extern "C" int dsg_sample(dsg_handle* h, const dsg_sample_args* a, float* out, i
     if (!h || !a || !out) return fail(DSG_E_INVALID, "dsg_sample: null argument");
     CHK(owned_by_queue(h));
     SampleJob job;
-    CHK(sample_prepare(h, a, B, stream, job));
+    CHK(sample_prepare(h, a, user_run_mode(h, 1), B, stream, job));
     CHK(run_lanes(&h, 1, a, &job));
     return sample_finish(h, out, stream, job);
 }
@@ -2755,11 +2765,6 @@ extern "C" int dsg_sample(dsg_handle* h, const dsg_sample_args* a, float* out, i
 // queues' dependent packet chains overlap on the GPU); with HIP launches the lanes' streams are fed step by step.  Every lane
 // runs the kernel set ITS handle selects (dsg_set_kernel_set / the batch): the call changes nothing about the arithmetic, so
 // lane i's sample is bit-identical to dsg_sample(lanes[i], &args[i], ...) on its own.
-struct LanesNow {          // how many lanes share the GPU during a call (select_kernels: block shape of k_ffn; never the arithmetic)
-    dsg_handle** hs; int n;
-    LanesNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) { for (int i = 0; i < n; ++i) hs[i]->lanes_now = n; }
-    ~LanesNow() { for (int i = 0; i < n; ++i) hs[i]->lanes_now = 1; }
-};
 extern "C" int dsg_sample_multi(dsg_handle** hs, int n, const dsg_sample_args* args, float** outs, int B, void* stream) {
     if (!hs || !args || !outs || n <= 0) return fail(DSG_E_INVALID, "dsg_sample_multi: bad argument");
     for (int i = 0; i < n; ++i) {
@@ -2770,8 +2775,7 @@ extern "C" int dsg_sample_multi(dsg_handle** hs, int n, const dsg_sample_args* a
     }
     if (n > 16) return fail(DSG_E_INVALID, "dsg_sample_multi: at most 16 lanes (4 overlap on the hardware; put further clips into the lanes' batches)");
     std::vector<SampleJob> jobs(n);
-    LanesNow lanes_now(hs, n);
-    for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &args[i], B, stream, jobs[i]));
+    for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &args[i], user_run_mode(hs[i], n), B, stream, jobs[i]));
     CHK(run_lanes(hs, n, args, jobs.data()));
     for (int i = 0; i < n; ++i) CHK(sample_finish(hs[i], outs[i], stream, jobs[i]));
     return 0;
@@ -2789,20 +2793,14 @@ static int launch_handoff(dsg_handle* h, float* clip_out, int B, int n_out, int 
     a.xs32 = h->xs32; a.tail_in = h->clip_tail[(c + 1) & 1]; a.tail_out = h->clip_tail[c & 1]; a.c_seed = h->c_seed; a.clip_out = clip_out;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S; a.n_out = n_out; a.c = c;
     a.root_shift = root_shift ? 1 : 0; a.is_first = c == 0 ? 1 : 0; a.is_last = c == K - 1 ? 1 : 0; a.keep_last_tail = keep_last_tail ? 1 : 0;
-    const size_t n = (size_t)B * h->T * (h->Jp / 4);
-    hipLaunchKernelGGL(k_window_handoff, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_state(h, k_window_handoff, B, a);
 }
 
 static int launch_clip_inp_window(dsg_handle* h, int B, int n_out, int c) {
     ClipInpArgs a;
     a.motion = h->cinp_motion; a.mask = h->cinp_mask; a.inp32 = h->inp32; a.inp_mask = h->inp_mask;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S; a.n_out = n_out; a.c = c;
-    const size_t n = (size_t)B * h->T * (h->Jp / 4);
-    hipLaunchKernelGGL(k_clip_inp_window, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_state(h, k_clip_inp_window, B, a);
 }
 
 // the two copies of the hand-off's tail, on first use: for the window loop below and for the rounds of a queue
@@ -2885,33 +2883,28 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
     }
     std::vector<SampleJob> jobs(n);
     std::vector<dsg_sample_args> wargs(args, args + n);
-    LanesNow lanes_now(hs, n);
+    // Every window runs as dsg_sample_multi would run it on the lane's user state (the noise streams; inpB == 0, checked above), but for:
     // Lanes with a clip-level constraint: window c's slice goes into inp32 / inp_mask where the window's conditioning is set -- on the handle's
     // stream, which sample_prepare drains before the first packet, whose acquire covers it like the conditioning; the pointers stay, only the
-    // contents change -- and the epilogue's inpainting is on (inpB: StepCtx::inpaint, GKey flag 32) for the windows of this call only: every
-    // lane came in with inpB == 0 (checked above) and leaves with it, on error returns too
-    struct ClipInpaintNow {
-        dsg_handle** hs; int n;
-        ClipInpaintNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) {}
-        ~ClipInpaintNow() { for (int i = 0; i < n; ++i) hs[i]->inpB = 0; }
-    } clip_inpaint_now(hs, n);
+    // contents change -- and the epilogue's inpainting is on (StepCtx::inpaint, GKey flag 32).
     // Lanes with a clip-level init motion: sample_prepare starts window c from q_sample of its slice (k_clip_x_in reads c_seed for the frames in
-    // front of the clip: window 0's y['seed'], uploaded above on the same stream).  clip_init_c is -1 outside this call, on error returns too
-    struct ClipInitNow {
-        dsg_handle** hs; int n;
-        ClipInitNow(dsg_handle** hs_, int n_) : hs(hs_), n(n_) {}
-        ~ClipInitNow() { for (int i = 0; i < n; ++i) hs[i]->clip_init_c = -1; }
-    } clip_init_now(hs, n);
+    // front of the clip: window 0's y['seed'], uploaded above on the same stream)
+    std::vector<RunMode> modes(n);
+    for (int i = 0; i < n; ++i) {
+        modes[i] = user_run_mode(hs[i], n);
+        if (hs[i]->cinpB > 0) modes[i].inpaint = B;
+        if (hs[i]->cinitB > 0) { modes[i].start = RunMode::CLIP_X_IN; modes[i].n_out = n_out; }
+    }
     for (int c = 0; c < K; ++c) {
         for (int i = 0; i < n; ++i) {
             dsg_handle* h = hs[i];
             const float* audio_c = audios[i] + (size_t)c * B * h->Ta * h->As;
             CHK(set_window_cond(h, styles[i], h->c_seed, audio_c, mask_local, mask_batch, B, 0, scales ? scales[i] : nullptr, stream));
-            if (h->cinpB > 0) { CHK(launch_clip_inp_window(h, B, n_out, c)); h->inpB = B; }
-            if (h->cinitB > 0) { h->clip_init_c = c; h->clip_init_n_out = n_out; }
+            if (h->cinpB > 0) CHK(launch_clip_inp_window(h, B, n_out, c));
+            modes[i].c = c;
             wargs[i].draw_base = args[i].draw_base + (uint32_t)c * (uint32_t)(1 + n_run);      // what K consecutive dsg_sample calls consume
         }
-        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, jobs[i]));
+        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], modes[i], B, stream, jobs[i]));
         CHK(run_lanes(hs, n, wargs.data(), jobs.data()));
         for (int i = 0; i < n; ++i) {
             CHK(clip_window_timed(hs[i]));
@@ -3006,24 +2999,20 @@ static int launch_clip_inp_window_q(dsg_handle* h, int B) {
     ClipInpQArgs a;
     a.slots = h->cq.edits; a.inp32 = h->inp32; a.inp_mask = h->inp_mask;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S;
-    const size_t n = (size_t)B * h->T * (h->Jp / 4);
-    hipLaunchKernelGGL(k_clipq_inp_window, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_state(h, k_clipq_inp_window, B, a);
 }
 static int launch_handoff_q(dsg_handle* h, int B, int round, int root_shift, int keep_last_tail) {
     HandoffQArgs a;
     a.xs32 = h->xs32; a.tail_in = h->clip_tail[(round + 1) & 1]; a.tail_out = h->clip_tail[round & 1]; a.c_seed = h->c_seed; a.slots = h->cq.slots;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S;
     a.root_shift = root_shift ? 1 : 0; a.keep_last_tail = keep_last_tail ? 1 : 0;
-    const size_t n = (size_t)B * h->T * (h->Jp / 4);
-    hipLaunchKernelGGL(k_window_handoff_q, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_state(h, k_window_handoff_q, B, a);
 }
 
 // The checks of a queue on its lanes, B, guided and args, and on one job: written once for dsg_sample_clip_queue_steps and the session
-// (dsg_queue_open / dsg_queue_submit), which make the same refusals with the same messages
+// (dsg_queue_open / dsg_queue_submit), which make the same refusals with the same messages.  A lane that carries noise streams or a
+// constraint (and dsg_sample_clip's lane with inpB > 0) is refused as a matter of the API -- the call would have to say which of the two
+// wins -- not for safety: a round's RunMode neither reads nor writes that state
 static int clip_queue_check_lanes(dsg_handle** hs, int n, int B, int guided, const dsg_sample_args* args) {
     for (int i = 0; i < n; ++i) {
         dsg_handle* h = hs[i];
@@ -3085,15 +3074,6 @@ static int queue_lane_ready(dsg_handle* h, int flags) {
     }
     return 0;
 }
-// ... and the lane as a queue found it: what QueueRound sets on a lane -- lanes_now, the keyed table and its draw offsets, the epilogue's
-// inpainting (inpB), the start through the edit table -- is put back.  Every lane came in unkeyed and with inpB == 0
-// (clip_queue_check_lanes).  Variant 5: the rows of c_seed_last now hold the jobs' snippets, so the lane asks for dsg_set_seed_last again,
-// as a fresh handle does
-static void queue_leave_lane(dsg_handle* h, bool seed_last_written) {
-    h->lanes_now = 1; h->nkB = 0; h->nk_seeds = false; h->nkeys.clear(); h->draw_offs_on = false;
-    h->inpB = 0; h->cq.edit_init = false;
-    if (seed_last_written) h->seed_last_B = 0;
-}
 
 // A job's tensor as the device reads it: where it is when that is device memory (or null), else its copy, made on h's stream, in the
 // `bytes` that room(bytes, &p) hands out -- a piece of the lane's staging (the one-shot call) or a block of the session's
@@ -3126,21 +3106,31 @@ struct QueueRound {
     std::vector<SampleJob> sjobs;
     int (*cond)(dsg_handle* h, int B, const SlotWork* const* lane) = nullptr;      // the lane's slots -> style / audio / c_seed / c_seed_last
     // lane_init[i]: lane i starts its rounds through the edit table (k_clipq_x_in), else through k_x_in; lane_inp[i]: the table's constraint is
-    // cut and the epilogue's inpainting is on (inpB).  lane_inp empty: decided per round, by whether a slot of the lane brings a mask
+    // cut and the epilogue's inpainting is on.  lane_inp empty: decided per round, by whether a slot of the lane brings a mask
     std::vector<char> lane_inp, lane_init;
+    // per lane: how the round's loop is started and run, and the storage of its noise table -- every slot its job's key and draw offsets
+    struct Draws { std::vector<unsigned> keys, offs, starts; std::vector<int> holds; };
+    std::vector<Draws> draws;
+    std::vector<RunMode> modes;
     bool seed_last_written = false;     // variant 5: some round has put a job's snippet into c_seed_last
     int64_t steps_run = 0;              // the step-loop length summed over the rounds since the caller last reset it
     std::vector<const SlotWork*> lane;
 
     QueueRound(dsg_handle** hs_, int n, int B_, const uint8_t* mask_, int guided_, const dsg_sample_args& a, int root_shift_, int keep_last_tail_)
         : hs(hs_, hs_ + n), B(B_), guided(guided_ ? 1 : 0), root_shift(root_shift_ ? 1 : 0), keep_last_tail(keep_last_tail_ ? 1 : 0), mask(mask_),
-          args(a), wargs(n, a), sjobs(n), lane_init(n, 0), lane(B_) {
-        for (dsg_handle* h : hs) {
-            h->cq.slots_host.resize(B); h->cq.edits_host.resize(B);
-            h->cq.scale_host.assign(B, 1.f);
-            h->draw_offs.resize(B); h->draw_starts.resize(B); h->draw_holds.resize(B);
-            h->lanes_now = n;
+          args(a), wargs(n, a), sjobs(n), lane_init(n, 0), draws(n), modes(n), lane(B_) {
+        for (int i = 0; i < n; ++i) {
+            dsg_handle::Queue& q = hs[i]->cq;
+            q.slots_host.resize(B); q.edits_host.resize(B);
+            q.scale_host.assign(B, 1.f);
+            Draws& d = draws[i];
+            d.keys.resize(4 * (size_t)B); d.offs.resize(B); d.starts.resize(B); d.holds.resize(B);
         }
+    }
+    // The lanes as the queue leaves them, on every path out of the one-shot call and at the session's close.  Variant 5: the rows of
+    // c_seed_last now hold the jobs' snippets, so the lanes ask for dsg_set_seed_last again, as a fresh handle does
+    void leave() {
+        if (seed_last_written) for (dsg_handle* h : hs) h->seed_last_B = 0;
     }
     // in front of the rounds of one call: they follow whatever `stream` still does to the tensors they read
     int begin(void* stream) {
@@ -3156,8 +3146,9 @@ struct QueueRound {
         for (int i = 0; i < n; ++i) {
             dsg_handle* h = hs[i];
             dsg_handle::Queue& q = h->cq;
+            Draws& d = draws[i];
             wargs[i].skip_timesteps = s_r;
-            h->nkeys.assign(4 * (size_t)B, 0u);
+            d.keys.assign(4 * (size_t)B, 0u);
             bool inp = !lane_inp.empty() && lane_inp[i];
             for (int b = 0; b < B; ++b) {
                 const SlotWork* w = lane[b] = slots[(size_t)b * n + i];
@@ -3169,32 +3160,32 @@ struct QueueRound {
                 const int skip = w ? w->skip : s_r, i0 = h->sched.n - skip - 1;
                 e.qa = (float)h->sched.sqrt_ac[i0]; e.qb = (float)h->sched.sqrt_1mac[i0]; e.do_q = skip > 0 ? 1 : 0;
                 q.slots_host[b] = HandoffSlot{nullptr, 0, 0, HQ_DEAD, 0};
-                h->draw_offs[b] = 0u; h->draw_starts[b] = 0u; h->draw_holds[b] = 0;
+                d.offs[b] = 0u; d.starts[b] = 0u; d.holds[b] = 0;
                 if (!w) continue;
                 const int c = w->c;
                 e.c = c;
                 q.scale_host[b] = w->job.scale;
-                set_noise_key(h, b, w->job.seed, w->job.stream_id);
+                set_noise_key(&d.keys[4 * b], w->job.seed, w->job.stream_id);
                 // what dsg_sample_clip alone consumes before window c; its step i is the round's loop index i + hold
-                h->draw_holds[b] = skip - s_r;
-                h->draw_starts[b] = (uint32_t)c * (uint32_t)(1 + w->n_run);
-                h->draw_offs[b] = h->draw_starts[b] - (uint32_t)h->draw_holds[b];
+                d.holds[b] = skip - s_r;
+                d.starts[b] = (uint32_t)c * (uint32_t)(1 + w->n_run);
+                d.offs[b] = d.starts[b] - (uint32_t)d.holds[b];
                 q.slots_host[b] = HandoffSlot{w->clip, w->ed.n_out, c, (c == 0 ? HQ_FIRST : 0) | (c == w->job.K - 1 ? HQ_LAST : 0), 0};
                 if (c == 0 && variant5) seed_last_written = true;
                 if (lane_inp.empty() && w->ed.mask) inp = true;
             }
-            h->nkB = B; h->nk_seeds = true; h->draw_offs_on = true;
             if (variant5) h->seed_last_B = B;
             HIPCHK(hipMemcpyAsync(q.slots, q.slots_host.data(), (size_t)B * sizeof(HandoffSlot), hipMemcpyHostToDevice, h->stream));
             CHK(cond(h, B, lane.data()));
             CHK(set_window_cond(h, q.style, h->c_seed, q.audio, mask, 1, B, 0, guided ? q.scale_host.data() : nullptr, stream));
             if (inp || lane_init[i])
                 HIPCHK(hipMemcpyAsync(q.edits, q.edits_host.data(), (size_t)B * sizeof(EditSlot), hipMemcpyHostToDevice, h->stream));
-            h->inpB = 0;
-            if (inp) { CHK(queue_lane_ready(h, QL_INP)); CHK(launch_clip_inp_window_q(h, B)); h->inpB = B; }
-            q.edit_init = lane_init[i] != 0;
+            if (inp) { CHK(queue_lane_ready(h, QL_INP)); CHK(launch_clip_inp_window_q(h, B)); }
+            RunMode& m = modes[i];
+            m.lanes = n; m.start = lane_init[i] ? RunMode::CLIPQ_X_IN : RunMode::X_IN; m.inpaint = inp ? B : 0;
+            m.noise = NoiseTable{B, true, d.keys.data(), d.offs.data(), d.starts.data(), d.holds.data()};
         }
-        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], B, stream, sjobs[i]));
+        for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], modes[i], B, stream, sjobs[i]));
         CHK(run_lanes(hs.data(), n, wargs.data(), sjobs.data()));
         for (int i = 0; i < n; ++i) {
             CHK(clip_window_timed(hs[i]));
@@ -3292,7 +3283,7 @@ extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_cli
     QueueRound rd(hs, n, B, mask_local, guided, *args, root_shift, keep_last_tail);
     struct QueueNow {      // the lanes leave the queue on every return path
         QueueRound& rd;
-        ~QueueNow() { for (dsg_handle* h : rd.hs) queue_leave_lane(h, rd.seed_last_written); }
+        ~QueueNow() { rd.leave(); }
     } queue_now{rd};
     rd.cond = cond_from_caller;
     rd.lane_inp.assign(n, 0);
@@ -3318,15 +3309,8 @@ extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_cli
             if (!rd.lane_inp[i] && !rd.lane_init[i]) continue;
             CHK(queue_lane_ready(h, QL_EDITS));
             if (need[i] > h->cq.stage_cap) {
-                // grown: the old staging goes back at once (nothing on the handle's stream may still read it)
-                HIPCHK(hipStreamSynchronize(h->stream));
-                if (h->cq.stage) {
-                    void* old = h->cq.stage;
-                    h->cq.stage = nullptr; h->cq.stage_cap = 0;
-                    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), old), h->allocs.end());
-                    (void)hipFree(old);
-                }
-                CHK(dalloc(h, &h->cq.stage, need[i], false));
+                h->cq.stage_cap = 0;
+                CHK(regrow(h, &h->cq.stage, need[i]));
                 h->cq.stage_cap = need[i];
             }
         }
@@ -3646,9 +3630,9 @@ extern "C" int dsg_queue_close(dsg_queue* q) {
     (void)hipSetDevice(q->rd.hs[0]->cfg.device);
     for (dsg_handle* h : q->rd.hs) {
         (void)hipStreamSynchronize(h->stream);
-        queue_leave_lane(h, q->rd.seed_last_written);
         h->owner = nullptr;
     }
+    q->rd.leave();
     for (void* p : q->all_blocks) (void)hipFree(p);
     if (q->rd.mask) (void)hipFree((void*)q->rd.mask);
     delete q;
