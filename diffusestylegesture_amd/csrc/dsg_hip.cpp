@@ -3001,9 +3001,9 @@ static int launch_clip_inp_window_q(dsg_handle* h, int B) {
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S;
     return launch_state(h, k_clipq_inp_window, B, a);
 }
-static int launch_handoff_q(dsg_handle* h, int B, int round, int root_shift, int keep_last_tail) {
-    HandoffQArgs a;
-    a.xs32 = h->xs32; a.tail_in = h->clip_tail[(round + 1) & 1]; a.tail_out = h->clip_tail[round & 1]; a.c_seed = h->c_seed; a.slots = h->cq.slots;
+static int launch_handoff_q(dsg_handle* h, int B, int root_shift, int keep_last_tail) {
+    HandoffQArgs a;      // (which tail a slot reads and which it writes: per slot, by its window index -- in the kernel)
+    a.xs32 = h->xs32; a.tail0 = h->clip_tail[0]; a.tail1 = h->clip_tail[1]; a.c_seed = h->c_seed; a.slots = h->cq.slots;
     a.B = B; a.J = h->J; a.Jp = h->Jp; a.T = h->T; a.S = h->S;
     a.root_shift = root_shift ? 1 : 0; a.keep_last_tail = keep_last_tail ? 1 : 0;
     return launch_state(h, k_window_handoff_q, B, a);
@@ -3040,9 +3040,9 @@ static int clip_queue_check_lanes(dsg_handle** hs, int n, int B, int guided, con
     if (args->mode != DSG_MODE_DDPM && args->mode != DSG_MODE_DDIM) return fail(DSG_E_INVALID, "mode");
     return 0;
 }
-static int clip_queue_check_job(const dsg_clip_job& q, const dsg_clip_edit* edit, int64_t j, int variant5) {
+static int clip_queue_check_job(const dsg_clip_job& q, const dsg_clip_edit* edit, int64_t j, int variant5, bool no_audio_yet = false) {
     if (q.K < 1) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has K < 1");
-    if (!q.style || !q.audio || !q.out) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has a null style / audio / out");
+    if (!q.style || (!q.audio && !no_audio_yet) || !q.out) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: job " + std::to_string(j) + " has a null style / audio / out");
     if (variant5 && !q.seed_last) return fail(DSG_E_INVALID, "dsg_sample_clip_queue: variant 5 needs seed_last for every job (job " + std::to_string(j) + " has none)");
     if (edit && !edit->inp_mask != !edit->inp_motion)
         return fail(DSG_E_INVALID, "dsg_sample_clip_queue_edit: inp_mask and inp_motion go together (both NULL: no constraint); job " + std::to_string(j) + " has one of them");
@@ -3056,6 +3056,7 @@ struct SlotWork {
     float* clip = nullptr;      // [ed.n_out][J] on the device: where the hand-off writes
     int c = 0;                  // the window the slot stands on
     int skip = 0, n_run = 0;    // the job's skip_timesteps and the steps of one of its windows (schedule length - skip)
+    const float* win_audio = nullptr;      // a live job of a session: the audio of window c, where it is read (null: job.audio + c * n_audio)
 };
 
 // The lane's device buffers for the rounds of a queue, on first use
@@ -3138,7 +3139,7 @@ struct QueueRound {
         for (dsg_handle* h : hs) { h->clip_ms = 0.0; CHK(order_after(h, stream)); }
         return 0;
     }
-    int run(const SlotWork* const* slots, int round, void* stream) {      // slots: [B][lanes] (global slot s: lane s % n, position s / n); round: its parity picks the tail
+    int run(const SlotWork* const* slots, void* stream) {      // slots: [B][lanes] (global slot s: lane s % n, position s / n)
         const int n = (int)hs.size(), n_sched = hs[0]->sched.n, variant5 = hs[0]->cfg.variant == 5;
         int s_r = n_sched;      // (the callers run no round without a live slot)
         for (int s = 0; s < n * B; ++s) if (slots[s]) s_r = std::min(s_r, slots[s]->skip);
@@ -3189,7 +3190,7 @@ struct QueueRound {
         CHK(run_lanes(hs.data(), n, wargs.data(), sjobs.data()));
         for (int i = 0; i < n; ++i) {
             CHK(clip_window_timed(hs[i]));
-            CHK(launch_handoff_q(hs[i], B, round, root_shift, keep_last_tail));
+            CHK(launch_handoff_q(hs[i], B, root_shift, keep_last_tail));
         }
         return 0;
     }
@@ -3333,7 +3334,7 @@ extern "C" int dsg_sample_clip_queue_steps(dsg_handle** hs, int n, const dsg_cli
             slots[s] = j < 0 ? nullptr : &work[j];
             if (j >= 0) work[j].c = r - first[j];
         }
-        CHK(rd.run(slots.data(), r, stream));
+        CHK(rd.run(slots.data(), stream));
     }
     for (int j = 0; j < n_jobs; ++j)
         if (work[j].clip != jobs[j].out) CHK(from_dev(hs[slot[j] % n], jobs[j].out, work[j].clip, n_clip[j]));      // (on the stream of the lane that wrote it)
@@ -3359,7 +3360,10 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
 //              the device (cond_gathered: k_clipq_gather, one launch per lane);
 //   edits      every lane starts every round through the edit table (k_clipq_x_in): a job with its own skip or an init motion may arrive in
 //              any round.  The constraint is cut in the rounds in which a slot of the lane brings one;
-//   outputs    a host `out` is fed from a session-owned device clip, the rows that became final copied after every round.
+//   outputs    a host `out` is fed from a session-owned device clip, the rows that became final copied after every round;
+//   live jobs  (dsg_queue_submit_live / _append / _finish) get their windows one by one: a pending one is placed once it has a window, a
+//              running one without a window to run is a dead slot for that round (its tail stays where its last window left it: the
+//              hand-off picks the tail buffers per slot, by the window index), and K is unknown until finish.
 // ---------------------------------------------------------------------------------------------------------
 struct QBlock { void* p; size_t cap; };
 struct QJob {
@@ -3367,6 +3371,16 @@ struct QJob {
     float* host_out = nullptr;        // the caller's host `out` (null: a device `out`, written by the hand-off itself)
     int state = DSG_JOB_PENDING, rows_ready = 0, rows_copied = 0, slot = -1, first_round = -1;
     std::vector<QBlock> blocks;       // the staging the job holds; back to the session's free list when it is done or cancelled
+    // A live job (dsg_queue_submit_live): its windows arrive one by one (dsg_queue_append) until dsg_queue_finish says how many there are.
+    // Until then w.job.K is INT32_MAX -- no window is the last one -- and w.ed.n_out is n_out(capacity); finish sets both to the clip's.
+    // wins[c]: what window c runs on, every pointer as the device reads it; the round puts it into w.job.style / .scale and w.win_audio
+    struct Win { const float* audio; const float* style; float scale; };
+    bool live = false, finished = false;
+    int capacity = 0;
+    const float* style0 = nullptr;    // the job's own style and scale: what window 0 runs on unless it brings its own
+    float scale0 = 1.f;
+    std::vector<Win> wins;            // the windows given so far
+    bool has_window() const { return !live || w.c < (int)wins.size(); }      // something to run in the next round
 };
 struct dsg_queue {
     QueueRound rd;                    // the lanes, B, guided, args, root_shift, keep_last_tail; rd.mask: the session's device copy of mask_local
@@ -3445,7 +3459,7 @@ static int cond_gathered(dsg_handle* h, int B, const SlotWork* const* lane) {
     q.gather_host.resize(B);
     for (int b = 0; b < B; ++b) {
         const SlotWork* w = lane[b];
-        q.gather_host[b] = w ? GatherSlot{w->job.style, w->job.audio + w->c * n_audio, w->job.seed0, w->job.seed_last, GQ_LIVE | (w->c == 0 ? GQ_FIRST : 0), 0}
+        q.gather_host[b] = w ? GatherSlot{w->job.style, w->win_audio ? w->win_audio : w->job.audio + w->c * n_audio, w->job.seed0, w->job.seed_last, GQ_LIVE | (w->c == 0 ? GQ_FIRST : 0), 0}
                              : GatherSlot{nullptr, nullptr, nullptr, nullptr, 0, 0};
     }
     HIPCHK(hipMemcpyAsync(q.gather, q.gather_host.data(), (size_t)B * sizeof(GatherSlot), hipMemcpyHostToDevice, h->stream));
@@ -3484,11 +3498,15 @@ extern "C" int dsg_queue_open(dsg_handle** hs, int n, int B, const uint8_t* mask
     return 0;
 }
 
-extern "C" int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg_clip_edit* edit, int skip_timesteps, int64_t* ticket, void* stream) {
+// dsg_queue_submit and dsg_queue_submit_live (n_given >= 0: job->K is the capacity and job->audio holds the first n_given windows)
+static int queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg_clip_edit* edit, int skip_timesteps, int n_given, int64_t* ticket, void* stream) {
     if (!q || !job || !ticket) return fail(DSG_E_INVALID, "dsg_queue_submit: null argument");
     dsg_handle* h0 = q->rd.hs[0];
     const int64_t t = (int64_t)q->jobs.size();
-    CHK(clip_queue_check_job(*job, edit, t, h0->cfg.variant == 5));
+    const bool live = n_given >= 0;
+    CHK(clip_queue_check_job(*job, edit, t, h0->cfg.variant == 5, live && n_given == 0));
+    if (live && n_given > job->K)
+        return fail(DSG_E_INVALID, "dsg_queue_submit_live: job " + std::to_string(t) + " brings " + std::to_string(n_given) + " windows for a capacity of " + std::to_string(job->K));
     const int n_sched = h0->sched.n, skip = skip_timesteps >= 0 ? skip_timesteps : q->rd.args.skip_timesteps;
     if (skip < 0 || skip >= n_sched)
         return fail(DSG_E_INVALID, "dsg_sample_clip_queue: skip_timesteps out of range: job " + std::to_string(t) + " has skip_timesteps " + std::to_string(skip) +
@@ -3515,7 +3533,9 @@ extern "C" int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg
     if (!rc) rc = staged(h0, job->style, (size_t)h0->cfg.style_dim_in * sizeof(float), room, (const void**)&w.job.style);
     if (!rc) rc = staged(h0, job->seed0, n_tail * sizeof(float), room, (const void**)&w.job.seed0);
     if (!rc) rc = staged(h0, job->seed_last, n_tail * sizeof(float), room, (const void**)&w.job.seed_last);
-    if (!rc) rc = staged(h0, job->audio, (size_t)job->K * n_audio * sizeof(float), room, (const void**)&w.job.audio);
+    const int n_windows = live ? n_given : job->K;      // the windows job->audio holds
+    if (n_windows == 0) w.job.audio = nullptr;
+    else if (!rc) rc = staged(h0, job->audio, (size_t)n_windows * n_audio * sizeof(float), room, (const void**)&w.job.audio);
     if (!rc && edit) {
         rc = staged(h0, edit->inp_motion, n_clip * sizeof(float), room, (const void**)&w.ed.motion);
         if (!rc) rc = staged(h0, edit->init_motion, n_clip * sizeof(float), room, (const void**)&w.ed.init);
@@ -3534,9 +3554,112 @@ extern "C" int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg
     if (rc) { queue_give(q, jb); return rc; }      // the session is as it was (the blocks taken so far wait in its free list)
     // device tensors of the job are read where they are: whatever `stream` still does to them comes first on every lane
     for (dsg_handle* h : q->rd.hs) CHK(order_after(h, stream));
+    if (live) {
+        jb.live = true; jb.capacity = job->K; jb.style0 = w.job.style; jb.scale0 = job->scale;
+        for (int c = 0; c < n_given; ++c) jb.wins.push_back(QJob::Win{w.job.audio + c * n_audio, jb.style0, jb.scale0});
+        w.job.K = 0x7fffffff;
+    }
     q->jobs.push_back(std::move(jb));
     *ticket = t;
     return 0;
+}
+extern "C" int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg_clip_edit* edit, int skip_timesteps, int64_t* ticket, void* stream) {
+    return queue_submit(q, job, edit, skip_timesteps, -1, ticket, stream);
+}
+extern "C" int dsg_queue_submit_live(dsg_queue* q, const dsg_clip_job* job, int n_given, int skip_timesteps, int64_t* ticket, void* stream) {
+    if (n_given < 0) return fail(DSG_E_INVALID, "dsg_queue_submit_live: n_given < 0");
+    return queue_submit(q, job, nullptr, skip_timesteps, n_given, ticket, stream);
+}
+
+// The end of a live job whose given windows have all run (dsg_queue_finish after the fact): nothing is left to run.  Without keep_last_tail
+// every row of the clip is written and delivered already.  With it the closing S rows are the slot's tail -- [S][J], the values handoff_row
+// stored for f >= keep after the shift, which are the values the last window would have written to the clip had it known it was the last;
+// window K - 1 wrote clip_tail[(K - 1) & 1] -- copied on the lane's stream into the clip and on to a host `out`.  The lane is drained: the
+// call has no stream of the caller's to order a device `out` before
+static int queue_finish_late(dsg_queue* q, QJob& jb) {
+    const QueueRound& rd = q->rd;
+    const int n = (int)rd.hs.size(), J = rd.hs[0]->J, S = rd.hs[0]->S, keep = rd.hs[0]->T - S, K = jb.w.job.K;
+    dsg_handle* h = rd.hs[jb.slot % n];
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (rd.keep_last_tail) {
+        const float* tail = h->clip_tail[(K - 1) & 1] + (size_t)(jb.slot / n) * S * J;
+        HIPCHK(hipMemcpyAsync(jb.w.clip + ((size_t)K * keep - S) * J, tail, (size_t)S * J * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    }
+    jb.rows_ready = jb.w.ed.n_out;
+    if (jb.host_out && jb.rows_ready > jb.rows_copied) {
+        const size_t at = (size_t)jb.rows_copied * J, cnt = (size_t)(jb.rows_ready - jb.rows_copied) * J;
+        HIPCHK(hipMemcpyAsync(jb.host_out + at, jb.w.clip + at, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        jb.rows_copied = jb.rows_ready;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    jb.state = DSG_JOB_DONE;
+    queue_give(q, jb);
+    q->slot_job[jb.slot] = -1;
+    return 0;
+}
+extern "C" int dsg_queue_finish(dsg_queue* q, int64_t ticket) {
+    if (!q) return fail(DSG_E_INVALID, "dsg_queue_finish: null queue");
+    if (ticket < 0 || ticket >= (int64_t)q->jobs.size()) return fail(DSG_E_INVALID, "dsg_queue_finish: no such ticket: " + std::to_string(ticket));
+    QJob& jb = q->jobs[ticket];
+    if (!jb.live) return fail(DSG_E_INVALID, "dsg_queue_finish: ticket " + std::to_string(ticket) + " is not a live job");
+    if (jb.finished || jb.state == DSG_JOB_DONE || jb.state == DSG_JOB_CANCELLED) return 0;      // nothing left to finish
+    jb.finished = true;
+    const int K = (int)jb.wins.size(), S = q->rd.hs[0]->S, keep = q->rd.hs[0]->T - S;
+    if (K == 0) {      // no window was ever given (so it never took a slot): there is no clip
+        jb.state = DSG_JOB_CANCELLED;
+        queue_give(q, jb);
+        return 0;
+    }
+    jb.w.job.K = K;
+    jb.w.ed.n_out = K * keep - (q->rd.keep_last_tail ? 0 : S);
+    if (jb.state == DSG_JOB_RUNNING && jb.w.c >= K) return queue_finish_late(q, jb);
+    return 0;      // windows still to run: the last of them runs with HQ_LAST and the job is done after that round
+}
+extern "C" int dsg_queue_append(dsg_queue* q, int64_t ticket, const dsg_queue_window* wins, int n, void* stream) {
+    if (!q || !wins) return fail(DSG_E_INVALID, "dsg_queue_append: null argument");
+    const std::string tk = std::to_string(ticket);
+    if (ticket < 0 || ticket >= (int64_t)q->jobs.size()) return fail(DSG_E_INVALID, "dsg_queue_append: no such ticket: " + tk);
+    QJob& jb = q->jobs[ticket];
+    if (!jb.live) return fail(DSG_E_INVALID, "dsg_queue_append: ticket " + tk + " is not a live job");
+    if (jb.state == DSG_JOB_DONE) return fail(DSG_E_INVALID, "dsg_queue_append: ticket " + tk + " is done");
+    if (jb.state == DSG_JOB_CANCELLED) return fail(DSG_E_INVALID, "dsg_queue_append: ticket " + tk + " is cancelled");
+    if (jb.finished) return fail(DSG_E_INVALID, "dsg_queue_append: ticket " + tk + " is finished");
+    if (n < 1) return fail(DSG_E_INVALID, "dsg_queue_append: ticket " + tk + ": n < 1");
+    if ((int64_t)jb.wins.size() + n > jb.capacity)
+        return fail(DSG_E_INVALID, "dsg_queue_append: ticket " + tk + ": " + std::to_string(jb.wins.size()) + " + " + std::to_string(n) +
+                                   " windows exceed the capacity of " + std::to_string(jb.capacity));
+    for (int i = 0; i < n; ++i) {
+        if (!wins[i].audio) return fail(DSG_E_INVALID, "dsg_queue_append: ticket " + tk + ": window " + std::to_string(i) + " has a null audio");
+        if ((wins[i].flags & DSG_WIN_LAST) && i != n - 1)
+            return fail(DSG_E_INVALID, "dsg_queue_append: ticket " + tk + ": DSG_WIN_LAST on window " + std::to_string(i) + " of " + std::to_string(n) + ": only the last entry may carry it");
+    }
+    dsg_handle* h0 = q->rd.hs[0];
+    HIPCHK(hipSetDevice(h0->cfg.device));
+    const size_t n_audio = (size_t)h0->Ta * h0->As, n_blocks = jb.blocks.size();
+    bool drained = false;      // (as dsg_queue_submit: a recycled block may still be read by a round in flight)
+    auto room = [&](size_t bytes, void** p) -> int {
+        if (!drained) { for (dsg_handle* h : q->rd.hs) HIPCHK(hipStreamSynchronize(h->stream)); drained = true; }
+        return queue_take(q, bytes, jb, p);
+    };
+    std::vector<QJob::Win> add(n);
+    int rc = 0;
+    for (int i = 0; i < n && !rc; ++i) {
+        const QJob::Win* prev = i > 0 ? &add[i - 1] : jb.wins.empty() ? nullptr : &jb.wins.back();
+        QJob::Win& wn = add[i];
+        rc = staged(h0, wins[i].audio, n_audio * sizeof(float), room, (const void**)&wn.audio);
+        if (!rc && wins[i].style) rc = staged(h0, wins[i].style, (size_t)h0->cfg.style_dim_in * sizeof(float), room, (const void**)&wn.style);
+        else wn.style = prev ? prev->style : jb.style0;
+        wn.scale = (wins[i].flags & DSG_WIN_SCALE) && q->rd.guided ? wins[i].scale : prev ? prev->scale : jb.scale0;
+    }
+    if (!rc && drained && hipStreamSynchronize(h0->stream) != hipSuccess) { (void)hipGetLastError(); rc = fail(DSG_E_RUNTIME, "dsg_queue_append: staging copy failed"); }
+    if (rc) {      // the job is as it was: the blocks taken here go back to the free list
+        for (size_t b = n_blocks; b < jb.blocks.size(); ++b) q->free_blocks.emplace(jb.blocks[b].cap, jb.blocks[b].p);
+        jb.blocks.resize(n_blocks);
+        return rc;
+    }
+    for (dsg_handle* h : q->rd.hs) CHK(order_after(h, stream));
+    jb.wins.insert(jb.wins.end(), add.begin(), add.end());
+    return (wins[n - 1].flags & DSG_WIN_LAST) ? dsg_queue_finish(q, ticket) : 0;
 }
 
 extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void* stream) {
@@ -3551,27 +3674,40 @@ extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void
     int done = 0;
     while (max_rounds <= 0 || done < max_rounds) {
         // placement: the free slots, lowest first, take the pending jobs, oldest ticket first
+        // (a pending live job without a window yet cannot be placed: the tickets behind it pass it)
+        size_t p = q->next_pending;
         for (int s = 0; s < n_slots; ++s) {
             if (q->slot_job[s] >= 0) continue;
             while (q->next_pending < q->jobs.size() && q->jobs[q->next_pending].state != DSG_JOB_PENDING) ++q->next_pending;
-            if (q->next_pending >= q->jobs.size()) break;
-            QJob& jb = q->jobs[q->next_pending];
+            p = std::max(p, q->next_pending);
+            while (p < q->jobs.size() && (q->jobs[p].state != DSG_JOB_PENDING || !q->jobs[p].has_window())) ++p;
+            if (p >= q->jobs.size()) break;
+            QJob& jb = q->jobs[p];
             jb.state = DSG_JOB_RUNNING; jb.slot = s; jb.first_round = (int)q->rounds_total;
-            q->slot_job[s] = (int64_t)q->next_pending++;
+            q->slot_job[s] = (int64_t)p++;
         }
+        // a running live job without a window to run sits the round out: a dead slot, whose c_seed rows, tail and state stay
         bool alive = false;
         for (int s = 0; s < n_slots; ++s) {
-            slots[s] = q->slot_job[s] < 0 ? nullptr : &q->jobs[q->slot_job[s]].w;
-            alive = alive || slots[s];
+            slots[s] = nullptr;
+            if (q->slot_job[s] < 0) continue;
+            QJob& jb = q->jobs[q->slot_job[s]];
+            if (!jb.has_window()) continue;
+            if (jb.live) {      // the window it stands on brings its own audio, style and scale
+                const QJob::Win& wn = jb.wins[jb.w.c];
+                jb.w.win_audio = wn.audio; jb.w.job.style = wn.style; jb.w.job.scale = wn.scale;
+            }
+            slots[s] = &jb.w;
+            alive = true;
         }
-        if (!alive) break;      // nothing alive, nothing pending
-        CHK(rd.run(slots.data(), (int)(q->rounds_total & 0x7fffffff), stream));
+        if (!alive) break;      // no slot has a window to run, no pending job can be placed
+        CHK(rd.run(slots.data(), stream));
         // the round's windows are handed off: the rows that became final go to the callers' host memory, on the stream of the lane that
         // wrote them; finished jobs leave their slots
         std::vector<char> copied(n, 0);
         for (int s = 0; s < n_slots; ++s) {
             const int64_t t = q->slot_job[s];
-            if (t < 0) continue;
+            if (!slots[s]) continue;
             QJob& jb = q->jobs[t];
             ++jb.w.c;
             jb.rows_ready = queue_rows_ready(q, jb);
@@ -3603,6 +3739,7 @@ extern "C" int dsg_queue_job(dsg_queue* q, int64_t ticket, dsg_queue_job_info* i
     const QJob& jb = q->jobs[ticket];
     memset(info, 0, sizeof *info);
     info->state = jb.state; info->windows_done = jb.w.c; info->rows_ready = jb.rows_ready; info->slot = jb.slot; info->first_round = jb.first_round;
+    if (jb.live) { info->windows_given = (int32_t)jb.wins.size(); info->live = DSG_JOB_LIVE | (jb.finished ? DSG_JOB_FINISHED : 0); }
     return 0;
 }
 extern "C" int dsg_queue_info(dsg_queue* q, int64_t* rounds_total, int* n_pending, int* n_running) {

@@ -1774,6 +1774,11 @@ __global__ void k_window_handoff(const HandoffArgs a) {
 // -- the clip a row goes to, its length, the window index, first / last -- comes per slot from a table in device memory (uploaded once per
 // round on the handle's stream).  A `dead` slot (no clip this round) writes nothing: not the clip, not the tail, not c_seed.  A slot that
 // starts a clip (is_first) neither shifts nor blends, whatever the slot's previous clip left in tail_in.
+// The two tail buffers alternate PER SLOT, by the window the slot stands on: slot b reads tail[(c + 1) & 1] and writes tail[c & 1], as
+// dsg_sample_clip does with its window index.  A slot that sits a round out (a live job of a session without a window to run: dead for that
+// round) finds its tail where its last window left it, however many rounds its neighbours ran meanwhile; with the parity taken from the
+// round, an odd number of idle rounds would hand the next window the other buffer.  The tails are per-slot rows [b][S][J], so "not tail_in:
+// other threads still read that one" holds slot by slot.
 struct HandoffSlot {
     float* clip_out;        // [n_out][J] of the slot's clip
     int n_out, c;           // its length and the window it stands on
@@ -1782,7 +1787,7 @@ struct HandoffSlot {
 };
 enum { HQ_FIRST = 1, HQ_LAST = 2, HQ_DEAD = 4 };
 struct HandoffQArgs {
-    const float* xs32; const float* tail_in; float* tail_out; float* c_seed; const HandoffSlot* slots;
+    const float* xs32; float* tail0; float* tail1; float* c_seed; const HandoffSlot* slots;      // tail0 / tail1: clip_tail[0] / [1]
     int B, J, Jp, T, S;
     int root_shift, keep_last_tail;
 };
@@ -1791,7 +1796,8 @@ __global__ void k_window_handoff_q(const HandoffQArgs a) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const HandoffSlot s = a.slots[i / per];
         if (s.flags & HQ_DEAD) continue;
-        handoff_row(a.xs32, a.tail_in, a.tail_out, a.c_seed, s.clip_out, i, a.J, a.Jp, a.T, a.S, s.n_out, s.c, a.root_shift,
+        const bool odd = s.c & 1;
+        handoff_row(a.xs32, odd ? a.tail0 : a.tail1, odd ? a.tail1 : a.tail0, a.c_seed, s.clip_out, i, a.J, a.Jp, a.T, a.S, s.n_out, s.c, a.root_shift,
                     (s.flags & HQ_FIRST) ? 1 : 0, (s.flags & HQ_LAST) ? 1 : 0, a.keep_last_tail);
     }
 }

@@ -546,16 +546,19 @@ class DSGDiffusion:
         return outs
 
     # ---- clips of different lengths over one batch of slots (dsg_sample_clip_queue) ------------------------------------------
-    def _clip_queue_job(self, cfg, clip, i, job, edit, use_torch, keep_last_tail, who="sample_clip_queue"):
+    def _clip_queue_job(self, cfg, clip, i, job, edit, use_torch, keep_last_tail, who="sample_clip_queue", capacity=None):
         """One clip dict of `sample_clip_queue` / `ClipQueue.submit` as the library's dsg_clip_job + dsg_clip_edit (filled in place).  Returns
-        (the host `out` [n_out, J], the buffers that must outlive the call, whether the clip has an edit)."""
+        (the host `out` [n_out, J], the buffers that must outlive the call, whether the clip has an edit).  `capacity` (`submit_live`): the
+        job's K and the size of `out`; "feats" are the windows given so far and may be empty."""
         from .model import _mask_bytes
         S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
         edit_keys = ("inpainting_mask", "inpainted_motion", "init_motion")
-        feats = list(clip["feats"])
-        if not feats:
+        feats = list(clip.get("feats") or []) if capacity is not None else list(clip["feats"])
+        if not feats and capacity is None:
             raise ValueError(f"{who}: a clip without windows")
-        if use_torch:
+        if not feats:
+            audio = L.Buf(None)
+        elif use_torch:
             import torch
             audio = L.Buf(torch.stack([f.float().reshape(cfg.audio_frames, cfg.audio_src_dim) for f in feats]))
         else:
@@ -569,8 +572,8 @@ class DSGDiffusion:
                 raise ValueError(f"{name} shape {tuple(b.obj.shape)}")
         st = clip.get("stream", 0)
         sd, sid = (st if isinstance(st, (tuple, list)) else (self._seed, st))
-        K = len(feats)
-        out = np.empty((K * (T - S) - (0 if keep_last_tail else S), J), np.float32)
+        K = len(feats) if capacity is None else int(capacity)
+        out = np.empty((max(K * (T - S) - (0 if keep_last_tail else S), 0), J), np.float32)
         job.style, job.seed0, job.seed_last, job.audio, job.out = style.ptr, seed0.ptr, last.ptr, audio.ptr, out.ctypes.data
         job.K, job.scale = K, float(1.0 if clip.get("scale") is None else clip["scale"])
         job.seed, job.stream_id = int(sd) & _U64, int(sid) & _U64
@@ -856,6 +859,7 @@ class ClipQueue:
         self._seed = diffusion._seed
         self._advance = 0
         self._outs, self._keep = [], {}
+        self._live = {}                                  # ticket -> [windows given, steps per window] of a live job
         hs = (C.c_void_p * len(self.lanes))(*[m.handle for m in self.lanes])
         q = C.c_void_p()
         self.lib.check(self.lib.cdll.dsg_queue_open(hs, len(self.lanes), self.B, mbuf.p, int(bool(guided)), C.byref(a), int(bool(root_shift)),
@@ -915,8 +919,86 @@ class ClipQueue:
         self._advance = max(self._advance, int(job.K) * (1 + d.num_timesteps - skip))
         return i
 
+    def submit_live(self, clip, capacity, out=None) -> int:
+        """A live clip (dsg_queue_submit_live): its windows arrive while it runs.  `clip` as for `submit`, without edits; "feats" are the
+        windows known now and may be empty.  `capacity`: the most windows it may ever get -- `out` (the caller's, or the session's) is
+        [n_out(capacity), J].  Feed it with `append`, end it with `finish` (or `append(..., last=True)`); `rows` / `result` as for every
+        clip.  With K windows given it is bit for bit `sample_clip` of those K windows alone, whenever they arrived."""
+        q, d = self._q(), self.diffusion
+        i = len(self._outs)
+        if any(clip.get(k) is not None for k in ("inpainting_mask", "inpainted_motion", "init_motion")):
+            raise ValueError(f"ClipQueue.submit_live: clip {i}: a live clip takes no edits (their coordinates depend on the final length)")
+        sk = clip.get("skip_timesteps")
+        if sk is not None and not 0 <= int(sk) < d.num_timesteps:
+            raise ValueError(f"ClipQueue.submit_live: clip {i}: skip_timesteps {int(sk)} outside [0, {d.num_timesteps - 1}]")
+        feats = list(clip.get("feats") or [])
+        use_torch = bool(feats) and L.is_torch(feats[0])
+        stream = L.current_stream_ptr() if any(L.is_torch(clip.get(k)) for k in ("style", "seed0", "seed_last")) or use_torch else None
+        job, edit = L.dsg_clip_job(), L.dsg_clip_edit()
+        seed_was, d._seed = d._seed, self._seed
+        try:
+            own, bufs, _ = d._clip_queue_job(self.cfg, clip, i, job, edit, use_torch, self.keep_last_tail, who="ClipQueue.submit_live", capacity=capacity)
+        finally:
+            d._seed = seed_was
+        if out is not None:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == own.shape):
+                raise ValueError(f"ClipQueue.submit_live: clip {i}: out must be a C-contiguous float32 array of shape {own.shape}")
+            job.out = out.ctypes.data
+        else:
+            out = own
+        ticket = C.c_int64(-1)
+        self.lib.check(self.lib.cdll.dsg_queue_submit_live(q, C.byref(job), len(feats), -1 if sk is None else int(sk), C.byref(ticket), stream))
+        assert ticket.value == i
+        self._outs.append(out)
+        dev = [b for b in bufs if b.obj is not None and L.is_torch(b.obj) and b.obj.is_cuda]
+        if dev:
+            self._keep[i] = dev
+        self._live[i] = [0, 1 + d.num_timesteps - (self.skip_timesteps if sk is None else int(sk))]
+        self._given(i, len(feats))
+        return i
+
+    def _given(self, ticket, n):
+        g = self._live[ticket]
+        g[0] += n
+        self._advance = max(self._advance, g[0] * g[1])
+
+    def append(self, ticket, feats, style=None, scale=None, last=False):
+        """Further windows for a live clip (dsg_queue_append).  `feats`: one window [T_a, A_src] (or [1, T_a, A_src]), or a list of them.
+        `style` / `scale`: from the first of these windows on (None: as before; `scale` is read by a guided session only).  `last=True`:
+        `finish` in the same call.  Host arrays are copied by the call; device tensors must stay valid until their window has run."""
+        q, cfg, t = self._q(), self.cfg, int(ticket)
+        wins = list(feats) if isinstance(feats, (list, tuple)) else [feats]
+        arr = (L.dsg_queue_window * max(len(wins), 1))()
+        bufs = []
+        for k, f in enumerate(wins):
+            a = L.Buf(f.float().reshape(cfg.audio_frames, cfg.audio_src_dim) if L.is_torch(f)
+                      else np.asarray(f, np.float32).reshape(cfg.audio_frames, cfg.audio_src_dim))
+            bufs.append(a)
+            arr[k].audio = a.ptr
+            if k == 0 and style is not None:
+                st = L.Buf(style)
+                if int(np.prod(st.obj.shape)) != cfg.style_dim_in:
+                    raise ValueError(f"style shape {tuple(st.obj.shape)}")
+                bufs.append(st)
+                arr[k].style = st.ptr
+            if k == 0 and scale is not None:
+                arr[k].scale, arr[k].flags = float(scale), L.WIN_SCALE
+        if last and wins:
+            arr[len(wins) - 1].flags |= L.WIN_LAST
+        dev = [b for b in bufs if L.is_torch(b.obj) and b.obj.is_cuda]
+        self.lib.check(self.lib.cdll.dsg_queue_append(q, t, arr, len(wins), L.current_stream_ptr() if dev else None))
+        if dev:
+            self._keep.setdefault(t, []).extend(dev)
+        if t in self._live:
+            self._given(t, len(wins))
+
+    def finish(self, ticket):
+        """No more windows for a live clip (dsg_queue_finish): its length is the windows given.  It is done after the round of its last
+        window -- at once when that has run already."""
+        self.lib.check(self.lib.cdll.dsg_queue_finish(self._q(), int(ticket)))
+
     def run(self, max_rounds=1) -> int:
-        """Up to `max_rounds` rounds (0: until nothing is alive or pending); returns the rounds run."""
+        """Up to `max_rounds` rounds (0: until nothing has a window to run and nothing pending can be placed); returns the rounds run."""
         n = C.c_int(0)
         stream = L.current_stream_ptr() if self._keep else None
         self.lib.check(self.lib.cdll.dsg_queue_run(self._q(), int(max_rounds), C.byref(n), stream))
@@ -926,10 +1008,14 @@ class ClipQueue:
         return int(n.value)
 
     def job(self, ticket) -> dict:
-        """{"state", "windows_done", "rows_ready", "slot", "first_round"} of a ticket (state: lib.JOB_*)."""
+        """{"state", "windows_done", "rows_ready", "slot", "first_round"} of a ticket (state: lib.JOB_*); a live clip adds "windows_given",
+        "live" (True) and "finished"."""
         info = L.dsg_queue_job_info()
         self.lib.check(self.lib.cdll.dsg_queue_job(self._q(), int(ticket), C.byref(info)))
-        return {k: int(getattr(info, k)) for k in ("state", "windows_done", "rows_ready", "slot", "first_round")}
+        d = {k: int(getattr(info, k)) for k in ("state", "windows_done", "rows_ready", "slot", "first_round")}
+        if info.reserved[1] & L.JOB_LIVE:
+            d.update(windows_given=int(info.reserved[0]), live=True, finished=bool(info.reserved[1] & L.JOB_FINISHED))
+        return d
 
     def info(self) -> dict:
         r, p, n = C.c_int64(0), C.c_int(0), C.c_int(0)
@@ -941,11 +1027,12 @@ class ClipQueue:
         return self._outs[int(ticket)][:self.job(ticket)["rows_ready"]]
 
     def result(self, ticket):
-        """The whole clip [n_out, J]; raises unless the job is done."""
-        st = self.job(ticket)["state"]
-        if st != L.JOB_DONE:
-            raise L.DSGError(f"ClipQueue.result: ticket {int(ticket)} is not done (state {st})")
-        return self._outs[int(ticket)]
+        """The whole clip [n_out, J]; raises unless the job is done.  A live clip: n_out of the windows it was given."""
+        j = self.job(ticket)
+        if j["state"] != L.JOB_DONE:
+            raise L.DSGError(f"ClipQueue.result: ticket {int(ticket)} is not done (state {j['state']})")
+        out = self._outs[int(ticket)]
+        return out[:j["rows_ready"]] if j.get("live") else out
 
     def cancel(self, ticket):
         self.lib.check(self.lib.cdll.dsg_queue_cancel(self._q(), int(ticket)))

@@ -54,6 +54,15 @@ class dsg_queue_job_info(C.Structure):
 
 
 JOB_PENDING, JOB_RUNNING, JOB_DONE, JOB_CANCELLED = 0, 1, 2, 3          # DSG_JOB_* of include/dsg.h
+JOB_LIVE, JOB_FINISHED = 1, 2          # bits of dsg_queue_job_info.live (reserved[1] here; reserved[0]: windows_given)
+
+
+class dsg_queue_window(C.Structure):
+    """One window of dsg_queue_append (include/dsg.h): its audio, and optionally the style / scale from this window on."""
+    _fields_ = [("audio", C.c_void_p), ("style", C.c_void_p), ("scale", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+WIN_SCALE, WIN_LAST = 1, 2          # DSG_WIN_* of include/dsg.h
 
 # every symbol include/dsg.h declares: name -> (restype, argtypes)
 _P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
@@ -95,6 +104,9 @@ SYMBOLS = {
     "dsg_queue_cancel": (_I, [_P, _I64]),
     "dsg_queue_close": (_I, [_P]),
     "dsg_queue_place": (_I, [_P, _P, _I, _I, _P, _P, C.POINTER(C.c_int32)]),
+    "dsg_queue_submit_live": (_I, [_P, C.POINTER(dsg_clip_job), _I, _I, C.POINTER(_I64), _P]),
+    "dsg_queue_append": (_I, [_P, _I64, C.POINTER(dsg_queue_window), _I, _P]),
+    "dsg_queue_finish": (_I, [_P, _I64]),
     "dsg_set_kernel_set": (_I, [_P, _I]),
     "dsg_get_kernel_set": (_I, [_P, C.POINTER(_I)]),
     "dsg_recommend_kernel_set": (_I, [_P, _I, _I, C.POINTER(_I)]),

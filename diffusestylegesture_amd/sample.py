@@ -628,6 +628,7 @@ class _ClipQueueSession:
         if B is None:
             B = max(1, min(m.max_batch for m in inners) // (2 if guided else 1))
         self.cfg, self.dsgplus, self.feature_division, self._real, self._n = inners[0].cfg, dsgplus, feature_division, {}, 0
+        self._live = {}                                  # ticket of a live clip -> [seed_pose, seed_last, the last window given] (DSG+)
         self._sets = _lane_kernel_sets(inners, int(B), kernel_set)
         self._sets.__enter__()
         try:
@@ -662,10 +663,61 @@ class _ClipQueueSession:
             self._real[t] = int(c["real_n_frames"])
         return t
 
+    def _window_audio(self, ticket, feats):
+        """the per-window features of a live clip as the library takes them; DSG+: as `_dsgplus_window_y` builds them (the attention3 model
+        puts the tail of the window before in front, so the last window given is kept per ticket)"""
+        feats = list(feats) if isinstance(feats, (list, tuple)) else [feats]
+        if not self.dsgplus or not feats:
+            return feats
+        use_torch = L.is_torch(feats[0])
+        seed_pose, seed_last, prev = self._live[ticket]
+        feats = [f if f.ndim == 3 else f[None] for f in feats]
+        chain = ([prev] if prev is not None else []) + feats
+        at = len(chain) - len(feats)
+        # (index 0 of the chain -- the zero left context -- is a window of this call only when it is the clip's first)
+        audio = [_dsgplus_window_y(self.cfg, chain, at + w, None, seed_pose, seed_last, use_torch, None)["audio"] for w in range(len(feats))]
+        self._live[ticket][2] = feats[-1]
+        return audio
+
+    def submit_live(self, clip, capacity) -> int:
+        """A live clip (`ClipQueue.submit_live`): the clip dict of `submit` without edits and without "real_n_frames"; "feats" are the
+        windows known now and may be empty; `capacity`: the most windows it may ever get.  Feed it with `append`, end it with `finish`."""
+        c = clip
+        style = np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"]
+        job = {"style": style, "scale": c.get("scale"), "stream": _queue_stream(c, self._n)}
+        if c.get("skip_timesteps") is not None:
+            job["skip_timesteps"] = c["skip_timesteps"]
+        ticket = self._n                                 # (tickets count submissions)
+        if self.dsgplus:
+            self._live[ticket] = [c["seed_pose"], c.get("seed_last"), None]
+            job["seed0"], job["seed_last"] = c["seed_pose"], c.get("seed_last")
+        else:
+            self._live[ticket] = None
+            job["seed0"] = c.get("seed_pose")
+        job["feats"] = self._window_audio(ticket, c.get("feats") or [])
+        t = self.queue.submit_live(job, capacity)
+        assert t == ticket
+        self._n += 1
+        return t
+
+    def append(self, ticket, feats, style=None, scale=None, last=False, real_n_frames=None):
+        """Further windows for a live clip (`ClipQueue.append`); `last=True` finishes it (DSG+: `real_n_frames` as for `finish`)."""
+        if style is not None and not L.is_torch(style):
+            style = np.asarray(style, np.float32).reshape(-1)
+        if last and self.dsgplus and real_n_frames is not None:
+            self._real[int(ticket)] = int(real_n_frames)
+        self.queue.append(ticket, self._window_audio(int(ticket), feats), style=style, scale=scale, last=last)
+
+    def finish(self, ticket, real_n_frames=None):
+        """No more windows for a live clip.  DSG+: `result` / `rows` crop to `real_n_frames` as `submit` does (None: no crop in time)."""
+        if self.dsgplus and real_n_frames is not None:
+            self._real[int(ticket)] = int(real_n_frames)
+        self.queue.finish(ticket)
+
     def _crop(self, ticket, q):
         if not self.dsgplus:
             return q
-        return np.ascontiguousarray(q[: self._real[int(ticket)], : self.cfg.njoints // self.feature_division], dtype=np.float32)
+        return np.ascontiguousarray(q[: self._real.get(int(ticket)), : self.cfg.njoints // self.feature_division], dtype=np.float32)
 
     def run(self, max_rounds=1) -> int:
         return self.queue.run(max_rounds)
@@ -697,7 +749,8 @@ class _ClipQueueSession:
 def open_clip_queue(lanes, diffusion, seed=123456, smoothing=True, skip_timesteps=0, ddim=False, eta=0.0, kernel_set="recommended", *, B=None,
                     guided=False):
     """`generate_clip_queue` as a session: submit ZEGGS clip dicts while it runs, collect rows per window (`DSGDiffusion.open_clip_queue`).
-    Returns a context manager with submit / run / job / rows / result / cancel / close.  `guided` is fixed at open (a lane wrapped in
+    Returns a context manager with submit / run / job / rows / result / cancel / close, and submit_live / append / finish for a clip whose
+    windows arrive while it runs.  `guided` is fixed at open (a lane wrapped in
     ClassifierFreeSampleModel turns it on); B defaults to the lanes' max_batch (halved with guidance).  Clip i is bit for bit
     `generate_clip(lane of batch 1, ..., windows="library", stream_id=clip_id)` whenever it was submitted."""
     return _ClipQueueSession(lanes, diffusion, False, seed, skip_timesteps, ddim, eta, kernel_set, B, guided, smoothing, 1)

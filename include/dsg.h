@@ -457,8 +457,11 @@ typedef struct dsg_queue_job_info {
     int32_t rows_ready;    /* rows [0, rows_ready) of the job's `out` are final and there */
     int32_t slot;          /* global slot, -1 while pending                               */
     int32_t first_round;   /* session round of its window 0, -1 while pending             */
-    int32_t reserved[3];
+    int32_t windows_given; /* a live job: the windows given so far; 0 for a closed job    */
+    int32_t live;          /* DSG_JOB_LIVE | DSG_JOB_FINISHED; 0 for a closed job         */
+    int32_t reserved[1];
 } dsg_queue_job_info;
+enum { DSG_JOB_LIVE = 1, DSG_JOB_FINISHED = 2 };      /* dsg_queue_job_info.live */
 int dsg_queue_open(dsg_handle** lanes, int n_lanes, int B, const uint8_t* mask_local, int guided,
                    const dsg_sample_args* args, int root_shift, int keep_last_tail, dsg_queue** out);
 int dsg_queue_submit(dsg_queue* q, const dsg_clip_job* job, const dsg_clip_edit* edit /* nullable */,
@@ -471,6 +474,55 @@ int dsg_queue_close(dsg_queue* q);
 /* host only, no device: exactly the placement the session follows */
 int dsg_queue_place(const int32_t* K, const int32_t* arrive_round, int n_jobs, int n_slots,
                     int32_t* slot, int32_t* first_round, int32_t* n_rounds);
+/* Live jobs: windows appended while the clip runs.  dsg_queue_submit wants all K audio windows of a job; a speaker who is still talking -- a
+ * live avatar, a TTS stream, a call -- has them one by one.  A live job is submitted with a CAPACITY and is fed window by window; the window
+ * hand-off (seed poses, root shift, one-frame blend) stays on the device, and the rows come back per window through rows_ready as for every
+ * job.  The promise: a live job comes out bit for bit as dsg_sample_clip produces its K windows alone -- B = 1, its (seed, stream_id), its
+ * skip, the same draw_base, root_shift / keep_last_tail and named kernel set, K = the windows it was finally given -- provided no window
+ * changes the style or the scale; it does not matter when the windows arrived, how many rounds the job sat out, or what ran beside it.  (Window
+ * c draws draw_base + c * (1 + n_run) and writes rows from c * (T - S) - S whatever K is.)  With a per-window style or scale it equals the
+ * K-call sequence of this header: dsg_set_window_cond[_cfg] with that window's style and scale, dsg_sample, and the stitching of sample.py.
+ * Reference counterpart: none.
+ * dsg_queue_submit_live: job->K is the capacity, the most windows the job may ever get, and job->out is [n_out(capacity), J]; job->audio holds
+ * the first n_given windows, contiguous (n_given == 0: may be NULL).  style, seed0, seed_last, scale, (seed, stream_id) and skip_timesteps
+ * mean what they mean at dsg_queue_submit, whose per-job checks and messages apply; n_given outside [0, K]: DSG_E_INVALID.  A live job takes
+ * no dsg_clip_edit: a constraint and an init motion are [n_out(K), J] tensors whose meaning depends on the final length (the cut tail of the
+ * last window), which a live job does not know yet.
+ * dsg_queue_append: n >= 1 further windows for a live job that is pending or running.  OWNERSHIP is the session's rule, per window: host
+ * tensors (audio, style) are copied into session staging before the call returns; device tensors are read where they are, behind `stream`,
+ * and must stay valid until windows_done has passed that window.  style NULL: the style of the window before it (window 0: the job's); scale
+ * is read only with DSG_WIN_SCALE in a guided session and holds from that window on.  DSG_WIN_LAST on the last entry is dsg_queue_finish in
+ * the same call.  DSG_E_INVALID, with the ticket in dsg_last_error: an unknown ticket, a job that is not live, a job that is finished, done
+ * or cancelled, n < 1, a null audio, more windows than the capacity, DSG_WIN_LAST anywhere but on the last entry.  A refused call leaves
+ * the job as it was.
+ * dsg_queue_finish: the job's K becomes the number of windows given.  Windows still to run: the last of them runs as a clip's last window
+ * and the job is DONE after that round.  Every given window has run already: the job is DONE before the call returns -- without
+ * keep_last_tail rows_ready is K * (T - S) - S already; with it the closing S rows are copied from the slot's tail (the values the hand-off
+ * kept for the next window's seed, after the shift) into rows [K * (T - S) - S, K * (T - S)), and on to a host `out`; the lane is drained.
+ * No window ever given: the job is cancelled.  Finishing a finished job: no-op.  An unknown ticket or a job that is not live: DSG_E_INVALID.
+ * PLACEMENT: a pending live job can be placed once it has a window; until then the tickets behind it pass it.  Once placed it keeps its slot
+ * until it is finished or cancelled; first_round is the round of its window 0.  IDLE SLOT: a running live job without a window to run when
+ * a round starts sits that round out -- dead for the round's start, draws, gather and hand-off; its y['seed'] rows, its tail and its state
+ * stay; windows_done and rows_ready do not move.  dsg_queue_run returns early when no slot has a window to run and no pending job can be
+ * placed: an idle live job alone runs no round.  rows_ready while live: min(n_out(capacity), windows_done * (T - S) - S); finished and done:
+ * n_out(K); rows of `out` past n_out(K) are never written.  dsg_queue_job: windows_given / live (above).  Cancel, close and the ownership
+ * of the lanes are unchanged.
+ * On the device: k_window_handoff_q picks the two tail buffers per slot by the slot's window index (as dsg_sample_clip does), not by the
+ * session's round, so a slot that sat out an odd number of rounds finds its tail where it left it; the gather table carries the style and
+ * audio pointer of the window the slot stands on.
+ * Added without a version step: dsg_version() stays 330; dsg_clip_job, dsg_clip_edit and dsg_queue_job_info keep their sizes. */
+enum { DSG_WIN_SCALE = 1, DSG_WIN_LAST = 2 };
+typedef struct dsg_queue_window {      /* 32 bytes */
+    const float* audio;   /* [T_a, A_src]: ONE window, as dsg_set_window_cond takes it; required */
+    const float* style;   /* [style_dim_in], or NULL: the style of the window before it (window 0: the job's) */
+    float scale;          /* y['scale'] from this window on; read only with DSG_WIN_SCALE in a guided session */
+    int32_t flags;        /* DSG_WIN_SCALE | DSG_WIN_LAST */
+    int32_t reserved[2];
+} dsg_queue_window;
+int dsg_queue_submit_live(dsg_queue* q, const dsg_clip_job* job, int n_given, int skip_timesteps /* < 0: args->skip_timesteps */,
+                          int64_t* ticket, void* stream);
+int dsg_queue_append(dsg_queue* q, int64_t ticket, const dsg_queue_window* wins, int n, void* stream);
+int dsg_queue_finish(dsg_queue* q, int64_t ticket);
 /* Per-element noise streams ("keyed noise") for dsg_sample / _multi / dsg_sample_clip / _multi.  seeds, stream_ids: HOST uint64[B], copied by
  * the call.  While set, element b of the batch draws from its own pair (seed_b, sid_b): draw d at frame f, feature j is
  *   philox4x32_10(ctr = ((f * Jq + j) >> 2, d, sid_b lo, sid_b hi), key = (seed_b lo, seed_b hi)) + Box-Muller,   Jq = J rounded up to 4,
