@@ -114,6 +114,24 @@ class _keyed:
         return False
 
 
+def _inner_lanes(lanes, who, batch=None):
+    """The lanes of a multi-lane / clip / queue call -- a model or a list of them -- as (their DSGDenoisers, their guided flags):
+    `_library_model` per lane; a lane that is no library model is the TypeError of `who`."""
+    lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
+    pairs = [DSGDiffusion._library_model(m, batch) for m in lanes]
+    if any(inner is None for inner, _ in pairs):
+        raise TypeError(f"{who} drives library denoisers (DSGDenoiser lanes)")
+    return [inner for inner, _ in pairs], [guided for _, guided in pairs]
+
+
+def _queue_mask(mask_local, T, who):
+    """`mask_local=` of the queue entry points as a Buf: one mask of T entries shared by every slot ("ones": all of them set)"""
+    mbuf = L.Buf(np.ones((T,), np.uint8) if isinstance(mask_local, str) else mask_local, "uint8")
+    if mbuf.obj is not None and int(np.prod(mbuf.obj.shape)) != T:
+        raise ValueError(f"{who}: mask_local is one mask of {T} entries, shared by every slot")
+    return mbuf
+
+
 class DSGDiffusion:
     """SpacedDiffusion(use_timesteps, betas=...) for START_X / FIXED_SMALL models (the only configuration
     `create_gaussian_diffusion` builds).  Table attributes carry the reference's names."""
@@ -182,6 +200,15 @@ class DSGDiffusion:
                 return None, False
             return model.model, True
         return None, False
+
+    def _clip_args(self, ddim, eta, skip_timesteps, clip_denoised, seed=None, stream_id=0):
+        """the dsg_sample_args of a clip or queue call: the sampler, and the stream (`seed`, default the one of `manual_seed`; `stream_id`)
+        at this object's draw counter"""
+        a = L.dsg_sample_args()
+        a.mode, a.skip_timesteps, a.eta = (L.MODE_DDIM if ddim else L.MODE_DDPM), int(skip_timesteps), float(eta)
+        a.seed, a.stream_id, a.draw_base = int(self._seed if seed is None else seed) & _U64, int(stream_id), self._draw
+        a.clip_denoised = int(bool(clip_denoised))
+        return a
 
     def _prepare(self, mode, model, guided, shape, noise, model_kwargs, skip_timesteps, init_image, dump_steps,
                  const_noise, eta, step_noise, seed, draw_base, clip_denoised, stream_id=None, first_step=0, max_steps=0):
@@ -350,18 +377,15 @@ class DSGDiffusion:
         B = int(shape[0])
         args = (L.dsg_sample_args * n)()
         outs, keeps, use_torch = [], [], False
+        models, guided = _inner_lanes(models, "p_sample_loop_multi", shape[0])
         for i, m in enumerate(models):
-            inner, guided = self._library_model(m, shape[0])
-            if inner is None:
-                raise TypeError("p_sample_loop_multi drives library denoisers (DSGDenoiser lanes)")
-            a, keep, _, ut = self._prepare(L.MODE_DDIM if ddim else L.MODE_DDPM, inner, guided, shape,
+            a, keep, _, ut = self._prepare(L.MODE_DDIM if ddim else L.MODE_DDPM, m, guided[i], shape,
                                            None if noises is None else noises[i], model_kwargs_list[i], skip_timesteps,
                                            None if init_images is None else init_images[i], None, False, eta, None,
                                            seeds[i], None, clip_denoised, stream_id=stream_ids[i])
             args[i] = a
             keeps.append(keep)
             use_torch = use_torch or ut
-            models[i] = inner
         hs = (C.c_void_p * n)(*[m.handle for m in models])
         optrs = (C.c_void_p * n)()
         for i, m in enumerate(models):
@@ -438,15 +462,9 @@ class DSGDiffusion:
         stream_ids = [self.stream_id + i for i in range(n)] if stream_ids is None else list(stream_ids)
         use_torch = L.is_torch(feats_per_lane[0][0])
         B = int(feats_per_lane[0][0].shape[0])
-        guided_any = scales is not None
-        inners = []
-        for m in models:
-            inner, guided = self._library_model(m, B)
-            if inner is None:
-                raise TypeError("sample_clip drives library denoisers (DSGDenoiser lanes)")
-            if guided and not guided_any:
-                raise KeyError("scale")
-            inners.append(inner)
+        inners, guided = _inner_lanes(models, "sample_clip", B)
+        if any(guided) and scales is None:
+            raise KeyError("scale")
         cfg = inners[0].cfg
         S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
         n_run = self.num_timesteps - skip_timesteps
@@ -494,10 +512,7 @@ class DSGDiffusion:
                     raise ValueError(f"seed_last shape {tuple(last.obj.shape)}")
                 m.lib.check(m.lib.cdll.dsg_set_seed_last(m.handle, last.p, B, stream))
                 keep.append(last)
-            a = args[i]
-            a.mode, a.skip_timesteps, a.eta = (L.MODE_DDIM if ddim else L.MODE_DDPM), int(skip_timesteps), float(eta)
-            a.seed, a.stream_id, a.draw_base = int(seeds[i]) & (2 ** 64 - 1), int(stream_ids[i]), self._draw
-            a.clip_denoised = int(bool(clip_denoised))
+            args[i] = self._clip_args(ddim, eta, skip_timesteps, clip_denoised, seeds[i], stream_ids[i])
             if use_torch and audio.obj.is_cuda:      # device -> PINNED host memory, as sample.py's _zeggs_finish
                 import torch
                 out = torch.empty((B, n_out, J), dtype=torch.float32, pin_memory=True)
@@ -513,29 +528,29 @@ class DSGDiffusion:
         lib = inners[0].lib
         keyed = _keyed(inners, [None] * n if clip_streams is None else clip_streams, B)
         try:
-            keyed.__enter__()
-            for m, (mk, mo) in zip(inners, inp):
-                if mk is not None:
-                    if tuple(mo.shape) != (B, n_out, J):
-                        raise ValueError(f"clip inpainted_motion shape {tuple(mo.shape)} != {(B, n_out, J)}")
-                    m.set_clip_inpainting(mk, mo, B)
-                elif m.clip_inpainting:
-                    m.set_clip_inpainting(None, None, 0)
-            for m, init in zip(inners, inits):
-                if init is not None:
-                    if tuple(init.shape) != (B, n_out, J):
-                        raise ValueError(f"clip init_motion shape {tuple(init.shape)} != {(B, n_out, J)}")
-                    m.set_clip_init(init, B)
-                elif m.clip_init:
-                    m.set_clip_init(None, 0)
-            if n == 1:
-                lib.check(lib.cdll.dsg_sample_clip(ptrs["h"][0], ptrs["style"][0], ptrs["seed0"][0], ptrs["audio"][0], mbuf.p, mb, ptrs["scale"][0],
-                                                   C.byref(args[0]), K, int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"][0], B, stream))
-            else:
-                lib.check(lib.cdll.dsg_sample_clip_multi(ptrs["h"], n, ptrs["style"], ptrs["seed0"], ptrs["audio"], mbuf.p, mb, ptrs["scale"], args, K,
-                                                         int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"], B, stream))
+            with keyed:
+                for m, (mk, mo) in zip(inners, inp):
+                    if mk is not None:
+                        if tuple(mo.shape) != (B, n_out, J):
+                            raise ValueError(f"clip inpainted_motion shape {tuple(mo.shape)} != {(B, n_out, J)}")
+                        m.set_clip_inpainting(mk, mo, B)
+                    elif m.clip_inpainting:
+                        m.set_clip_inpainting(None, None, 0)
+                for m, init in zip(inners, inits):
+                    if init is not None:
+                        if tuple(init.shape) != (B, n_out, J):
+                            raise ValueError(f"clip init_motion shape {tuple(init.shape)} != {(B, n_out, J)}")
+                        m.set_clip_init(init, B)
+                    elif m.clip_init:
+                        m.set_clip_init(None, 0)
+                if n == 1:
+                    lib.check(lib.cdll.dsg_sample_clip(ptrs["h"][0], ptrs["style"][0], ptrs["seed0"][0], ptrs["audio"][0], mbuf.p, mb,
+                                                       ptrs["scale"][0], C.byref(args[0]), K, int(bool(root_shift)), int(bool(keep_last_tail)),
+                                                       ptrs["out"][0], B, stream))
+                else:
+                    lib.check(lib.cdll.dsg_sample_clip_multi(ptrs["h"], n, ptrs["style"], ptrs["seed0"], ptrs["audio"], mbuf.p, mb, ptrs["scale"],
+                                                             args, K, int(bool(root_shift)), int(bool(keep_last_tail)), ptrs["out"], B, stream))
         finally:
-            keyed.__exit__()
             for m in inners:
                 if m.clip_inpainting:
                     m.set_clip_inpainting(None, None, 0)
@@ -546,10 +561,12 @@ class DSGDiffusion:
         return outs
 
     # ---- clips of different lengths over one batch of slots (dsg_sample_clip_queue) ------------------------------------------
-    def _clip_queue_job(self, cfg, clip, i, job, edit, use_torch, keep_last_tail, who="sample_clip_queue", capacity=None):
+    @staticmethod
+    def _clip_queue_job(cfg, clip, i, job, edit, use_torch, keep_last_tail, seed, who="sample_clip_queue", capacity=None):
         """One clip dict of `sample_clip_queue` / `ClipQueue.submit` as the library's dsg_clip_job + dsg_clip_edit (filled in place).  Returns
-        (the host `out` [n_out, J], the buffers that must outlive the call, whether the clip has an edit).  `capacity` (`submit_live`): the
-        job's K and the size of `out`; "feats" are the windows given so far and may be empty."""
+        (the host `out` [n_out, J], the buffers that must outlive the call, whether the clip has an edit).  `seed`: the seed of a clip whose
+        "stream" is a bare id.  `capacity` (`submit_live`): the job's K and the size of `out`; "feats" are the windows given so far and may
+        be empty."""
         from .model import _mask_bytes
         S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
         edit_keys = ("inpainting_mask", "inpainted_motion", "init_motion")
@@ -571,7 +588,7 @@ class DSGDiffusion:
             if b.obj is not None and int(np.prod(b.obj.shape)) != J * S:
                 raise ValueError(f"{name} shape {tuple(b.obj.shape)}")
         st = clip.get("stream", 0)
-        sd, sid = (st if isinstance(st, (tuple, list)) else (self._seed, st))
+        sd, sid = (st if isinstance(st, (tuple, list)) else (seed, st))
         K = len(feats) if capacity is None else int(capacity)
         out = np.empty((max(K * (T - S) - (0 if keep_last_tail else S), 0), J), np.float32)
         job.style, job.seed0, job.seed_last, job.audio, job.out = style.ptr, seed0.ptr, last.ptr, audio.ptr, out.ctypes.data
@@ -606,18 +623,11 @@ class DSGDiffusion:
         Clip i is then bit for bit `sample_clip` of that clip alone with ITS skip_timesteps, so fresh generations (0) and edits of any
         depth share the slots of one call (dsg_sample_clip_queue_steps, called only when some clip has the key; `lib.clip_queue_plan`
         with `n_run` is the schedule).  The draw counter advances by max(K_i * (1 + n_run_i))."""
-        lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
+        inners, _ = _inner_lanes(lanes, "sample_clip_queue")
         clips = list(clips)
-        if not lanes or not clips:
+        if not inners or not clips:
             raise ValueError("sample_clip_queue: at least one lane and one clip")
-        inners = []
-        for m in lanes:
-            inner, _ = self._library_model(m, None)
-            if inner is None:
-                raise TypeError("sample_clip_queue drives library denoisers (DSGDenoiser lanes)")
-            inners.append(inner)
         cfg = inners[0].cfg
-        S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
         skips, own_skips = [], False
         for i, clip in enumerate(clips):
             sk = clip.get("skip_timesteps")
@@ -631,25 +641,18 @@ class DSGDiffusion:
         use_torch = L.is_torch(clips[0]["feats"][0])
         edit_keys = ("inpainting_mask", "inpainted_motion", "init_motion")
         stream = L.current_stream_ptr() if use_torch or any(L.is_torch(c.get(k)) for c in clips for k in edit_keys) else None
-        if isinstance(mask_local, str):
-            mask_local = np.ones((T,), np.uint8)
-        mbuf = L.Buf(mask_local, "uint8") if mask_local is not None else L.Buf(None)
-        if mbuf.obj is not None and int(np.prod(mbuf.obj.shape)) != T:
-            raise ValueError(f"sample_clip_queue: mask_local is one mask of {T} entries, shared by every slot")
+        mbuf = _queue_mask(mask_local, cfg.n_poses, "sample_clip_queue")
         jobs = (L.dsg_clip_job * len(clips))()
         edits, edited = (L.dsg_clip_edit * len(clips))(), False
         keep, outs = [mbuf], []
         for i, (job, edit, clip) in enumerate(zip(jobs, edits, clips)):
-            out, bufs, has_edit = self._clip_queue_job(cfg, clip, i, job, edit, use_torch, keep_last_tail)
+            out, bufs, has_edit = self._clip_queue_job(cfg, clip, i, job, edit, use_torch, keep_last_tail, self._seed)
             edited = edited or has_edit
             keep += bufs
             outs.append(out)
         for m in inners:
             m.set_schedule(self)
-        a = L.dsg_sample_args()
-        a.mode, a.skip_timesteps, a.eta = (L.MODE_DDIM if ddim else L.MODE_DDPM), int(skip_timesteps), float(eta)
-        a.seed, a.stream_id, a.draw_base = int(self._seed) & _U64, 0, self._draw
-        a.clip_denoised = int(bool(clip_denoised))
+        a = self._clip_args(ddim, eta, skip_timesteps, clip_denoised)
         hs = (C.c_void_p * len(inners))(*[m.handle for m in inners])
         lib = inners[0].lib
         tail = (int(B), mbuf.p, int(bool(guided)), C.byref(a), int(bool(root_shift)), int(bool(keep_last_tail)), stream)
@@ -831,30 +834,16 @@ class ClipQueue:
     one thread.  Placement is first come, first served (`lib.queue_place`)."""
 
     def __init__(self, diffusion, lanes, B, *, root_shift, keep_last_tail, ddim, eta, skip_timesteps, clip_denoised, guided, mask_local):
-        lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
-        if not lanes:
-            raise ValueError("open_clip_queue: at least one lane")
         self._handle = None
-        self.lanes = []
-        for m in lanes:
-            inner, _ = diffusion._library_model(m, None)
-            if inner is None:
-                raise TypeError("open_clip_queue drives library denoisers (DSGDenoiser lanes)")
-            self.lanes.append(inner)
+        self.lanes, _ = _inner_lanes(lanes, "open_clip_queue")
+        if not self.lanes:
+            raise ValueError("open_clip_queue: at least one lane")
         self.diffusion, self.cfg, self.B, self.keep_last_tail = diffusion, self.lanes[0].cfg, int(B), bool(keep_last_tail)
         self.lib = self.lanes[0].lib
-        T = self.cfg.n_poses
-        if isinstance(mask_local, str):
-            mask_local = np.ones((T,), np.uint8)
-        mbuf = L.Buf(mask_local, "uint8") if mask_local is not None else L.Buf(None)
-        if mbuf.obj is not None and int(np.prod(mbuf.obj.shape)) != T:
-            raise ValueError(f"open_clip_queue: mask_local is one mask of {T} entries, shared by every slot")
+        mbuf = _queue_mask(mask_local, self.cfg.n_poses, "open_clip_queue")
         for m in self.lanes:
             m.set_schedule(diffusion)
-        a = L.dsg_sample_args()
-        a.mode, a.skip_timesteps, a.eta = (L.MODE_DDIM if ddim else L.MODE_DDPM), int(skip_timesteps), float(eta)
-        a.seed, a.stream_id, a.draw_base = int(diffusion._seed) & _U64, 0, diffusion._draw
-        a.clip_denoised = int(bool(clip_denoised))
+        a = diffusion._clip_args(ddim, eta, skip_timesteps, clip_denoised)
         self.skip_timesteps = int(skip_timesteps)
         self._seed = diffusion._seed
         self._advance = 0
@@ -887,74 +876,57 @@ class ClipQueue:
         """One clip dict as `sample_clip_queue` takes it, "skip_timesteps" and the edit keys included.  Returns its ticket (0, 1, ...).
         `out`: the caller's own C-contiguous float32 numpy array [n_out, J] to receive the clip (a playback buffer); rows past
         `rows_ready` are never touched.  Default: an array of the session's."""
-        q, d = self._q(), self.diffusion
-        i = len(self._outs)
-        sk = clip.get("skip_timesteps")
-        if sk is not None and not 0 <= int(sk) < d.num_timesteps:
-            raise ValueError(f"ClipQueue.submit: clip {i}: skip_timesteps {int(sk)} outside [0, {d.num_timesteps - 1}]")
-        tensors = [clip["feats"][0] if len(clip["feats"]) else None] + [clip.get(k) for k in ("inpainting_mask", "inpainted_motion", "init_motion")]
-        use_torch = L.is_torch(tensors[0])
-        stream = L.current_stream_ptr() if any(L.is_torch(t) for t in tensors) else None
-        job, edit = L.dsg_clip_job(), L.dsg_clip_edit()
-        seed_was, d._seed = d._seed, self._seed          # (a bare stream id keeps the seed the session was opened under)
-        try:
-            own, bufs, has_edit = d._clip_queue_job(self.cfg, clip, i, job, edit, use_torch, self.keep_last_tail, who="ClipQueue.submit")
-        finally:
-            d._seed = seed_was
-        if out is not None:
-            if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == own.shape):
-                raise ValueError(f"ClipQueue.submit: clip {i}: out must be a C-contiguous float32 array of shape {own.shape}")
-            job.out = out.ctypes.data
-        else:
-            out = own
-        ticket = C.c_int64(-1)
-        self.lib.check(self.lib.cdll.dsg_queue_submit(q, C.byref(job), C.byref(edit) if has_edit else None, -1 if sk is None else int(sk),
-                                                      C.byref(ticket), stream))
-        assert ticket.value == i
-        self._outs.append(out)
-        dev = [b for b in bufs if b.obj is not None and L.is_torch(b.obj) and b.obj.is_cuda]
-        if dev:
-            self._keep[i] = dev                          # device tensors are read where they are, until the clip is done or cancelled
-        skip = self.skip_timesteps if sk is None else int(sk)
-        self._advance = max(self._advance, int(job.K) * (1 + d.num_timesteps - skip))
-        return i
+        return self._submit(clip, out, None)
 
     def submit_live(self, clip, capacity, out=None) -> int:
         """A live clip (dsg_queue_submit_live): its windows arrive while it runs.  `clip` as for `submit`, without edits; "feats" are the
         windows known now and may be empty.  `capacity`: the most windows it may ever get -- `out` (the caller's, or the session's) is
         [n_out(capacity), J].  Feed it with `append`, end it with `finish` (or `append(..., last=True)`); `rows` / `result` as for every
         clip.  With K windows given it is bit for bit `sample_clip` of those K windows alone, whenever they arrived."""
+        self._q()
+        if any(clip.get(k) is not None for k in ("inpainting_mask", "inpainted_motion", "init_motion")):
+            raise ValueError(f"ClipQueue.submit_live: clip {len(self._outs)}: a live clip takes no edits (their coordinates depend on the final length)")
+        return self._submit(clip, out, capacity)
+
+    def _submit(self, clip, out, capacity):
+        """`submit` (`capacity` None: dsg_queue_submit) and `submit_live` (dsg_queue_submit_live)"""
+        live = capacity is not None
+        who = "ClipQueue.submit_live" if live else "ClipQueue.submit"
         q, d = self._q(), self.diffusion
         i = len(self._outs)
-        if any(clip.get(k) is not None for k in ("inpainting_mask", "inpainted_motion", "init_motion")):
-            raise ValueError(f"ClipQueue.submit_live: clip {i}: a live clip takes no edits (their coordinates depend on the final length)")
         sk = clip.get("skip_timesteps")
         if sk is not None and not 0 <= int(sk) < d.num_timesteps:
-            raise ValueError(f"ClipQueue.submit_live: clip {i}: skip_timesteps {int(sk)} outside [0, {d.num_timesteps - 1}]")
-        feats = list(clip.get("feats") or [])
-        use_torch = bool(feats) and L.is_torch(feats[0])
-        stream = L.current_stream_ptr() if any(L.is_torch(clip.get(k)) for k in ("style", "seed0", "seed_last")) or use_torch else None
+            raise ValueError(f"{who}: clip {i}: skip_timesteps {int(sk)} outside [0, {d.num_timesteps - 1}]")
+        feats = (clip.get("feats") or []) if live else clip["feats"]
+        first = feats[0] if len(feats) else None
+        # (the current torch stream goes with the job as soon as ANY of its tensors is a torch tensor: the library orders its reads behind it)
+        tensors = [first] + [clip.get(k) for k in ("style", "seed0", "seed_last", "inpainting_mask", "inpainted_motion", "init_motion")]
+        stream = L.current_stream_ptr() if any(L.is_torch(t) for t in tensors) else None
         job, edit = L.dsg_clip_job(), L.dsg_clip_edit()
-        seed_was, d._seed = d._seed, self._seed
-        try:
-            own, bufs, _ = d._clip_queue_job(self.cfg, clip, i, job, edit, use_torch, self.keep_last_tail, who="ClipQueue.submit_live", capacity=capacity)
-        finally:
-            d._seed = seed_was
+        # (a bare stream id keeps the seed the session was opened under)
+        own, bufs, has_edit = d._clip_queue_job(self.cfg, clip, i, job, edit, L.is_torch(first), self.keep_last_tail, self._seed, who=who, capacity=capacity)
         if out is not None:
             if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == own.shape):
-                raise ValueError(f"ClipQueue.submit_live: clip {i}: out must be a C-contiguous float32 array of shape {own.shape}")
+                raise ValueError(f"{who}: clip {i}: out must be a C-contiguous float32 array of shape {own.shape}")
             job.out = out.ctypes.data
         else:
             out = own
-        ticket = C.c_int64(-1)
-        self.lib.check(self.lib.cdll.dsg_queue_submit_live(q, C.byref(job), len(feats), -1 if sk is None else int(sk), C.byref(ticket), stream))
+        ticket, skip = C.c_int64(-1), -1 if sk is None else int(sk)
+        if live:
+            self.lib.check(self.lib.cdll.dsg_queue_submit_live(q, C.byref(job), len(feats), skip, C.byref(ticket), stream))
+        else:
+            self.lib.check(self.lib.cdll.dsg_queue_submit(q, C.byref(job), C.byref(edit) if has_edit else None, skip, C.byref(ticket), stream))
         assert ticket.value == i
         self._outs.append(out)
         dev = [b for b in bufs if b.obj is not None and L.is_torch(b.obj) and b.obj.is_cuda]
         if dev:
-            self._keep[i] = dev
-        self._live[i] = [0, 1 + d.num_timesteps - (self.skip_timesteps if sk is None else int(sk))]
-        self._given(i, len(feats))
+            self._keep[i] = dev                          # device tensors are read where they are, until the clip is done or cancelled
+        steps = 1 + d.num_timesteps - (self.skip_timesteps if sk is None else int(sk))
+        if live:
+            self._live[i] = [0, steps]
+            self._given(i, len(feats))
+        else:
+            self._advance = max(self._advance, int(job.K) * steps)
         return i
 
     def _given(self, ticket, n):

@@ -9,6 +9,8 @@ HIP library.  Windows of one clip are serially dependent (window c is seeded by 
 from __future__ import annotations
 
 import argparse
+import collections
+import contextlib
 import functools
 import math
 import os
@@ -16,6 +18,7 @@ import os
 import numpy as np
 
 from . import lib as L
+from .diffusion import _inner_lanes
 
 style2onehot = {
     'Happy': [1, 0, 0, 0, 0, 0], 'Sad': [0, 1, 0, 0, 0, 0], 'Neutral': [0, 0, 1, 0, 0, 0],
@@ -251,6 +254,72 @@ def _per_lane(masks, motions, n):
     return list(zip(masks, motions))
 
 
+def _ones_mask(T, like):
+    """the all-ones y['mask_local'] [1, T] of a window: a torch tensor beside `like`, or numpy, as `like` is"""
+    if L.is_torch(like):
+        import torch
+        return torch.ones(1, T, dtype=torch.bool, device=like.device)
+    return np.ones((1, T), bool)
+
+
+# The two window loops of the reference trees, as the host loop below runs them.  window_y(cfg, feats, c, sty, out, seed0, seed_last,
+# use_torch, mask) -> y of window c (`out`: the windows stitched so far); stitch(out, s, S, smoothing, use_torch);
+# finish(out, cfg, real_n_frames, feature_division, use_torch) -> the clip; keep_last_tail: the coordinates of the clip-level edits.
+_Pipeline = collections.namedtuple("_Pipeline", "window_y stitch finish keep_last_tail")
+_ZEGGS = _Pipeline(
+    lambda cfg, feats, c, sty, out, seed0, seed_last, use_torch, mask:
+        _zeggs_window_y(cfg, feats[c], sty, out[-1] if out else None, seed0, use_torch, mask),
+    _zeggs_stitch,
+    lambda out, cfg, real_n_frames, feature_division, use_torch: _zeggs_finish(out, cfg.n_seed, use_torch),
+    False)
+_DSGPLUS = _Pipeline(
+    lambda cfg, feats, c, sty, out, seed0, seed_last, use_torch, mask:
+        _dsgplus_window_y(cfg, feats, c, sty, seed0 if c == 0 else out[-1][..., -cfg.n_seed:], seed_last, use_torch, mask),
+    lambda out, s, S, smoothing, use_torch: _dsgplus_stitch(out, s, S, use_torch),
+    lambda out, cfg, real_n_frames, feature_division, use_torch:
+        _dsgplus_finish(out, cfg.n_seed, cfg.njoints, real_n_frames, feature_division, use_torch),
+    True)
+
+
+def _host_windows(pipe, diffusion, lanes, feats_per_lane, stys, seed0s, seed_lasts, inp, inits, step, smoothing=False, real_n_frames=None,
+                  feature_division=1, sets=None):
+    """THE host window loop (`windows="host"`) of the four drivers, for n >= 1 lanes: window c of every lane gets its y (`pipe.window_y`,
+    the slice of the lane's clip-level constraint `inp[i]` in it) and its `init_image` (the slice of `inits[i]`), `step(ys, init_images)`
+    samples the n windows -- one library call -- and returns one [B, J, 1, T] per lane, which is stitched onto the lane's clip.  Returns
+    the finished clip of every lane.  `sets`: the `_lane_kernel_sets` of a multi-lane call, in force for the windows and put back BEFORE
+    the clips are finished -- finishing waits for the device, putting the sets back does not and overlaps the last window."""
+    cfg = lanes[0].cfg
+    n, use_torch, klt = len(lanes), L.is_torch(feats_per_lane[0][0]), pipe.keep_last_tail
+    mask = _ones_mask(cfg.n_poses, feats_per_lane[0][0])
+    outs = [[] for _ in range(n)]
+    with sets or contextlib.nullcontext():
+        for c in range(len(feats_per_lane[0])):
+            ys = [_constrained(pipe.window_y(cfg, feats_per_lane[i], c, stys[i], outs[i], seed0s[i], seed_lasts[i], use_torch, mask),
+                               cfg, inp[i][0], inp[i][1], c, klt) for i in range(n)]
+            ss = step(ys, [_window_init(cfg, inits[i], seed0s[i], c, klt) for i in range(n)])
+            for i in range(n):
+                pipe.stitch(outs[i], ss[i], cfg.n_seed, smoothing, use_torch)
+        if any(mk is not None for mk, _ in inp):
+            _release_window_constraint(diffusion, lanes)
+    return [pipe.finish(o, cfg, real_n_frames, feature_division, use_torch) for o in outs]
+
+
+def _lane_step(sample_fn, model, B, skip_timesteps, keyed):
+    """`step` of the single-lane drivers: the reference's call of its `sample_fn` (sample.py:253-265)"""
+    shape = (B, model.cfg.njoints, 1, model.cfg.n_poses)
+    return lambda ys, init_images: [sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": ys[0]}, skip_timesteps=skip_timesteps,
+                                              init_image=init_images[0], progress=False, dump_steps=None, noise=None, const_noise=False,
+                                              **keyed)]
+
+
+def _lanes_step(diffusion, lanes, B, seed, stream_ids, skip_timesteps, ddim, eta, keyed):
+    """`step` of the multi-lane drivers: the lanes' windows in one `p_sample_loop_multi`"""
+    shape = (B, lanes[0].cfg.njoints, 1, lanes[0].cfg.n_poses)
+    return lambda ys, init_images: diffusion.p_sample_loop_multi(list(lanes), shape, [{"y": y} for y in ys], seeds=[seed] * len(lanes),
+                                                                 stream_ids=stream_ids, skip_timesteps=skip_timesteps, ddim=ddim, eta=eta,
+                                                                 init_images=init_images, **keyed)
+
+
 def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, skip_timesteps=0, sample_fn=None,
                   stream_id=None, seed_pose=None, device=None, *, windows="host", ddim=False, eta=0.0, inpainting_mask=None,
                   inpainted_motion=None, init_motion=None, clip_ids=None):
@@ -265,37 +334,19 @@ def generate_clip(model, diffusion, feats, style, seed=123456, smoothing=True, s
     `skip_timesteps` leaves and sampled back (host loop), or the library cuts and noises the same on the device (`windows="library"`).
     `stream_id` (default 0): the Philox stream of the call, shared by the B clips (slot b of it).  `clip_ids` (B ints, instead of
     `stream_id`): clip i draws from the stream (seed, clip_ids[i]) -- the same motion in any batch, slot, lane or rank."""
-    cfg = model.cfg
-    S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
     B = int(feats[0].shape[0])
     stream_id, keyed = _clip_ids(clip_ids, stream_id, B)
-    if _check_windows(windows, sample_fn):
-        diffusion.manual_seed(seed, stream_id)
-        sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
+    library = _check_windows(windows, sample_fn)
+    diffusion.manual_seed(seed, stream_id)          # torch.manual_seed(seed) at sample.py:212
+    sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
+    if library:
         return diffusion.sample_clip(model, list(feats), sty, seed0=seed_pose, root_shift=smoothing, keep_last_tail=False,
                                      ddim=ddim, eta=eta, skip_timesteps=skip_timesteps, inpainting_mask=inpainting_mask,
                                      inpainted_motion=inpainted_motion, init_motion=init_motion, **keyed)
-    sample_fn = sample_fn or _loop_fn(diffusion, ddim, eta)
-    diffusion.manual_seed(seed, stream_id)          # torch.manual_seed(seed) at sample.py:212
-    shape = (B, J, 1, T)
-    out = []
-    if use_torch:
-        import torch
-        mask = torch.ones(1, T, dtype=torch.bool, device=feats[0].device)
-    else:
-        mask = np.ones((1, T), bool)
-    sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
-    for c, feat in enumerate(feats):
-        y = _zeggs_window_y(cfg, feat, sty, out[-1] if out else None, seed_pose, use_torch, mask)
-        y = _constrained(y, cfg, inpainting_mask, inpainted_motion, c, False)
-        s = sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=skip_timesteps,
-                      init_image=_window_init(cfg, init_motion, seed_pose, c, False), progress=False, dump_steps=None, noise=None,
-                      const_noise=False, **keyed)
-        _zeggs_stitch(out, s, S, smoothing, use_torch)
-    if inpainting_mask is not None:
-        _release_window_constraint(diffusion, [model])
-    return _zeggs_finish(out, S, use_torch)
+    step = _lane_step(sample_fn or _loop_fn(diffusion, ddim, eta), model, B, skip_timesteps, keyed)
+    return _host_windows(_ZEGGS, diffusion, [model], [feats], [sty], [seed_pose], [None], [(inpainting_mask, inpainted_motion)], [init_motion],
+                         step, smoothing)[0]
 
 
 def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456, smoothing=True, skip_timesteps=0,
@@ -318,42 +369,27 @@ def generate_clips_streams(lanes, diffusion, feats_per_lane, styles, seed=123456
     n = len(lanes)
     inp = _per_lane(inpainting_mask, inpainted_motion, n)
     inits = _per_lane_init(init_motion, n)
-    cfg = lanes[0].cfg
-    S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     K = len(feats_per_lane[0])
     if any(len(f) != K for f in feats_per_lane) or len(feats_per_lane) != n:
         raise ValueError("one feature list per lane, the same number of windows each")
     use_torch = L.is_torch(feats_per_lane[0][0])
     B = int(feats_per_lane[0][0].shape[0])
     stream_ids, keyed = _lane_clip_ids(clip_ids, stream_ids, n, B)
-    with _lane_kernel_sets(lanes, B, kernel_set):
-        diffusion.manual_seed(seed, 0)
-        shape = (B, J, 1, T)
-        dev = feats_per_lane[0][0].device if use_torch else None
-        if use_torch:
-            import torch
-            mask = torch.ones(1, T, dtype=torch.bool, device=dev)
-        else:
-            mask = np.ones((1, T), bool)
-        per_lane_style = (not L.is_torch(styles)) and np.asarray(styles).ndim == 2 and len(styles) == n and np.asarray(styles).shape[0] == n and B == 1
-        stys = [_style_batch(styles[i] if per_lane_style else styles, B, use_torch, dev) for i in range(n)]
-        if _check_windows(windows):
-            return np.concatenate(diffusion.sample_clip_multi(list(lanes), [list(f) for f in feats_per_lane], stys, root_shift=smoothing,
-                                                              keep_last_tail=False, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
-                                                              seeds=[seed] * n, stream_ids=stream_ids, inpainting_masks=[p[0] for p in inp],
-                                                              inpainted_motions=[p[1] for p in inp], init_motions=inits, **keyed), axis=0)
-        outs = [[] for _ in range(n)]
-        for c in range(K):
-            ys = [{"y": _constrained(_zeggs_window_y(cfg, feats_per_lane[i][c], stys[i], outs[i][-1] if outs[i] else None, None, use_torch, mask),
-                                     cfg, inp[i][0], inp[i][1], c, False)} for i in range(n)]
-            ss = diffusion.p_sample_loop_multi(list(lanes), shape, ys, seeds=[seed] * n, stream_ids=stream_ids,
-                                               skip_timesteps=skip_timesteps, ddim=ddim, eta=eta,
-                                               init_images=[_window_init(cfg, inits[i], None, c, False) for i in range(n)], **keyed)
-            for i in range(n):
-                _zeggs_stitch(outs[i], ss[i], S, smoothing, use_torch)
-        if inpainting_mask is not None:
-            _release_window_constraint(diffusion, lanes)
-    return np.concatenate([_zeggs_finish(o, S, use_torch) for o in outs], axis=0)
+    library, sets = _check_windows(windows), _lane_kernel_sets(lanes, B, kernel_set)
+    diffusion.manual_seed(seed, 0)
+    dev = feats_per_lane[0][0].device if use_torch else None
+    per_lane_style = (not L.is_torch(styles)) and np.asarray(styles).ndim == 2 and len(styles) == n and np.asarray(styles).shape[0] == n and B == 1
+    stys = [_style_batch(styles[i] if per_lane_style else styles, B, use_torch, dev) for i in range(n)]
+    if library:
+        with sets:
+            seqs = diffusion.sample_clip_multi(list(lanes), [list(f) for f in feats_per_lane], stys, root_shift=smoothing,
+                                               keep_last_tail=False, ddim=ddim, eta=eta, skip_timesteps=skip_timesteps,
+                                               seeds=[seed] * n, stream_ids=stream_ids, inpainting_masks=[p[0] for p in inp],
+                                               inpainted_motions=[p[1] for p in inp], init_motions=inits, **keyed)
+    else:
+        step = _lanes_step(diffusion, lanes, B, seed, stream_ids, skip_timesteps, ddim, eta, keyed)
+        seqs = _host_windows(_ZEGGS, diffusion, lanes, feats_per_lane, stys, [None] * n, [None] * n, inp, inits, step, smoothing, sets=sets)
+    return np.concatenate(seqs, axis=0)
 
 
 class _lane_kernel_sets:
@@ -457,40 +493,24 @@ def generate_clips_streams_dsgplus(lanes, diffusion, feats_per_lane, styles, see
     n = len(lanes)
     inp = _per_lane(inpainting_mask, inpainted_motion, n)
     inits = _per_lane_init(init_motion, n)
-    cfg = lanes[0].cfg
-    S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     K = len(feats_per_lane[0])
     if any(len(f) != K for f in feats_per_lane) or len(feats_per_lane) != n or len(seed0s) != n:
         raise ValueError("one feature list and one seed clip per lane, the same number of windows each")
     use_torch = L.is_torch(feats_per_lane[0][0])
     B = int(feats_per_lane[0][0].shape[0])
     stream_ids, keyed = _lane_clip_ids(clip_ids, stream_ids, n, B)
-    with _lane_kernel_sets(lanes, B, kernel_set):
-        diffusion.manual_seed(seed, 0)
-        shape = (B, J, 1, T)
-        dev = feats_per_lane[0][0].device if use_torch else None
-        if use_torch:
-            import torch
-            mask = torch.ones(1, T, dtype=torch.bool, device=dev)
-        else:
-            mask = np.ones((1, T), bool)
-        sty = _style_batch(styles, B, use_torch, dev)
-        if _check_windows(windows):
-            return np.concatenate(_dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division,
-                                                   seed, stream_ids, skip_timesteps, ddim, eta, inp, inits, keyed), axis=0)
-        outs = [[] for _ in range(n)]
-        for c in range(K):
-            ys = [{"y": _constrained(_dsgplus_window_y(cfg, feats_per_lane[i], c, sty, seed0s[i] if c == 0 else outs[i][-1][..., -S:],
-                                                       None if seed_lasts is None else seed_lasts[i], use_torch, mask),
-                                     cfg, inp[i][0], inp[i][1], c, True)} for i in range(n)]
-            ss = diffusion.p_sample_loop_multi(list(lanes), shape, ys, seeds=[seed] * n, stream_ids=stream_ids,
-                                               skip_timesteps=skip_timesteps, ddim=ddim, eta=eta,
-                                               init_images=[_window_init(cfg, inits[i], seed0s[i], c, True) for i in range(n)], **keyed)
-            for i in range(n):
-                _dsgplus_stitch(outs[i], ss[i], S, use_torch)
-        if inpainting_mask is not None:
-            _release_window_constraint(diffusion, lanes)
-    return np.concatenate([_dsgplus_finish(o, S, J, real_n_frames, feature_division, use_torch) for o in outs], axis=0)
+    library, sets = _check_windows(windows), _lane_kernel_sets(lanes, B, kernel_set)
+    diffusion.manual_seed(seed, 0)
+    sty = _style_batch(styles, B, use_torch, feats_per_lane[0][0].device if use_torch else None)
+    if library:
+        with sets:
+            seqs = _dsgplus_library(diffusion, lanes, feats_per_lane, sty, seed0s, seed_lasts, real_n_frames, feature_division,
+                                    seed, stream_ids, skip_timesteps, ddim, eta, inp, inits, keyed)
+    else:
+        step = _lanes_step(diffusion, lanes, B, seed, stream_ids, skip_timesteps, ddim, eta, keyed)
+        seqs = _host_windows(_DSGPLUS, diffusion, lanes, feats_per_lane, [sty] * n, seed0s, [None] * n if seed_lasts is None else seed_lasts,
+                             inp, inits, step, real_n_frames=real_n_frames, feature_division=feature_division, sets=sets)
+    return np.concatenate(seqs, axis=0)
 
 
 def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, seed=123456, skip_timesteps=0,
@@ -506,16 +526,11 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
     features, before the crop to `real_n_frames` and the feature division.  `init_motion` [B, K*stride, J]: an existing clip to edit as in
     `generate_clip`, in the same coordinates (the full J features, K*stride frames).  `stream_id` (default 0) / `clip_ids` (B ints: every
     clip its own Philox stream (seed, clip_ids[i])) as in `generate_clip`."""
-    cfg = model.cfg
-    S, T, J = cfg.n_seed, cfg.n_poses, cfg.njoints
     use_torch = L.is_torch(feats[0])
     B = int(feats[0].shape[0])
     stream_id, keyed = _clip_ids(clip_ids, stream_id, B)
     library = _check_windows(windows, sample_fn)
-    sample_fn = sample_fn or _loop_fn(diffusion, ddim, eta)
     diffusion.manual_seed(seed, stream_id)
-    shape = (B, J, 1, T)
-    out = []
     sty = _style_batch(style, B, use_torch, feats[0].device if use_torch else None)
     if library:
         return _dsgplus_library(diffusion, [model], [feats], sty, [seed0], None if seed_last is None else [seed_last], real_n_frames,
@@ -524,30 +539,15 @@ def generate_clip_dsgplus(model, diffusion, feats, style, seed0, real_n_frames, 
                                           None if inpainted_motion is None else [inpainted_motion], 1),
                                 None if init_motion is None else [init_motion],
                                 {"clip_streams": [keyed["clip_streams"]]} if keyed else None)[0]
-    if use_torch:
-        import torch
-        dev = feats[0].device
-        mask = torch.ones(1, T, dtype=torch.bool, device=dev)
-    else:
-        mask = np.ones((1, T), bool)
-    for c in range(len(feats)):
-        y = _dsgplus_window_y(cfg, feats, c, sty, seed0 if c == 0 else out[-1][..., -S:], seed_last, use_torch, mask)
-        y = _constrained(y, cfg, inpainting_mask, inpainted_motion, c, True)
-        s = sample_fn(model, shape, clip_denoised=False, model_kwargs={"y": y}, skip_timesteps=skip_timesteps,
-                      init_image=_window_init(cfg, init_motion, seed0, c, True), progress=False, dump_steps=None, noise=None,
-                      const_noise=False, **keyed)
-        _dsgplus_stitch(out, s, S, use_torch)
-    if inpainting_mask is not None:
-        _release_window_constraint(diffusion, [model])
-    return _dsgplus_finish(out, S, J, real_n_frames, feature_division, use_torch)
+    step = _lane_step(sample_fn or _loop_fn(diffusion, ddim, eta), model, B, skip_timesteps, keyed)
+    return _host_windows(_DSGPLUS, diffusion, [model], [feats], [sty], [seed0], [seed_last], [(inpainting_mask, inpainted_motion)], [init_motion],
+                         step, real_n_frames=real_n_frames, feature_division=feature_division)[0]
 
 
 def _queue_lanes(lanes, clips, B):
     """(the lanes' DSGDenoisers, guided, B) of a clip-queue call: guidance is on when any clip carries a scale; B defaults to
     min(max_batch, ceil(N / lanes)) -- max_batch halved with guidance, the twins ride in the same batch."""
-    from .model import ClassifierFreeSampleModel
-    lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
-    inners = [m.model if isinstance(m, ClassifierFreeSampleModel) else m for m in lanes]
+    inners, _ = _inner_lanes(lanes, "sample_clip_queue")
     guided = any(c.get("scale") is not None for c in clips)
     if B is None:
         room = min(m.max_batch for m in inners) // (2 if guided else 1)
@@ -555,13 +555,23 @@ def _queue_lanes(lanes, clips, B):
     return inners, guided, int(B)
 
 
-def _queue_stream(clip, i):
-    return int(clip.get("clip_id", i))
-
-
-def _queue_edits(clip):
-    """the per-clip edits of a clip-queue dict (and the clip's own skip_timesteps, the strength of its edit), passed through as `DSGDiffusion.sample_clip_queue` takes them"""
-    return {k: clip[k] for k in ("inpainting_mask", "inpainted_motion", "init_motion", "skip_timesteps") if clip.get(k) is not None}
+def _queue_job(cfg, clip, i, dsgplus, live=False):
+    """One clip dict of the queue drivers as the job dict `DSGDiffusion.sample_clip_queue` / `ClipQueue.submit[_live]` take: the style
+    flat, "seed_pose" as "seed0", "clip_id" (default `i`: the clip's index or ticket) as "stream", the clip's edits and its own
+    "skip_timesteps" passed through; DSG+: the per-window features as `_dsgplus_window_y` builds them.  `live`: a live clip -- no edits,
+    and "feats" are taken as they are (`_ClipQueueSession._window_audio` has built them)."""
+    c = clip
+    job = {"feats": c["feats"], "style": c["style"] if L.is_torch(c["style"]) else np.asarray(c["style"], np.float32).reshape(-1),
+           "seed0": c.get("seed_pose"), "scale": c.get("scale"), "stream": int(c.get("clip_id", i))}
+    job.update({k: c[k] for k in (("skip_timesteps",) if live else ("inpainting_mask", "inpainted_motion", "init_motion", "skip_timesteps"))
+                if c.get(k) is not None})
+    if dsgplus:
+        job["seed0"], job["seed_last"] = c["seed_pose"], c.get("seed_last")
+        if not live:
+            feats = [f if f.ndim == 3 else f[None] for f in c["feats"]]
+            job["feats"] = [_dsgplus_window_y(cfg, feats, w, None, c["seed_pose"], c.get("seed_last"), L.is_torch(feats[0]), None)["audio"]
+                            for w in range(len(feats))]
+    return job
 
 
 def generate_clip_queue(lanes, diffusion, clips, seed=123456, smoothing=True, skip_timesteps=0, ddim=False, eta=0.0,
@@ -579,8 +589,7 @@ def generate_clip_queue(lanes, diffusion, clips, seed=123456, smoothing=True, sk
     order given."""
     clips = list(clips)
     inners, guided, B = _queue_lanes(lanes, clips, B)
-    jobs = [{"feats": c["feats"], "style": np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"],
-             "seed0": c.get("seed_pose"), "scale": c.get("scale"), "stream": _queue_stream(c, i), **_queue_edits(c)} for i, c in enumerate(clips)]
+    jobs = [_queue_job(inners[0].cfg, c, i, False) for i, c in enumerate(clips)]
     with _lane_kernel_sets(inners, B, kernel_set):
         diffusion.manual_seed(seed, 0)
         return diffusion.sample_clip_queue(inners, jobs, B, root_shift=smoothing, keep_last_tail=False, ddim=ddim, eta=eta,
@@ -600,14 +609,7 @@ def generate_clip_queue_dsgplus(lanes, diffusion, clips, seed=123456, skip_times
     clips = list(clips)
     inners, guided, B = _queue_lanes(lanes, clips, B)
     cfg = inners[0].cfg
-    jobs = []
-    for i, c in enumerate(clips):
-        use_torch = L.is_torch(c["feats"][0])
-        feats = [f if f.ndim == 3 else f[None] for f in c["feats"]]
-        audio = [_dsgplus_window_y(cfg, feats, w, None, c["seed_pose"], c.get("seed_last"), use_torch, None)["audio"] for w in range(len(feats))]
-        jobs.append({"feats": audio, "style": np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"],
-                     "seed0": c["seed_pose"], "seed_last": c.get("seed_last"), "scale": c.get("scale"), "stream": _queue_stream(c, i),
-                     **_queue_edits(c)})
+    jobs = [_queue_job(cfg, c, i, True) for i, c in enumerate(clips)]
     with _lane_kernel_sets(inners, B, kernel_set):
         diffusion.manual_seed(seed, 0)
         seqs = diffusion.sample_clip_queue(inners, jobs, B, root_shift=False, keep_last_tail=True, ddim=ddim, eta=eta,
@@ -621,10 +623,8 @@ class _ClipQueueSession:
     the lane); close puts back what they ran before, as `_lane_kernel_sets` does."""
 
     def __init__(self, lanes, diffusion, dsgplus, seed, skip_timesteps, ddim, eta, kernel_set, B, guided, root_shift, feature_division):
-        from .model import ClassifierFreeSampleModel
-        lanes = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes]
-        inners = [m.model if isinstance(m, ClassifierFreeSampleModel) else m for m in lanes]
-        guided = bool(guided) or any(isinstance(m, ClassifierFreeSampleModel) for m in lanes)
+        inners, wrapped = _inner_lanes(lanes, "open_clip_queue")
+        guided = bool(guided) or any(wrapped)
         if B is None:
             B = max(1, min(m.max_batch for m in inners) // (2 if guided else 1))
         self.cfg, self.dsgplus, self.feature_division, self._real, self._n = inners[0].cfg, dsgplus, feature_division, {}, 0
@@ -647,20 +647,10 @@ class _ClipQueueSession:
 
     def submit(self, clip) -> int:
         """One clip dict of `generate_clip_queue` (`generate_clip_queue_dsgplus` for a DSG+ session); "clip_id" defaults to the ticket."""
-        c, cfg = clip, self.cfg
-        style = np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"]
-        job = {"style": style, "scale": c.get("scale"), "stream": _queue_stream(c, self._n), **_queue_edits(c)}
-        if self.dsgplus:
-            use_torch = L.is_torch(c["feats"][0])
-            feats = [f if f.ndim == 3 else f[None] for f in c["feats"]]
-            job["feats"] = [_dsgplus_window_y(cfg, feats, w, None, c["seed_pose"], c.get("seed_last"), use_torch, None)["audio"] for w in range(len(feats))]
-            job["seed0"], job["seed_last"] = c["seed_pose"], c.get("seed_last")
-        else:
-            job["feats"], job["seed0"] = c["feats"], c.get("seed_pose")
-        t = self.queue.submit(job)
+        t = self.queue.submit(_queue_job(self.cfg, clip, self._n, self.dsgplus))
         self._n += 1
         if self.dsgplus:
-            self._real[t] = int(c["real_n_frames"])
+            self._real[t] = int(clip["real_n_frames"])
         return t
 
     def _window_audio(self, ticket, feats):
@@ -682,19 +672,9 @@ class _ClipQueueSession:
     def submit_live(self, clip, capacity) -> int:
         """A live clip (`ClipQueue.submit_live`): the clip dict of `submit` without edits and without "real_n_frames"; "feats" are the
         windows known now and may be empty; `capacity`: the most windows it may ever get.  Feed it with `append`, end it with `finish`."""
-        c = clip
-        style = np.asarray(c["style"], np.float32).reshape(-1) if not L.is_torch(c["style"]) else c["style"]
-        job = {"style": style, "scale": c.get("scale"), "stream": _queue_stream(c, self._n)}
-        if c.get("skip_timesteps") is not None:
-            job["skip_timesteps"] = c["skip_timesteps"]
         ticket = self._n                                 # (tickets count submissions)
-        if self.dsgplus:
-            self._live[ticket] = [c["seed_pose"], c.get("seed_last"), None]
-            job["seed0"], job["seed_last"] = c["seed_pose"], c.get("seed_last")
-        else:
-            self._live[ticket] = None
-            job["seed0"] = c.get("seed_pose")
-        job["feats"] = self._window_audio(ticket, c.get("feats") or [])
+        self._live[ticket] = [clip["seed_pose"], clip.get("seed_last"), None] if self.dsgplus else None
+        job = _queue_job(self.cfg, dict(clip, feats=self._window_audio(ticket, clip.get("feats") or [])), ticket, self.dsgplus, live=True)
         t = self.queue.submit_live(job, capacity)
         assert t == ticket
         self._n += 1
