@@ -74,7 +74,7 @@ struct Ctx {
     char* ka_dev = nullptr; size_t ka_cap = 0;
     std::vector<char> ka_host;
     std::vector<Launch> plan;
-    double last_ms = 0.0;
+    double run_ms = 0.0;
     bool nofence = false;   // no acquire / release between the packets of the loop: everything the loop writes is coherent without
                             // cache maintenance (uncached buffers, dsg_hip.cpp uc_mode)
     char bdf[32] = {0};     // PCI address of the agent the queue lives on (== the HIP device's: checked in init)
@@ -334,7 +334,7 @@ inline bool run(Ctx& c, int n_steps, double timeout_s) {
     }
     const uint64_t budget_ns = (uint64_t)(timeout_s * 1e9);
     const hsa_signal_value_t v = hsa_signal_wait_scacquire(c.done, HSA_SIGNAL_CONDITION_LT, 1, budget_ns, HSA_WAIT_STATE_ACTIVE);
-    c.last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c.run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (v >= 1) { c.err = "completion signal timed out"; return false; }
 #ifdef DSG_STAMPS
     if (tr.armed) {
@@ -407,7 +407,7 @@ inline bool run(Ctx& c, int n_steps, double timeout_s) {
 
 // Several lanes at once, one host thread: every lane's chain of dependent packets lives on its own queue, so the command
 // processor overlaps them; the host deals one step at a time to every lane that has room (a full queue is skipped, never
-// waited on, so one slow lane cannot starve the others).  last_ms of each lane = first doorbell of the call to ITS completion.
+// waited on, so one slow lane cannot starve the others).  run_ms of each lane = first doorbell of the call to ITS completion.
 inline bool run_multi(Ctx** cs, const int* n_steps, int n, double timeout_s, std::string& err) {
     std::vector<int> next(n, 0);
     for (int i = 0; i < n; ++i) hsa_signal_store_relaxed(cs[i]->done, 1);
@@ -427,10 +427,10 @@ inline bool run_multi(Ctx** cs, const int* n_steps, int n, double timeout_s, std
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) { err = "queues stalled"; return false; }
     }
     for (int i = 0; i < n; ++i) {
-        if (n_steps[i] <= 0) { cs[i]->last_ms = 0.0; continue; }
+        if (n_steps[i] <= 0) { cs[i]->run_ms = 0.0; continue; }
         const double left = timeout_s - std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const hsa_signal_value_t v = hsa_signal_wait_scacquire(cs[i]->done, HSA_SIGNAL_CONDITION_LT, 1, (uint64_t)(std::max(left, 1.0) * 1e9), HSA_WAIT_STATE_ACTIVE);
-        cs[i]->last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        cs[i]->run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (v >= 1) { err = cs[i]->err = "completion signal timed out"; return false; }
     }
     return true;

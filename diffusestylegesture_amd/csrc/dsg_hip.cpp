@@ -129,15 +129,22 @@ static Core classify_core(int D, int H, int Tp) {
     return Core::OTHER;
 }
 
-// The per-element noise streams of one step loop, as `dyn` takes them: B keys {seed lo, seed hi, stream lo, stream hi} at word 8 (seeds ==
-// false: the seed words come from args->seed; const_noise: element 0's key for everyone), pairs {offset, hold} (GemmArgs::draw_off, DrawOff)
-// at 8 + 4 max_batch, the start kernels' offsets at 8 + 6 max_batch.  offs / starts / holds are a clip queue's: with per-clip skip_timesteps
-// a slot that starts `hold` loop indices into the round draws its steps at offs = starts - hold and its start at starts.  Null in every other
-// keyed call: zeros, written with every keyed upload, so nothing of a queue's round outlives it on the device.  Host storage of the builder's
-struct NoiseTable {
+// The per-element noise streams of one step loop, as the noise block takes them (GemmArgs::dyn has the layout): B keys {seed lo, seed hi, stream
+// lo, stream hi} (seeds == false: the seed words come from args->seed; const_noise: element 0's key for everyone).  offs / starts / holds are a
+// clip queue's: with per-clip skip_timesteps a slot that starts `hold` loop indices into the round draws its steps at offs = starts - hold and its
+// start at starts.  Null in every other keyed call: zeros, written with every keyed upload, so nothing of a queue's round outlives it on the device
+struct NoiseTable {      // (host storage of the builder's)
     int B = 0; bool seeds = false;      // B == 0: unkeyed
-    const unsigned *keys = nullptr, *offs = nullptr, *starts = nullptr;
-    const int* holds = nullptr;
+    const unsigned *keys = nullptr, *offs = nullptr, *starts = nullptr; const int* holds = nullptr;
+};
+// What the last sampling call on a handle did: what the dsg_last_* exports read, and nothing else.  While a call runs, its facts live in its
+// own storage (SampleJob; the sums of a clip's windows, of a queue's rounds); commit_report writes them here once per lane where the call
+// succeeds, so a call that is refused or fails, and a dsg_queue_run without a round, leave the previous report whole
+struct LastRun {
+    bool sampled = false; int steps = 0;      // a sampling call has completed; its steps (a clip: K * n_run, a queue: the summed round lengths)
+    int path = 0; bool nofence = false;       // of its last window / round: 0 HIP launches, 1 AQL packets, 2 hipGraph replay; packets without fences
+    double host_ms = -1.0;                    // >= 0: taken on the host (the AQL clock; a sum over windows / rounds); < 0: events ev_t0 .. ev_t1, resolved when asked
+    int kset = -1;                            // the kernel set of the last step; dsg_forward commits this alone (no sampling call); < 0: no step has run
 };
 struct dsg_handle {
     dsg_config cfg;
@@ -171,7 +178,6 @@ struct dsg_handle {
     // window hand-off of dsg_sample_clip (k_window_handoff): the previous window's last S frames [B][S][J], two copies used in turn (a hand-off reads
     // one and writes the other), and the stitched clip when the caller's `out` is host memory.  Allocated on first use
     float* clip_tail[2] = {nullptr, nullptr}; float* clip_out = nullptr; size_t clip_out_cap = 0;
-    bool clip_timing = false; double clip_ms = 0.0;      // the last sampling call was dsg_sample_clip: dsg_last_sample_ms reports the sum over its windows
     // clip-level inpainting constraint (dsg_set_clip_inpainting): the library's own copy in the stitched clip's coordinates [cinpB][cinp_frames][J];
     // cinpB == 0: off.  Allocated on first use, grown when needed (cinp_cap elements).  dsg_sample_clip cuts window c's constraint out of it into
     // inp32 / inp_mask (k_clip_inp_window)
@@ -179,10 +185,8 @@ struct dsg_handle {
     // clip-level init motion (dsg_set_clip_init): the library's own copy [cinitB][cinit_frames][J] in the stitched clip's coordinates; cinitB == 0:
     // off.  Allocated on first use, grown when needed (cinit_cap elements).  Only dsg_sample_clip reads it (k_clip_x_in)
     int cinitB = 0, cinit_frames = 0; float* cinit_motion = nullptr; size_t cinit_cap = 0;
-    int last_path = -1;                  // submission path of the last dsg_sample: 0 HIP launches, 1 AQL packets, 2 hipGraph replay
-    bool last_nofence = false;           // ... and whether its packets went without fences
+    LastRun last;                        // the report of the last sampling call (commit_report)
     int kset_req = DSG_KSET_AUTO;        // dsg_set_kernel_set: the kernel set every step of this handle runs (AUTO: by batch, select_kernels)
-    int last_kset = -1;                  // ... and the one the last dsg_forward / dsg_sample ran
     // state / activations
     float *xs32 = nullptr, *partial = nullptr, *X0 = nullptr, *pre1 = nullptr, *pre2 = nullptr, *Xn = nullptr,
           *X1 = nullptr, *fwd_out = nullptr, *io_tmp = nullptr, *io_tmp2 = nullptr, *ext_noise = nullptr;
@@ -194,8 +198,7 @@ struct dsg_handle {
     StepCtl* ctl = nullptr;              // device-resident step control (dsg_kernels.h: StepCtl)
     int* t_arr = nullptr; unsigned* dyn = nullptr;
     // per-element noise streams (dsg_set_noise_streams): nkB user batch elements, 0 = off; nkeys = their keys {seed lo, seed hi, stream lo,
-    // stream hi} (nk_seeds == false: the seed words come from args->seed, per call).  dyn_host: the staging copy of `dyn`
-    // (8 + 7 * max_batch words: + the draw offsets, see NoiseTable) every sampling call uploads
+    // stream hi} (nk_seeds == false: the seed words come from args->seed, per call).  dyn_host: the staging copy of `dyn` every sampling call uploads
     int nkB = 0; bool nk_seeds = false; std::vector<unsigned> nkeys, dyn_host;
     // What a lane holds for the rounds of a clip queue (dsg_sample_clip_queue*, dsg_queue_*; QueueRound fills all of it).  The device buffers
     // are allocated on first use (queue_lane_ready); the *_host vectors are the copies uploaded per round, which outlive the uploads
@@ -229,8 +232,6 @@ struct dsg_handle {
     int fence_next = 0;                  // step_launch: the next recorded packet acquires (1) / releases (2) at agent scope
     int aql_mode = 1;                    // DSG_AQL: 1 (default) = AQL packets for the eager step loop, 0 = HIP launches
     bool aql_warned = false;
-    bool aql_timing = false;             // the last dsg_sample was timed by the host clock around the AQL run
-    double aql_ms = 0.0;
     // A/B switches of the batched sets, read ONCE at dsg_create (round-4 advisor: they used to be getenv calls in select_kernels /
     // run_step, i.e. in the hot path and outside the hipGraph key): -1 = not set
     int env_loc64_from = 2048;           // DSG_LOC64_FROM=<workgroups>: k_loc as two waves per (head, window, clip) from that many of them (test hook / A/B)
@@ -251,7 +252,6 @@ struct dsg_handle {
         return std::tie(B, mode, mb, cn, n_run, n_tab, flags, kset) < std::tie(o.B, o.mode, o.mb, o.cn, o.n_run, o.n_tab, o.flags, o.kset); } };
     struct GVal { hipGraphExec_t exec; hipGraph_t graph; int steps; };
     std::map<GKey, GVal> graphs;
-    float last_ms = -1.f; int last_steps = 0; bool timing_valid = false;
 };
 
 // bf16 activations (DSG_PREC_BF16, DSG_PREC_BF16W2): the compute-dtype shadows / fragment layouts of the bf16 kernels
@@ -650,8 +650,8 @@ extern "C" int dsg_create(const dsg_config* c, dsg_handle** out) {
     CHK(dalloc(h, &h->mask, (size_t)B * h->T));
     CHK(dalloc(h, &h->ctr, 8));
     CHK(dalloc(h, &h->cfg_scale, (size_t)B));
-    CHK(dalloc(h, &h->dyn, 8 + 7 * (size_t)B));      // + the key table of keyed noise (GemmArgs::dyn) + its draw offsets and holds (GemmArgs::draw_off) + the start offsets
-    h->dyn_host.assign(8 + 7 * (size_t)B, 0u);
+    CHK(dalloc(h, &h->dyn, GemmArgs::dyn_words(B)));      // the noise block (GemmArgs::dyn)
+    h->dyn_host.assign(GemmArgs::dyn_words(B), 0u);
     CHK(dalloc(h, &h->t_arr, (size_t)B));
     // the xs32 master is read as a GEMM operand in fp32 mode: rows padded to a 16-row tile exist (allocated above)
     return 0;
@@ -1289,8 +1289,8 @@ extern "C" int dsg_recommend_kernel_set(dsg_handle* h, int B, int lanes, int* se
 }
 extern "C" int dsg_last_kernel_set(dsg_handle* h, int* set) {
     if (!h || !set) return fail(DSG_E_INVALID, "null argument");
-    if (h->last_kset < 0) return fail(DSG_E_STATE, "no step has run");
-    *set = h->last_kset;
+    if (h->last.kset < 0) return fail(DSG_E_STATE, "no step has run");
+    *set = h->last.kset;
     return 0;
 }
 
@@ -1644,7 +1644,7 @@ static GemmArgs gemm_linear2(const dsg_handle* h, const GemmArgs& z, int M, cons
 static GemmArgs gemm_pose_head(const dsg_handle* h, const GemmArgs& z, int M, const Layer& last) {
     GemmArgs g = gemm_of(h, z, M, h->Jp, h->D, h->Wp_out, h->b_out);
     g.X = h->pre2; g.ln_g = last.g2; g.ln_b = last.be2;
-    g.xs32 = h->xs32; g.xsA = is_bf16(h) ? h->xsA : nullptr; g.fwd_out = h->fwd_out; g.dyn = h->dyn; g.draw_off = h->dyn + 8 + 4 * (size_t)h->Bmax;
+    g.xs32 = h->xs32; g.xsA = is_bf16(h) ? h->xsA : nullptr; g.fwd_out = h->fwd_out; g.dyn = h->dyn; g.draw_off = h->dyn + GemmArgs::dyn_pairs(h->Bmax);
     return g;
 }
 // the step control of the two GEMMs that read / advance it (k_in, pose head)
@@ -1983,7 +1983,6 @@ static int run_step(dsg_handle* h, const StepCtx& c) {
             CHK((launch_gemm_w<P, PRO_LN, EPI_OUT>(h, g, ks)));
         }
     }
-    h->last_kset = ks.set;
     return 0;
 }
 // ---- diagnostics: time a chain of ONE phase kernel (graph replay) to separate launch floor, kernel body and
@@ -2363,6 +2362,7 @@ extern "C" int dsg_forward(dsg_handle* h, const float* x, const int64_t* t, floa
     CHK(ensure_set_buffers(h, c.ks));
     CHK(launch_x_in(h, xd, nullptr, 0, 0.f, 0.f, 0, nk, nullptr, nullptr, 0, B, c.ks));
     CHK(run_step_p(h, c));
+    h->last.kset = c.ks.set;      // (no sampling call: the rest of the report stays)
     CHK(from_dev(h, out, h->fwd_out, n));
     CHK(order_before(h, stream));
     return 0;
@@ -2439,7 +2439,13 @@ struct SampleJob {
     int first = 0;                       // absolute loop index of its first step (dsg_sample_args.first_step: a resumed chain)
     bool dumping = false, aql = false;
     int spg = -1;
+    // what the loop did, for the call's report (run_lanes / sample_run_hip): LastRun::path, ::nofence, and with AQL packets (>= 0) the milliseconds
+    int path = 0; bool nofence = false; double clock_ms = -1.0;      // on the host clock from the first doorbell to the completion signal
 };
+// The one writer of a handle's report (beside dsg_forward, for the kernel set alone): once per lane, where a sampling call succeeds
+static void commit_report(dsg_handle* h, const SampleJob& job, int steps, double host_ms) {
+    h->last = LastRun{true, steps, job.path, job.nofence, host_ms, job.c.ks.set};
+}
 
 #ifndef DSG_EMU
 // One-time check of the premise of the fence-free loop on the device it is about to run on (advisor, round 2): a hand-off
@@ -2506,132 +2512,134 @@ static HostProf g_hp;
 #define HP_START() ((void)0)
 #define HP_LAP(i) ((void)0)
 #endif
-static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, const RunMode& m, int B, void* stream, SampleJob& job) {
+// sample_prepare, piece by piece (what a piece enqueues goes on h->stream).  The refusals that need nothing but the arguments; rows: B + the twins of guidance
+static int sample_check(dsg_handle* h, const dsg_sample_args* a, const RunMode& m, int B, int* rows) {
     if (!h || !a) return fail(DSG_E_INVALID, "dsg_sample: null argument");
     if (!h->finalized || !h->cond_set) return fail(DSG_E_STATE, "dsg_sample before finalize / set_window_cond");
-    int rows = 0;
-    CHK(rows_for(h, B, &rows));
-    const NoiseTable& nt = m.noise;
+    CHK(rows_for(h, B, rows));
     // (the user's batches: what user_run_mode took over; a window's cut and a queue's round bring the call's own B)
     if (m.inpaint > 0 && m.inpaint != B) return fail(DSG_E_INVALID, "batch differs from the batch of dsg_set_inpainting");
-    if (nt.B > 0 && nt.B != B)
-        return fail(DSG_E_INVALID, "batch " + std::to_string(B) + " differs from the batch of dsg_set_noise_streams (" + std::to_string(nt.B) + ")");
+    if (m.noise.B > 0 && m.noise.B != B)
+        return fail(DSG_E_INVALID, "batch " + std::to_string(B) + " differs from the batch of dsg_set_noise_streams (" + std::to_string(m.noise.B) + ")");
     if (a->mode != DSG_MODE_DDPM && a->mode != DSG_MODE_DDIM) return fail(DSG_E_INVALID, "mode");
     // (dump points are allowed with DDIM: ddim_sample_loop_progressive is built on them; the Python ddim_sample_loop itself
     // refuses dump_steps like the reference, gaussian_diffusion.py:913-916)
     if (a->mode == DSG_MODE_DDIM && a->const_noise)
         return fail(DSG_E_NOT_IMPLEMENTED, "ddim_sample_loop: const_noise (gaussian_diffusion.py:915-916)");
+    return 0;
+}
+// what the start kernel of a chain reads: explicit x_T inputs on the device (null: none), the call's key, the noise block's tables (null: unkeyed)
+struct StartIn { const float *noise = nullptr, *init = nullptr; NoiseKey nk; const unsigned *keys = nullptr, *offs = nullptr; };
+// The noise block (GemmArgs::dyn), filled in dyn_host and uploaded in front of the start kernel, which reads its tables too (handed back in s, with the key)
+static int upload_noise_block(dsg_handle* h, const dsg_sample_args* a, const NoiseTable& nt, StartIn& s) {
+    unsigned *dyn = h->dyn_host.data(), *key = dyn + GemmArgs::DYN_KEY;
+    set_noise_key(key, a->seed, a->stream_id);
+    s.nk = NoiseKey{key[0], key[1], key[2], key[3]};
+    dyn[GemmArgs::DYN_DRAW] = a->draw_base + 1u;
+    const size_t pairs = GemmArgs::dyn_pairs(h->Bmax), starts = GemmArgs::dyn_starts(h->Bmax);
+    for (int b = 0; b < nt.B; ++b) {
+        const unsigned* k = nt.keys + 4 * (a->const_noise ? 0 : b);
+        key = dyn + GemmArgs::DYN_KEYS + 4 * b;
+        key[0] = nt.seeds ? k[0] : s.nk.k0; key[1] = nt.seeds ? k[1] : s.nk.k1; key[2] = k[2]; key[3] = k[3];
+        dyn[pairs + 2 * b] = nt.offs ? nt.offs[b] : 0u; dyn[pairs + 2 * b + 1] = nt.holds ? (unsigned)nt.holds[b] : 0u;
+        dyn[starts + b] = nt.starts ? nt.starts[b] : 0u;
+    }
+    const bool keyed = nt.B > 0;
+    HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? starts + (size_t)nt.B : GemmArgs::DYN_DRAW + 1) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    s.keys = keyed ? h->dyn + GemmArgs::DYN_KEYS : nullptr; s.offs = keyed ? h->dyn + starts : nullptr;      // (offs: the start kernels'; GemmArgs::draw_off is the pair table)
+    return 0;
+}
+// x_T (gaussian_diffusion.py:701-713) into the state, in the layout of the job's kernel set
+static int start_chain(dsg_handle* h, const dsg_sample_args* a, const RunMode& m, const SampleJob& job, const StartIn& s) {
+    const float qa = (float)h->sched.sqrt_ac[h->n_run - 1], qb = (float)h->sched.sqrt_1mac[h->n_run - 1];      // (q_sample at the chain's first timestep)
+    if (m.start == RunMode::CLIPQ_X_IN)      // (a round of the clip queue on a lane that runs a job with an init motion, or of a call with per-clip skips)
+        return launch_clip_x_in_q(h, s.nk, s.keys, s.offs, a->draw_base, job.B, job.c.ks);
+    if (m.start == RunMode::CLIP_X_IN)       // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
+        return launch_clip_x_in(h, m.c, m.n_out, qa, qb, s.nk, s.keys, s.offs, a->draw_base, job.B, job.c.ks);
+    const int do_q = (job.first == 0 && (a->skip_timesteps > 0 || a->init_image)) ? 1 : 0;      // (a resumed chain starts from x_t as handed over)
+    return launch_x_in(h, s.noise, s.init, do_q, qa, qb, s.noise ? 0 : 1, s.nk, s.keys, s.offs, a->draw_base, job.B, job.c.ks);
+}
+// replayed per-step noise [steps of the whole chain][n]: where it is on the device, or its upload
+static int replayed_noise(dsg_handle* h, const float* step_noise, size_t n, const float** ext) {
+    *ext = step_noise;
+    if (!step_noise || is_device_ptr(step_noise)) return 0;
+    const size_t ne = (size_t)h->n_run * n;
+    if (ne > h->ext_noise_cap) { CHK(dalloc(h, &h->ext_noise, ne, false)); h->ext_noise_cap = ne; }
+    HIPCHK(hipMemcpyAsync(h->ext_noise, step_noise, ne * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    *ext = h->ext_noise;
+    return 0;
+}
+#ifndef DSG_EMU
+// The step loop as hand-written AQL packets (dsg_aql.h): one recording pass of run_step (no launch), argument blocks to device memory; job.aql says that
+// the plan stands, and run_lanes then sends n_run x the same packets on the handle's own HSA queue.  Any failure before the first packet falls back to
+// the HIP launches; a failure after submission is an error.  Not for dump points, nor where a graph is wanted
+static int plan_aql(dsg_handle* h, SampleJob& job) {
+    if (h->aql_mode != 1 || job.dumping || (job.spg > 0 && job.n_run >= job.spg) || job.n_run <= 0) return 0;
+    bool planned = dsg_aql::init(h->aql, h->cfg.device, (const void*)&dsg_version);
+    const bool nofence = planned && h->uc_mode == 1 && uc_selfcheck(h);
+    HP_LAP(3);
+    if (planned) {
+        dsg_aql::begin(h->aql);
+        const int rc = run_step_p(h, job.c);
+        HP_LAP(4);
+        planned = dsg_aql::finish(h->aql) && rc == 0;
+        HP_LAP(5);
+        h->aql.recording = false;
+        h->aql.nofence = nofence;            // fence-free packets (see uc_mode; 2: uncached buffers behind the usual fences)
+    }
+    if (!planned) {
+        if (!h->aql_warned) { fprintf(stderr, "libdsg_hip: AQL path unavailable (%s); using HIP launches\n", h->aql.err.c_str()); h->aql_warned = true; }
+        h->aql_mode = 0;
+        return 0;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));         // state / control block / conditioning are in place
+    job.aql = true;
+    return 0;
+}
+#endif
+
+static int sample_prepare(dsg_handle* h, const dsg_sample_args* a, const RunMode& m, int B, void* stream, SampleJob& job) {
+    int rows = 0;
+    CHK(sample_check(h, a, m, B, &rows));
     HIPCHK(hipSetDevice(h->cfg.device));
     HP_START();
     CHK(order_after(h, stream));
-    int n_run = 0;
-    CHK(build_step_tables(h, a->mode, a->skip_timesteps, a->eta, &n_run));
+    int n_total = 0;
+    CHK(build_step_tables(h, a->mode, a->skip_timesteps, a->eta, &n_total));
     HP_LAP(0);
-    // a chain may be run in pieces (first_step / max_steps: the lazy generator forms of the loops): steps [first, first + n_iter)
-    const int first = a->first_step, n_total = n_run;
+    // a chain may be run in pieces (first_step / max_steps: the lazy generator forms of the loops): steps [first, first + n_run)
+    const int first = a->first_step;
     if (first < 0 || first >= n_total || a->max_steps < 0) return fail(DSG_E_INVALID, "first_step / max_steps out of range");
     if (first > 0 && !a->init_noise) return fail(DSG_E_INVALID, "first_step > 0 resumes a chain: init_noise must hold x_t of that step");
-    const int n_iter = a->max_steps > 0 ? std::min(a->max_steps, n_total - first) : n_total - first;
+    job = SampleJob();      // (a caller's job serves window after window); n_run: the steps of this call (the tables keep the whole chain: h->n_run)
+    job.B = B; job.first = first; job.n_run = a->max_steps > 0 ? std::min(a->max_steps, n_total - first) : n_total - first;
     const size_t n = (size_t)B * h->J * h->T;
-    NoiseKey nk;
-    nk.k0 = (unsigned)(a->seed & 0xffffffffu); nk.k1 = (unsigned)(a->seed >> 32);
-    nk.s0 = (unsigned)(a->stream_id & 0xffffffffu); nk.s1 = (unsigned)(a->stream_id >> 32);
-
-    // x_T (gaussian_diffusion.py:701-713)
-    const float *noise_d = nullptr, *init_d = nullptr;
-    CHK(to_dev(h, a->init_noise, h->io_tmp, n, &noise_d));
-    CHK(to_dev(h, a->init_image, h->io_tmp2, n, &init_d));
-    const int do_q = (first == 0 && (a->skip_timesteps > 0 || a->init_image)) ? 1 : 0;      // (a resumed chain starts from x_t as handed over)
-    const int i0 = n_run - 1;
-    KernelSel ksel;
-    CHK(select_kernels(h, rows, m.lanes, ksel));      // (first: the layout of the state shadow belongs to the kernel set)
-    CHK(ensure_set_buffers(h, ksel));
-    // what the loop reads from device memory instead of its arguments: the call's key, the draw index of step 0 and, with per-element noise
-    // streams, the table (NoiseTable) -- uploaded here because the start kernels read the table too
-    const int keyed = nt.B > 0 ? 1 : 0;
-    {
-        unsigned* dyn = h->dyn_host.data();
-        dyn[0] = nk.k0; dyn[1] = nk.k1; dyn[2] = nk.s0; dyn[3] = nk.s1; dyn[4] = a->draw_base + 1u;
-        const size_t off0 = 8 + 4 * (size_t)h->Bmax, start0 = 8 + 6 * (size_t)h->Bmax;
-        for (int b = 0; b < nt.B; ++b) {
-            const unsigned* k = nt.keys + 4 * (a->const_noise ? 0 : b);
-            dyn[8 + 4 * b] = nt.seeds ? k[0] : nk.k0; dyn[9 + 4 * b] = nt.seeds ? k[1] : nk.k1;
-            dyn[10 + 4 * b] = k[2]; dyn[11 + 4 * b] = k[3];
-            dyn[off0 + 2 * b] = nt.offs ? nt.offs[b] : 0u;
-            dyn[off0 + 2 * b + 1] = nt.holds ? (unsigned)nt.holds[b] : 0u;
-            dyn[start0 + b] = nt.starts ? nt.starts[b] : 0u;
-        }
-        HIPCHK(hipMemcpyAsync(h->dyn, dyn, (keyed ? start0 + (size_t)nt.B : 5) * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
-    }
-    const unsigned* keys_d = keyed ? h->dyn + 8 : nullptr;
-    const unsigned* offs_d = keyed ? h->dyn + 8 + 6 * (size_t)h->Bmax : nullptr;      // (the start kernels': GemmArgs::draw_off is the pair table)
-    if (m.start == RunMode::CLIPQ_X_IN)      // (a round of the clip queue on a lane that runs a job with an init motion, or of a call with per-clip skips)
-        CHK(launch_clip_x_in_q(h, nk, keys_d, offs_d, a->draw_base, B, ksel));
-    else if (m.start == RunMode::CLIP_X_IN)  // (dsg_sample_clip on a handle with a clip-level init: it has refused init_noise / init_image / first_step)
-        CHK(launch_clip_x_in(h, m.c, m.n_out, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0], nk, keys_d, offs_d, a->draw_base, B, ksel));
-    else
-        CHK(launch_x_in(h, noise_d, init_d, do_q, (float)h->sched.sqrt_ac[i0], (float)h->sched.sqrt_1mac[i0],
-                        noise_d ? 0 : 1, nk, keys_d, offs_d, a->draw_base, B, ksel));
-    // replayed per-step noise
-    const float* ext = nullptr;
-    if (a->step_noise) {
-        const size_t ne = (size_t)n_total * n;
-        if (is_device_ptr(a->step_noise)) ext = a->step_noise;
-        else {
-            if (ne > h->ext_noise_cap) { CHK(dalloc(h, &h->ext_noise, ne, false)); h->ext_noise_cap = ne; }
-            HIPCHK(hipMemcpyAsync(h->ext_noise, a->step_noise, ne * sizeof(float), hipMemcpyHostToDevice, h->stream));
-            ext = h->ext_noise;
-        }
-    }
+    StartIn s;
+    CHK(to_dev(h, a->init_noise, h->io_tmp, n, &s.noise));
+    CHK(to_dev(h, a->init_image, h->io_tmp2, n, &s.init));
+    StepCtx& c = job.c;
+    CHK(select_kernels(h, rows, m.lanes, c.ks));      // (first: the layout of the state shadow belongs to the kernel set)
+    CHK(ensure_set_buffers(h, c.ks));
+    CHK(upload_noise_block(h, a, m.noise, s));
+    CHK(start_chain(h, a, m, job, s));
+    CHK(replayed_noise(h, a->step_noise, n, &c.ext_noise));
     hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(64), 0, h->stream, h->ctl, h->st_tmodel, first);
     HIPCHK(hipGetLastError());
     HP_LAP(1);
     HIPCHK(hipStreamSynchronize(h->stream));      // (the upload of `dyn` above has landed)
     HP_LAP(2);
-    StepCtx& c = job.c;
-    c.B = rows; c.out_mode = a->mode == DSG_MODE_DDPM ? OUT_DDPM : OUT_DDIM; c.use_ctr = true; c.ext_noise = ext;
-    c.const_noise = a->const_noise; c.keyed = keyed; c.clip_x0 = a->clip_denoised ? 1 : 0;
-    c.no_noise = (a->mode == DSG_MODE_DDIM && a->eta == 0.f && !ext) ? 1 : 0;
+    c.B = rows; c.out_mode = a->mode == DSG_MODE_DDPM ? OUT_DDPM : OUT_DDIM; c.use_ctr = true;
+    c.const_noise = a->const_noise; c.keyed = m.noise.B > 0 ? 1 : 0; c.clip_x0 = a->clip_denoised ? 1 : 0;
+    c.no_noise = (a->mode == DSG_MODE_DDIM && a->eta == 0.f && !c.ext_noise) ? 1 : 0;
     c.inpaint = m.inpaint > 0 ? 1 : 0;     // (the AQL argument blocks are recorded anew below for every call: on / off needs no invalidation)
-    c.ks = ksel;
-    n_run = n_iter;                          // from here on: the steps of this call (the tables keep the whole chain: h->n_run)
-    job.n_run = n_iter; job.B = B; job.done = 0; job.first = first;
     job.dumping = a->n_dump > 0 && a->dump_steps && a->dump_out;
     // steps_per_graph: 0 = default = no hipGraph.  Measured on MI355X / ROCm 7.2: hipGraph replay of the step is slower than
     // stream-ordered HIP launches (180 vs 157 us; 151-163 us with DEBUG_CLR_GRAPH_PACKET_CAPTURE=0), and both lose to the
     // hand-written AQL submission (139 us) -- graphs stay opt-in (steps_per_graph > 0).
     job.spg = h->cfg.steps_per_graph == 0 ? -1 : h->cfg.steps_per_graph;
-    if (job.dumping || ext) job.spg = -1;            // rare paths run eagerly (ext pointer / dump points are per call)
-    h->aql_timing = false;
-    h->last_path = 0; h->last_nofence = false;
-    job.aql = false;
+    if (job.dumping || c.ext_noise) job.spg = -1;           // rare paths run eagerly (ext pointer / dump points are per call)
 #ifndef DSG_EMU
-    // The step loop as hand-written AQL packets (dsg_aql.h): one recording pass of run_step (no launch), argument
-    // blocks to device memory, then n_run x the same packets on the handle's own HSA queue.  Any failure before the
-    // first packet falls back to the HIP launches; a failure after submission is an error.
-    const bool graph_wanted = job.spg > 0 && n_run >= job.spg;
-    if (h->aql_mode == 1 && !job.dumping && !graph_wanted && n_run > 0) {
-        bool planned = dsg_aql::init(h->aql, h->cfg.device, (const void*)&dsg_version);
-        bool nofence = false;
-        if (planned && h->uc_mode == 1) nofence = uc_selfcheck(h);
-        HP_LAP(3);
-        if (planned) {
-            dsg_aql::begin(h->aql);
-            const int rc = run_step_p(h, c);
-            HP_LAP(4);
-            planned = dsg_aql::finish(h->aql) && rc == 0;
-            HP_LAP(5);
-            h->aql.recording = false;
-            h->aql.nofence = nofence;            // fence-free packets (see uc_mode; 2: uncached buffers behind the usual fences)
-        }
-        if (!planned) {
-            if (!h->aql_warned) { fprintf(stderr, "libdsg_hip: AQL path unavailable (%s); using HIP launches\n", h->aql.err.c_str()); h->aql_warned = true; }
-            h->aql_mode = 0;
-        } else {
-            HIPCHK(hipStreamSynchronize(h->stream));         // state / control block / conditioning are in place
-            job.aql = true;
-        }
-    }
+    CHK(plan_aql(h, job));
 #endif
     HIPCHK(hipEventRecord(h->ev_t0, h->stream));
     HP_LAP(6);
@@ -2669,8 +2677,7 @@ static int sample_run_hip(dsg_handle* h, const dsg_sample_args* a, SampleJob& jo
         }
         if (ok) {
             while (n_run - job.done >= spg) { HIPCHK(hipGraphLaunch(it->second.exec, h->stream)); job.done += spg; }
-            h->last_path = 2;
-            h->last_kset = c.ks.set;
+            job.path = 2;      // (also when trailing steps follow eagerly below)
         }
     }
     int di = 0;
@@ -2699,8 +2706,7 @@ static int run_lanes(dsg_handle** hs, int n, const dsg_sample_args* args, Sample
         if (job.aql) {
             if (!dsg_aql::run(h->aql, job.n_run, 60.0 + 0.01 * job.n_run)) return fail(DSG_E_RUNTIME, "AQL run: " + h->aql.err);
             job.done = job.n_run;
-            h->aql_timing = true; h->aql_ms = h->aql.last_ms;
-            h->last_path = 1; h->last_nofence = h->aql.nofence;
+            job.path = 1; job.nofence = h->aql.nofence; job.clock_ms = h->aql.run_ms;
         }
 #endif
         return sample_run_hip(h, &args[0], job);
@@ -2717,7 +2723,7 @@ static int run_lanes(dsg_handle** hs, int n, const dsg_sample_args* args, Sample
         if (!dsg_aql::run_multi(ctxs.data(), steps.data(), n, tmax, err)) return fail(DSG_E_RUNTIME, "AQL run: " + err);
         for (int i = 0; i < n; ++i) {
             jobs[i].done = jobs[i].n_run;
-            hs[i]->aql_timing = true; hs[i]->aql_ms = hs[i]->aql.last_ms; hs[i]->last_path = 1; hs[i]->last_nofence = hs[i]->aql.nofence;
+            jobs[i].path = 1; jobs[i].nofence = hs[i]->aql.nofence; jobs[i].clock_ms = hs[i]->aql.run_ms;
         }
     }
 #endif
@@ -2742,8 +2748,7 @@ static int sample_finish(dsg_handle* h, float* out, void* stream, SampleJob& job
     const size_t n = (size_t)job.B * h->J * h->T;
     HP_LAP(7);                               // (the step loop itself)
     HIPCHK(hipEventRecord(h->ev_t1, h->stream));
-    h->last_steps = job.n_run; h->timing_valid = true; h->clip_timing = false;
-    h->last_kset = job.c.ks.set;
+    commit_report(h, job, job.n_run, job.clock_ms);      // (not timed by the AQL clock: the two events, resolved when asked)
     CHK(launch_x_out(h, h->fwd_out, job.B));
     CHK(from_dev(h, out, h->fwd_out, n));
     CHK(order_before(h, stream));
@@ -2809,17 +2814,15 @@ static int clip_tails_ready(dsg_handle* h) {
         if (!h->clip_tail[k]) CHK(dalloc(h, &h->clip_tail[k], (size_t)h->Bmax * h->J * h->S));
     return 0;
 }
-// The step loop of a window (of a queue's round) has been issued on lane h: its time goes into clip_ms, what dsg_last_sample_ms reports for
-// the call -- the AQL run's host clock, else the events around the loop, waited for here.  The hand-off follows
-static int clip_window_timed(dsg_handle* h) {
+// The step loop of a window (of a queue's round) has been issued on lane h: its time -- the AQL run's host clock, else the events around the
+// loop, waited for here -- goes onto `sum`, the caller's, which is what dsg_last_sample_ms reports for the call.  The hand-off follows
+static int clip_window_timed(dsg_handle* h, const SampleJob& job, double& sum) {
     HIPCHK(hipEventRecord(h->ev_t1, h->stream));
-    if (h->aql_timing) h->clip_ms += h->aql_ms;
-    else {
-        float ms = 0.f;
-        HIPCHK(hipEventSynchronize(h->ev_t1));
-        HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
-        h->clip_ms += ms;
-    }
+    if (job.clock_ms >= 0.0) { sum += job.clock_ms; return 0; }
+    float ms = 0.f;
+    HIPCHK(hipEventSynchronize(h->ev_t1));
+    HIPCHK(hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1));
+    sum += ms;
     return 0;
 }
 
@@ -2879,9 +2882,9 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
         CHK(order_after(h, stream));
         if (seed0s && seed0s[i]) CHK(upload(h, h->c_seed, seed0s[i], n_tail * sizeof(float)));
         else HIPCHK(hipMemsetAsync(h->c_seed, 0, n_tail * sizeof(float), h->stream));
-        h->clip_ms = 0.0;
     }
     std::vector<SampleJob> jobs(n);
+    std::vector<double> ms(n, 0.0);      // per lane: the sum over its windows
     std::vector<dsg_sample_args> wargs(args, args + n);
     // Every window runs as dsg_sample_multi would run it on the lane's user state (the noise streams; inpB == 0, checked above), but for:
     // Lanes with a clip-level constraint: window c's slice goes into inp32 / inp_mask where the window's conditioning is set -- on the handle's
@@ -2907,14 +2910,13 @@ static int sample_clip(dsg_handle** hs, int n, const float* const* styles, const
         for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], modes[i], B, stream, jobs[i]));
         CHK(run_lanes(hs, n, wargs.data(), jobs.data()));
         for (int i = 0; i < n; ++i) {
-            CHK(clip_window_timed(hs[i]));
+            CHK(clip_window_timed(hs[i], jobs[i], ms[i]));
             CHK(launch_handoff(hs[i], clip[i], B, n_out, c, K, root_shift, keep_last_tail));
         }
     }
     for (int i = 0; i < n; ++i) {
         dsg_handle* h = hs[i];
-        h->last_steps = K * n_run; h->timing_valid = true; h->clip_timing = true;
-        h->last_kset = jobs[i].c.ks.set;
+        commit_report(h, jobs[i], K * n_run, ms[i]);
         if (clip[i] != outs[i]) CHK(from_dev(h, outs[i], clip[i], n_clip));
         CHK(order_before(h, stream));
     }
@@ -3114,12 +3116,12 @@ struct QueueRound {
     std::vector<Draws> draws;
     std::vector<RunMode> modes;
     bool seed_last_written = false;     // variant 5: some round has put a job's snippet into c_seed_last
-    int64_t steps_run = 0;              // the step-loop length summed over the rounds since the caller last reset it
+    int64_t steps_run = 0; std::vector<double> ms;      // since begin(): the step-loop length summed over the rounds, and per lane the time of its loops
     std::vector<const SlotWork*> lane;
 
     QueueRound(dsg_handle** hs_, int n, int B_, const uint8_t* mask_, int guided_, const dsg_sample_args& a, int root_shift_, int keep_last_tail_)
         : hs(hs_, hs_ + n), B(B_), guided(guided_ ? 1 : 0), root_shift(root_shift_ ? 1 : 0), keep_last_tail(keep_last_tail_ ? 1 : 0), mask(mask_),
-          args(a), wargs(n, a), sjobs(n), lane_init(n, 0), draws(n), modes(n), lane(B_) {
+          args(a), wargs(n, a), sjobs(n), lane_init(n, 0), draws(n), modes(n), ms(n, 0.0), lane(B_) {
         for (int i = 0; i < n; ++i) {
             dsg_handle::Queue& q = hs[i]->cq;
             q.slots_host.resize(B); q.edits_host.resize(B);
@@ -3135,8 +3137,8 @@ struct QueueRound {
     }
     // in front of the rounds of one call: they follow whatever `stream` still does to the tensors they read
     int begin(void* stream) {
-        steps_run = 0;
-        for (dsg_handle* h : hs) { h->clip_ms = 0.0; CHK(order_after(h, stream)); }
+        steps_run = 0; ms.assign(hs.size(), 0.0);
+        for (dsg_handle* h : hs) CHK(order_after(h, stream));
         return 0;
     }
     int run(const SlotWork* const* slots, void* stream) {      // slots: [B][lanes] (global slot s: lane s % n, position s / n)
@@ -3189,7 +3191,7 @@ struct QueueRound {
         for (int i = 0; i < n; ++i) CHK(sample_prepare(hs[i], &wargs[i], modes[i], B, stream, sjobs[i]));
         CHK(run_lanes(hs.data(), n, wargs.data(), sjobs.data()));
         for (int i = 0; i < n; ++i) {
-            CHK(clip_window_timed(hs[i]));
+            CHK(clip_window_timed(hs[i], sjobs[i], ms[i]));
             CHK(launch_handoff_q(hs[i], B, root_shift, keep_last_tail));
         }
         return 0;
@@ -3197,9 +3199,8 @@ struct QueueRound {
     // behind the rounds of one call (ran: there was one): what dsg_last_sample_ms and its kin report, and `stream` follows the lanes
     int end(bool ran, void* stream) {
         for (size_t i = 0; i < hs.size(); ++i) {
-            dsg_handle* h = hs[i];
-            if (ran) { h->last_steps = (int)steps_run; h->timing_valid = true; h->clip_timing = true; h->last_kset = sjobs[i].c.ks.set; }
-            CHK(order_before(h, stream));
+            if (ran) commit_report(hs[i], sjobs[i], (int)steps_run, ms[i]);
+            CHK(order_before(hs[i], stream));
         }
         return 0;
     }
@@ -3784,27 +3785,25 @@ extern "C" int dsg_sync(dsg_handle* h) {
 }
 extern "C" int dsg_last_sample_ms(dsg_handle* h, float* ms, int* n_steps) {
     if (!h || !ms) return fail(DSG_E_INVALID, "null argument");
-    if (!h->timing_valid) return fail(DSG_E_STATE, "no dsg_sample has run");
+    if (!h->last.sampled) return fail(DSG_E_STATE, "no dsg_sample has run");
     HIPCHK(hipEventSynchronize(h->ev_t1));
-    if (h->clip_timing) *ms = (float)h->clip_ms;    // dsg_sample_clip: the sum over its windows
-    else if (h->aql_timing) *ms = (float)h->aql_ms;      // AQL path: host clock from the first doorbell to the completion signal
+    if (h->last.host_ms >= 0.0) *ms = (float)h->last.host_ms;      // the AQL clock, or the sum over a clip's windows / a queue's rounds
     else HIPCHK(hipEventElapsedTime(ms, h->ev_t0, h->ev_t1));
-    if (n_steps) *n_steps = h->last_steps;
+    if (n_steps) *n_steps = h->last.steps;
     return 0;
 }
 // how the step loop of the last dsg_sample was submitted: 0 = HIP launches, 1 = hand-written AQL packets, 2 = hipGraph replay
 extern "C" int dsg_last_sample_path(dsg_handle* h, int* path) {
     if (!h || !path) return fail(DSG_E_INVALID, "null argument");
-    if (!h->timing_valid) return fail(DSG_E_STATE, "no dsg_sample has run");
-    *path = h->last_path;
+    if (!h->last.sampled) return fail(DSG_E_STATE, "no dsg_sample has run");
+    *path = h->last.path;
     return 0;
 }
-
 // 1 when the packets of the last dsg_sample's loop carried no acquire / release fences (AQL paths only)
 extern "C" int dsg_last_sample_fence_free(dsg_handle* h, int* fence_free) {
     if (!h || !fence_free) return fail(DSG_E_INVALID, "null argument");
-    if (!h->timing_valid) return fail(DSG_E_STATE, "no dsg_sample has run");
-    *fence_free = h->last_nofence ? 1 : 0;
+    if (!h->last.sampled) return fail(DSG_E_STATE, "no dsg_sample has run");
+    *fence_free = h->last.nofence ? 1 : 0;
     return 0;
 }
 

@@ -548,17 +548,20 @@ struct GemmArgs {
                             // advances the B side); null outside the sampling loop
     StepTables st;          // tables the block-0 bookkeeping reads (n_tab entries)
     int n_tab;
-    const unsigned* dyn;    // device: {seed lo, seed hi, stream lo, stream hi, draw index of step 0, -, -, -} + the key table of keyed noise
-                            // (words 8 + 4 b .. 8 + 4 b + 3: noise_key_of) -- kept out of the kernel arguments so a captured graph is
-                            // reusable across windows / clips
+    // The noise block: what the loop reads from device memory instead of its arguments, so that a captured graph is reusable across windows / clips.  32-bit
+    // words, for a handle of mb = max_batch elements (the tables do not move with a call's batch).  An unkeyed call writes words 0 .. 4; a keyed one (per-element
+    // streams: dsg_set_noise_streams, a clip queue's round; the host's NoiseTable) also B entries of each table.  Element b then draws with ITS key at index
+    // dyn[DYN_DRAW] + step + offset[b] (wraps), and for loop indices step < hold[b] the epilogue leaves it alone: no draw, no write of its state, shadow or twin.
+    enum { DYN_KEY = 0, DYN_DRAW = 4, DYN_KEYS = 8 };      // the call's key {seed lo, seed hi, stream lo, stream hi}; the draw index of step 0; the key table (noise_key_of)
+    static constexpr size_t dyn_pairs(size_t mb) { return DYN_KEYS + 4 * mb; }        // {offset, hold} per element (DrawOff), 8-byte aligned: draw_off
+    static constexpr size_t dyn_starts(size_t mb) { return dyn_pairs(mb) + 2 * mb; }  // the start kernels' draw offset per element (XInArgs::offs)
+    static constexpr size_t dyn_words(size_t mb) { return dyn_starts(mb) + mb; }
+    const unsigned* dyn;
     const float* ext_noise; // optional [n_steps][B][J][T] replayed noise, else null
     int B;
     int const_noise;
-    int keyed;              // EPI_OUT: per-element noise streams (dsg_set_noise_streams): the key of element b from dyn + 8, batch term of the counter 0
-    const unsigned* draw_off;   // keyed: uint32 pairs {offset, hold} [B] behind the key table (dyn + 8 + 4 max_batch: 8-byte aligned, it does not move with the
-                            // batch).  Element b's draw index is dyn[4] + step + offset[b] (wraps), and for loop indices step < hold[b] the epilogue leaves the
-                            // element alone: no draw, no write of its state, shadow or twin.  {0, 0} everywhere but in the clip queue, whose slots stand
-                            // on different windows (dsg_sample_clip_queue) and may start later on the round's timestep axis (dsg_sample_clip_queue_steps)
+    int keyed;              // EPI_OUT: per-element noise streams (dsg_set_noise_streams): the key of element b from the key table, batch term of the counter 0
+    const unsigned* draw_off;   // = dyn + dyn_pairs(mb)
     int ws_G;               // dsg_stream.h: row-block groups of the persistent grid (multiple of 8)
     int a_frag;             // PRO_DIRECT: A is stored fragment-major ([row tile][k-block][64 lanes][16 B], qk_off) -- hidden, attention rows
     int out_frag;           // EPI_GELU: the output goes out fragment-major (it is the next GEMM's A operand)
@@ -749,8 +752,7 @@ __device__ __forceinline__ void ln_rows(const GemmArgs& g, int m0, int tid, char
 // Epilogue operands of one 16 x 16 output tile (bias, residual rows, x_t, noise): requested early, they do not depend on
 // the main loop
 struct TileOps { f32x4 pb, pr, pz; float pbs; bool ovalid; };
-// one entry of GemmArgs::draw_off: read as ONE 8-byte word, workgroup-uniform
-struct __attribute__((aligned(8))) DrawOff { unsigned off; int hold; };
+struct __attribute__((aligned(8))) DrawOff { unsigned off; int hold; };      // one entry of GemmArgs::draw_off: read as ONE 8-byte word, workgroup-uniform
 // x_t of (row m, features j0 .. j0 + 3) for the sampler epilogue: unconditional load from a clamped (always valid) row
 template <class P>
 __device__ __forceinline__ f32x4 out_xt_load(const GemmArgs& g, int m, int j0) {
@@ -788,30 +790,28 @@ __device__ __forceinline__ void gemm_prefetch_tile(const GemmArgs& g, int m0, in
                         o.pz[e] = (j0 + e < g.J)
                                        ? g.ext_noise[(((size_t)step * g.B + bn) * g.J + j0 + e) * g.T + f] : 0.f;
                 } else {
-                    // The key: the call's, dyn[0 .. 3], or with per-element streams (keyed: workgroup-uniform) the element's, from the table behind it
-                    // (noise_key_of), with the batch term of the counter 0.  Requested here with pb / pr, in front of the main loop.  Keyed, a pass
-                    // of the loop serves the lanes of ONE batch element of the wave (1 or 2 elements per 16-row tile); unkeyed there is one pass.
-                    // This form costs no kernel a spill or a wave of occupancy; selecting the key's address per lane in a straight line did
-                    // (k_ws<EPI_OUT, 16, ONE>, at its bound of 128 registers: 8 bytes of scratch).  The element's draw offset and its hold
-                    // (GemmArgs::draw_off) are read at the same point, one workgroup-uniform 8-byte read beside the key.  A held element (a slot of
-                    // dsg_sample_clip_queue_steps whose own chain starts at a later loop index of the round) gives up `ovalid` here: the epilogue
-                    // then writes nothing of it -- state, shadow, twin -- and no noise is drawn for it.  Keyed calls come through here with
-                    // no_noise too (DDIM, eta = 0), for the hold alone
+                    // The key: the call's, or with per-element streams (keyed: workgroup-uniform) the element's, from the table behind it (GemmArgs::dyn),
+                    // with the batch term of the counter 0.  Requested here with pb / pr, in front of the main loop.  Keyed, a pass of the loop serves
+                    // the lanes of ONE batch element of the wave (1 or 2 elements per 16-row tile); unkeyed there is one pass.  This form costs no kernel
+                    // a spill or a wave of occupancy; selecting the key's address per lane in a straight line did (k_ws<EPI_OUT, 16, ONE>, at its bound
+                    // of 128 registers: 8 bytes of scratch).  The element's {offset, hold} is one workgroup-uniform 8-byte read beside the key.  A held
+                    // element (a slot of dsg_sample_clip_queue_steps whose own chain starts at a later loop index of the round) gives up `ovalid` here,
+                    // which is all the epilogue needs to leave it alone.  Keyed calls come through here with no_noise too (DDIM, eta = 0), for the hold alone
                     bool todo = true;
                     do {
                         const int bu = g.keyed ? __builtin_amdgcn_readfirstlane(bn) : 0;
                         if (!g.keyed || bn == bu) {
-                            NoiseKey nk = {g.dyn[0], g.dyn[1], g.dyn[2], g.dyn[3]};
+                            NoiseKey nk = {g.dyn[GemmArgs::DYN_KEY], g.dyn[GemmArgs::DYN_KEY + 1], g.dyn[GemmArgs::DYN_KEY + 2], g.dyn[GemmArgs::DYN_KEY + 3]};
                             unsigned off = 0u;
                             bool held = false;
                             if (g.keyed) {
-                                nk = noise_key_of(g.dyn + 8, bu);
+                                nk = noise_key_of(g.dyn + GemmArgs::DYN_KEYS, bu);
                                 const DrawOff oh = ((const DrawOff*)g.draw_off)[bu];
                                 off = oh.off; held = step < oh.hold;
                             }
                             if (held) o.ovalid = false;
                             else if (!g.no_noise)
-                                o.pz = philox_normal4((imul24((int)imul24(bn, g.keyed ? 0 : g.T) + f, g.Jq) + (unsigned)j0) >> 2, g.dyn[4] + (unsigned)step + off, nk);
+                                o.pz = philox_normal4((imul24((int)imul24(bn, g.keyed ? 0 : g.T) + f, g.Jq) + (unsigned)j0) >> 2, g.dyn[GemmArgs::DYN_DRAW] + (unsigned)step + off, nk);
                             todo = false;
                         }
                     } while (todo);
