@@ -1190,7 +1190,7 @@ struct FfnArgs {
     float* X1;              // OP on 64-row blocks (no LDS left to park them): the fp32 LayerNorm1 rows, written by the prologue and read back after phase 1
 };
 
-template <class P, int DT, int FT, int RT, int NW, int LA = 2, bool LATE_R = false, bool OP = false, int RING = 0, bool WO_RING = false>      // D = 64 DT, ff = 64 FT, RT row tiles per workgroup, NW waves, LA tiles / 2 LA k-blocks of look-ahead
+template <class P, int DT, int FT, int RT, int NW, int LA = 2, bool LATE_R = false, bool OP = false, int RING = 0, bool WO_RING = false, bool A_LDS = false>      // D = 64 DT, ff = 64 FT, RT row tiles per workgroup, NW waves, LA tiles / 2 LA k-blocks of look-ahead
 __global__ __launch_bounds__(64 * NW) void k_ffn(const FfnArgs g) {      // RING > 0: the weights of both phases as ONE stream through a rolling ring of RING fragments (see below)
     DSG_TL_SCOPE();
     typedef typename P::elem elem;
@@ -1202,6 +1202,10 @@ __global__ __launch_bounds__(64 * NW) void k_ffn(const FfnArgs g) {      // RING
     constexpr int NT = 64 * NW;
     static_assert(FW >= LA && FW % LA == 0 && DW >= 1 && KF % KC == 0 && (FF / 16) % NW == 0 && (D / 16) % NW == 0, "shape");
     static_assert(!P::W2 || (OP && RING > 0 && RT < 4), "bf16w2: the ring forms with the prologue");
+    // A_LDS (bf16w2 at the DSG+ widths): the operand fragments of out_proj (attention rows) and linear1 (LayerNorm1 rows) are read from their LDS image
+    // per k-block instead of waiting in registers -- as hi + lo pairs they are KD x 8 = 96 / 128 registers per row tile next to the ring.  Same MFMAs on the
+    // same operands in the same order.
+    static_assert(!A_LDS || (OP && RING > 0 && WO_RING && RT == 1), "operands from LDS: the 16-row ring form with W_o in the ring");
     constexpr int HID_LO = RT * 16 * HP;             // bf16w2: `hidden` as a hi + lo pair of images (P::store4_a / P::aload)
     __shared__ __attribute__((aligned(16))) char hid[P::AF * RT * 16 * HP];
     __shared__ float red[RT][2][NW][16];
@@ -1223,7 +1227,7 @@ __global__ __launch_bounds__(64 * NW) void k_ffn(const FfnArgs g) {      // RING
     const int m0 = mb * 16 * RT, mt_last = g.MT - 1;
     // ---- loads that do not depend on phase 1: A fragments, first W1 tiles, residual rows, the per-column vectors
     constexpr int RH = (OP && RT >= 4) ? 2 : RT;     // OP on 64-row blocks: the prologue takes the row tiles two at a time (register budget)
-    typename P::afrag af[RT][KD];
+    typename P::afrag af[A_LDS ? 1 : RT][A_LDS ? 1 : KD];
     // OP: the RH x KD attention-row fragments of a half are fetched ONCE per workgroup -- NFW of them per wave -- and handed round through LDS (the tail of
     // `hid`, free until phase 1): every wave needs all of them, and eight waves loading the same 16 KB from uncached memory were 23 MB of memory-side reads
     // per launch at 64 clips for 2.9 MB of rows
@@ -1256,10 +1260,12 @@ __global__ __launch_bounds__(64 * NW) void k_ffn(const FfnArgs g) {      // RING
             else stg[(wave * NFW + i) * 64 + lane] = afw[i];
         }
         DSG_LDS_BARRIER();
+        if constexpr (!A_LDS) {
 #pragma unroll
-        for (int rt = rt0; rt < rt0 + RH; ++rt)
+            for (int rt = rt0; rt < rt0 + RH; ++rt)
 #pragma unroll
-            for (int kb = 0; kb < KD; ++kb) af[rt][kb] = P::aload((const char*)&stg[((rt - rt0) * KD + kb) * P::AF * 64 + lane], 1024);
+                for (int kb = 0; kb < KD; ++kb) af[rt][kb] = P::aload((const char*)&stg[((rt - rt0) * KD + kb) * P::AF * 64 + lane], 1024);
+        }
     };
     load_a(0);
     const f32x4* w1 = (const f32x4*)g.W1 + lane;
@@ -1355,7 +1361,15 @@ __global__ __launch_bounds__(64 * NW) void k_ffn(const FfnArgs g) {      // RING
             share_a(r0);
 #pragma unroll
             for (int kb = 0; kb < KD; ++kb) {
-                if constexpr (WO_RING) {      // (RH == RT <= 2: a slot is consumed by the row tiles side by side; what follows W_o in the stream is W1)
+                if constexpr (A_LDS) {        // (one row tile: the k-block's attention-row pair straight from the stage)
+                    const typename P::afrag ak = P::aload((const char*)&stg[kb * P::AF * 64 + lane], 1024);
+#pragma unroll
+                    for (int t = 0; t < DW; ++t) {
+                        const int i = kb * DW + t;
+                        acc1[0][t] = P::mma_w(ring[i % NRING], ak, acc1[0][t]);
+                        ring[i % NRING] = ring_load(i + RING);
+                    }
+                } else if constexpr (WO_RING) {      // (RH == RT <= 2: a slot is consumed by the row tiles side by side; what follows W_o in the stream is W1)
 #pragma unroll
                     for (int t = 0; t < DW; ++t) {
                         const int i = kb * DW + t;
@@ -1446,10 +1460,12 @@ __global__ __launch_bounds__(64 * NW) void k_ffn(const FfnArgs g) {      // RING
             DSG_LOADS_ISSUED();
         }
         DSG_LDS_BARRIER();                                    // (also: red is free for LayerNorm2)
+        if constexpr (!A_LDS) {
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
+            for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-            for (int kb = 0; kb < KD; ++kb) af[rt][kb] = P::aload(xa + (rt * 16 + lr) * XP + (kb * P::KB + P::E * lg) * ES, XA_LO);
+                for (int kb = 0; kb < KD; ++kb) af[rt][kb] = P::aload(xa + (rt * 16 + lr) * XP + (kb * P::KB + P::E * lg) * ES, XA_LO);
+        }
         if constexpr (BIG) DSG_LDS_BARRIER();                 // every wave holds its operand: phase 1 may overwrite the aliased rows
         DSG_TL_MARK(2);      // LayerNorm1 (three barriers) -> linear1's operand registers
     } else {
@@ -1475,8 +1491,12 @@ __global__ __launch_bounds__(64 * NW) void k_ffn(const FfnArgs g) {      // RING
 #pragma unroll
             for (int kb = 0; kb < KD; ++kb) {
                 const int i = N0 + j * KD + kb;
+                if constexpr (A_LDS) {
+                    c[0] = P::mma_w(ring[i % NRING], P::aload(xa + lr * XP + (kb * P::KB + P::E * lg) * ES, XA_LO), c[0]);
+                } else {
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) c[rt] = P::mma_w(ring[i % NRING], af[rt][kb], c[rt]);      // D[n 4lg+r][row lr]
+                    for (int rt = 0; rt < RT; ++rt) c[rt] = P::mma_w(ring[i % NRING], af[rt][kb], c[rt]);      // D[n 4lg+r][row lr]
+                }
                 if (i + RING < N0 + N1 + N2) ring[i % NRING] = ring_load(i + RING);
                 DSG_LOADS_ISSUED();
             }

@@ -1051,6 +1051,7 @@ enum class Form {
     ATTN_OP_FFN,    // QKV, k_attn_op, k_ffn                                            STREAM / ROWS under DSG_CLIP_ATTN=0
     CLIP_FFN,       // k_clip_attn, k_ffn<OP>                                           STREAM, ROWS (bf16, bf16w2) at C256 / C128
     CLIP_W_FFN,     // k_clip_attn_w, k_ffn<OP>                                         ROWS at C384 / C512
+    QKV_ATTN_FFN,   // QKV (on the hi + lo rows in X0a), k_attn, k_ffn<OP>              ROWS at C384 / C512 in bf16w2
 };
 static bool leaves_x0a(Form f) { return f >= Form::ATTN_OP_SPLIT; }
 struct KernelSel {
@@ -1109,6 +1110,12 @@ static bool rows_wide_ok(const dsg_handle* h) {
 // (not under fused guidance: its last layer runs the QKV GEMM + k_attn_op, which have no bf16w2 form)
 static bool rows_w2_ok(const dsg_handle* h) {
     return h->prec == DSG_PREC_BF16W2 && ((h->core == Core::C256 && h->ff == 1024) || (h->core == Core::C128 && h->ff == 128));
+}
+// bf16w2 at the DSG+ widths: the decomposition rows_wide_ok started from -- the direct QKV GEMM (k_gemm_qkv_pair: its rows are the hi + lo pair in X0a) + k_attn,
+// then k_ffn<OP> on one 16-row tile with W_o leading a 16-slot ring of two-register fragments and the operand fragments re-read from LDS (A_LDS): 3 + 3L
+// dispatches; 16 x 16 tile pose embedding and pose head.  Reachable by name only: resolve_auto_set and the uc_mode decision of dsg_create read rows_w2_ok, not this
+static bool rows_w2_wide_ok(const dsg_handle* h) {
+    return h->prec == DSG_PREC_BF16W2 && core_wide(h) && h->ff == 1024;
 }
 // the streamed pose embedding at the DSG+ pose widths (round 6: k_ws2<EPI_PARTIAL, 17 / 18, 2>, K over two workgroups) -- in the ROWS set
 // (a GEMM of K = Jp, N = latent_dim: it depends on those two widths alone, not on the attention core -- any head count / clip length)
@@ -1176,10 +1183,10 @@ static int resolve_auto_set(const dsg_handle* h, int B, int lanes) {
 static int check_set(const dsg_handle* h, int set) {
     if (set < DSG_KSET_LATENCY || set > DSG_KSET_ROWS) return fail(DSG_E_INVALID, "unknown kernel set");
     if (set == DSG_KSET_LATENCY && h->D > 512) return fail(DSG_E_NOT_IMPLEMENTED, "kernel set LATENCY: latent_dim > 512");
-    if ((set == DSG_KSET_STREAM || set == DSG_KSET_ROWS) && !stream_set_ok(h) && !(set == DSG_KSET_ROWS && (rows_w2_ok(h) || rows_wide_ok(h))))
-        return fail(DSG_E_NOT_IMPLEMENTED, "kernel sets STREAM / ROWS: bf16, latent_dim 128 / 256, 4 heads, ff 128 / 1024 (ROWS: bf16w2 there as well, and bf16 at the DSG+ widths -- latent_dim 384 / 512, ff 1024) only");
-    if (h->prec == DSG_PREC_BF16W2 && ((set > DSG_KSET_TILE && !(set == DSG_KSET_ROWS && rows_w2_ok(h))) || (set == DSG_KSET_LATENCY && h->D > 256)))
-        return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2: kernel sets LATENCY (latent_dim <= 256), TILE and ROWS (latent_dim 128 / 256) only");
+    if ((set == DSG_KSET_STREAM || set == DSG_KSET_ROWS) && !stream_set_ok(h) && !(set == DSG_KSET_ROWS && (rows_w2_ok(h) || rows_wide_ok(h) || rows_w2_wide_ok(h))))
+        return fail(DSG_E_NOT_IMPLEMENTED, "kernel sets STREAM / ROWS: bf16, latent_dim 128 / 256, 4 heads, ff 128 / 1024 (ROWS: bf16w2 there as well, and bf16 / bf16w2 at the DSG+ widths -- latent_dim 384 / 512, ff 1024) only");
+    if (h->prec == DSG_PREC_BF16W2 && ((set > DSG_KSET_TILE && !(set == DSG_KSET_ROWS && (rows_w2_ok(h) || rows_w2_wide_ok(h)))) || (set == DSG_KSET_LATENCY && h->D > 256)))
+        return fail(DSG_E_NOT_IMPLEMENTED, "precision bf16w2: kernel sets LATENCY (latent_dim <= 256), TILE and ROWS (latent_dim 128 / 256, ff 128 / 1024; 384 / 512, ff 1024; 4 heads) only");
     return 0;
 }
 // lanes: how many lanes share the GPU in this call (RunMode::lanes) -- the block shape of k_ffn, never the set or the arithmetic
@@ -1222,6 +1229,9 @@ static int select_kernels(const dsg_handle* h, int B, int lanes, KernelSel& k) {
             if (rows_wide_ok(h)) {      // (>= 3 lanes whose row tiles together exceed one round of the CUs: 32-row blocks, see layer_clip_w_ffn)
                 k.form = Form::CLIP_W_FFN;
                 k.ffn_rows = lanes >= 3 && lanes * cdiv(rows, 16) > 256 ? 32 : 16;
+            } else if (rows_w2_wide_ok(h)) {      // (16-row tiles at every lane count: the only W2 block shape)
+                k.form = Form::QKV_ATTN_FFN;
+                k.ffn_rows = 16;
             } else if (w2 || clip) {
                 k.form = Form::CLIP_FFN;
                 k.ffn_rows = 16;
@@ -1232,7 +1242,7 @@ static int select_kernels(const dsg_handle* h, int B, int lanes, KernelSel& k) {
     }
     k.xs_frag = k.blk() && h->prec == DSG_PREC_BF16 && (h->Jp == 1152 || h->Jp == 128 || xs_frag_wide(h, set));
     const bool clip_form = k.form == Form::CLIP_SPLIT || k.form == Form::CLIP_FFN || k.form == Form::CLIP_W_FFN;
-    k.x0a_frag = (k.stream() || clip_form) ? (w2 ? 2 : 1) : 0;
+    k.x0a_frag = (k.stream() || clip_form || k.form == Form::QKV_ATTN_FFN) ? (w2 ? 2 : 1) : 0;      // (QKV_ATTN_FFN: k_gemm_qkv_pair reads the pair)
     // split-K of the pose-embedding GEMM across workgroups: one split per 256 pose features for the 16 x 16 tile kernel; the block kernel splits K
     // over its 4 waves already, so 2 workgroup splits keep a wave's share at <= 8 k-blocks (one batch of loads) without fragmenting the work 5 ways.
     // (streamed embedding: K stays whole but at the DSG+ pose widths, see k_ws2; bf16w2: the 16 x 16 tiles)
@@ -1890,6 +1900,29 @@ static int layer_clip_w_ffn(dsg_handle* h, const LayerCtx& y) {
         default: return no_inst(h, "k_ffn<OP>");
     }
 }
+// ROWS at the DSG+ widths in bf16w2: the QKV GEMM on the hi + lo rows in X0a (layer 0: the embedding, after it LayerNorm2 of the previous layer), k_attn -- its rows
+// are the fragment-major pair k_ffn<OP> takes -- and k_ffn<OP> on one 16-row tile: W_o | W1 | W2 as two-register fragments through a 16-slot ring, the attention
+// rows / LayerNorm1 rows re-read from their LDS image per k-block (A_LDS; held they are 96 / 128 registers)
+template <class P>
+static int layer_qkv_attn_ffn(dsg_handle* h, const LayerCtx& y) {
+    GemmArgs g = gemm_qkv(h, y.z, y.M, y.ly, 1, nullptr);
+    g.KS = 1; g.kb_per_split = g.KBtot;
+    g.inv_ntok = fastdiv_inv(g.ntok); g.inv_hd = fastdiv_inv(g.hd);
+    if (g.NT % 4) return fail(DSG_E_INVALID, "gemm: NT not divisible by the workgroup tile");
+    const dim3 grid(xcd_grid_x(g.NT / 4), g.MT, 1);
+    switch (h->core) {      // (one batch of fragment loads per wave: 12 / 16 k-blocks)
+        case Core::C384: CHK((step_launch<&k_gemm_qkv_pair<P, 12>>(h, grid, dim3(256), g))); break;
+        case Core::C512: CHK((step_launch<&k_gemm_qkv_pair<P, 16>>(h, grid, dim3(256), g))); break;
+        default: return no_inst(h, "k_gemm_qkv_pair");
+    }
+    CHK(launch_attn<P>(h, y.z.B));
+    const FfnArgs f = ffn_args(h, y, true);
+    switch (h->core) {
+        case Core::C384: return step_launch<&k_ffn<P, 6, 16, 1, 8, 2, true, true, 16, true, true>>(h, dim3(y.MT), dim3(512), f);
+        case Core::C512: return step_launch<&k_ffn<P, 8, 16, 1, 8, 2, true, true, 16, true, true>>(h, dim3(y.MT), dim3(512), f);
+        default: return no_inst(h, "k_ffn<OP>");
+    }
+}
 // the forms that exist for precision P (select_kernels picks no other): fp32 has no k_clip_attn / k_ffn, bf16w2 no k_attn_op
 template <class P>
 static int run_layer(dsg_handle* h, Form f, const LayerCtx& y) {
@@ -1903,6 +1936,7 @@ static int run_layer(dsg_handle* h, Form f, const LayerCtx& y) {
         case Form::ATTN_OP_FFN: if constexpr (bf16) return layer_attn_op_ffn<P>(h, y); break;
         case Form::CLIP_FFN: if constexpr (bf16 || P::W2) return layer_clip_ffn<P>(h, y); break;
         case Form::CLIP_W_FFN: if constexpr (bf16) return layer_clip_w_ffn<P>(h, y); break;
+        case Form::QKV_ATTN_FFN: if constexpr (P::W2) return layer_qkv_attn_ffn<P>(h, y); break;
     }
     return fail(DSG_E_NOT_IMPLEMENTED, "layer form without an instantiation for this precision");
 }

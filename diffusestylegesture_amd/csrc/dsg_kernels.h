@@ -941,7 +941,7 @@ __device__ __forceinline__ void gemm_epilogue_tile(const GemmArgs& g, int m0, in
 // chunk's weight fragments are requested only after the current chunk's MFMAs, i.e. every further chunk is an exposed L2 round
 // trip (~1 us at one wave per SIMD).  8 covers K = 256 in bf16 (ZEGGS); the DSG+ widths (K = 384 / 512: 12 / 16 k-blocks) get
 // their own instantiations (round 4: the K = D GEMMs of BEAT / TWH ran two serial load phases each).
-template <class P, int PRO, int EPI, int WN, int WK, int TNW, bool LEAN = false, bool CFG = false, int CH = 8>
+template <class P, int PRO, int EPI, int WN, int WK, int TNW, bool LEAN = false, bool CFG = false, int CH = 8, bool APAIR = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
     static_assert(!CFG || (EPI == EPI_OUT && PRO == PRO_LN && !LEAN), "guidance lives in the pose-head epilogue");
     typedef typename P::elem elem;
@@ -953,7 +953,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
     // PBF16W2: the A operand is a hi + lo pair where a kernel of the step produced it for this GEMM -- the LayerNorm rows (LDS) and
     // the two direct GEMMs with the residual epilogue: out_proj (k_attn's rows) and linear2 (`hidden`), both fragment-major
     // (round 6: ... and the pose head of the ROWS set, which reads the LayerNorm2 rows k_ffn wrote as a hi + lo pair)
-    constexpr bool A2 = P::W2 && (IS_LN || (PRO == PRO_DIRECT && (EPI == EPI_RESID || EPI == EPI_OUT)));
+    // (APAIR: ... and the QKV projection of the ROWS set at the DSG+ widths, on the embedding's / k_ffn's LayerNorm2 rows in X0a -- k_gemm_qkv_pair)
+    static_assert(!APAIR || (P::W2 && PRO == PRO_DIRECT), "a hi + lo A operand from memory: bf16w2, direct");
+    constexpr bool A2 = P::W2 && (IS_LN || APAIR || (PRO == PRO_DIRECT && (EPI == EPI_RESID || EPI == EPI_OUT)));
     typedef typename std::conditional<A2, typename P::afrag, f32x4>::type AFrag;
     __shared__ __attribute__((aligned(16))) float lds_red[WK > 1 ? (WK - 1) * WN * TNW * 64 * 4 : 4];
 
@@ -1155,6 +1157,11 @@ __global__ __launch_bounds__(256) void k_gemm_cfg(const GemmArgs g) { DSG_TL_SCO
 
 template <class P, int PRO, int EPI, int WN, int WK, int TNW, int CH = 8>
 __global__ __launch_bounds__(256) void k_gemm(const GemmArgs g) { DSG_TL_SCOPE(); gemm_body<P, PRO, EPI, WN, WK, TNW, false, false, CH>(g); }
+
+// bf16w2, ROWS at the DSG+ widths: the QKV projection reads its rows from X0a as the fragment-major hi + lo pair k_loc (x0a_frag == 2) and k_ffn leave there --
+// three MFMAs per fragment pair like every other pair operand of the mode; Q / K / V come out as single bf16, as from every QKV kernel
+template <class P, int CH = 8>
+__global__ __launch_bounds__(256) void k_gemm_qkv_pair(const GemmArgs g) { DSG_TL_SCOPE(); gemm_body<P, PRO_DIRECT, EPI_QKV, 4, 1, 1, false, false, CH, true>(g); }
 
 // ---------------------------------------------------------------------------------------------------------
 // k_loc: per (batch, window, local head).  h = sum_s partial_s + Cframe + TE2[t]; rotary(pos = frame);

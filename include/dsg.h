@@ -74,7 +74,9 @@ enum {
 /* DSG_PREC_BF16W2 (ABI 320): bf16 activations, every weight as hi + lo bf16 (16 mantissa bits), two MFMAs per weight fragment --
  * the precision mode between bf16 and fp32 (the bf16 drift of a 1000-step chain is the weights' 8-bit mantissa).  Kernel sets
  * LATENCY and TILE (every batch size) and, at latent_dim 128 / 256 without fused guidance, ROWS (round 6: k_clip_attn + the feed-forward kernel on
- * two-register fragments; DSG_KSET_AUTO picks it from 800 token rows -- 16 clips in lock step 453 -> 331 us per step); BLOCK / STREAM are
+ * two-register fragments; DSG_KSET_AUTO picks it from 800 token rows -- 16 clips in lock step 453 -> 331 us per step) and, at the DSG+ widths
+ * (latent_dim 384 / 512, 4 heads, ff 1024) without fused guidance, ROWS by name only (the QKV GEMM + k_attn + the feed-forward kernel on one 16-row tile,
+ * 3 + 3L dispatches; DSG_KSET_AUTO stays on TILE there); BLOCK / STREAM are
  * DSG_E_NOT_IMPLEMENTED.  The reference computes in fp32
  * (main/train/training_loop.py:39: no autocast): DSG_PREC_FP32 is its arithmetic, the other two trade accuracy for speed. */
 enum { DSG_PREC_FP32 = 0, DSG_PREC_BF16 = 1, DSG_PREC_BF16W2 = 2 };
@@ -104,7 +106,9 @@ enum {
                                DSG_KSET_AUTO keeps guided calls on BLOCK, the set is reached by naming it): streamed pose embedding, then per layer the attention half per (clip, head) (k_clip_attn_w: the rows pass
                                through the LDS in chunks) + the same feed-forward kernel -- on 32-row blocks when >= 3 lanes together exceed one round of the
                                CUs -- = 3 + 2L dispatches; from
-                               9 BEAT / 13 TWH clips in one lane, 4 per lane and 16 in all with several lanes.  DSG_E_NOT_IMPLEMENTED elsewhere */
+                               9 BEAT / 13 TWH clips in one lane, 4 per lane and 16 in all with several lanes.  bf16w2 at the DSG+ widths (no fused
+                               guidance; by name only, DSG_KSET_AUTO keeps TILE): 16 x 16 tile pose embedding and pose head, per layer the QKV GEMM on the
+                               hi + lo rows + k_attn + the feed-forward kernel on 16-row tiles = 3 + 3L dispatches.  DSG_E_NOT_IMPLEMENTED elsewhere */
 };
 enum { DSG_MODE_DDPM = 0, DSG_MODE_DDIM = 1 };
 
