@@ -3093,6 +3093,7 @@ struct SlotWork {
     int c = 0;                  // the window the slot stands on
     int skip = 0, n_run = 0;    // the job's skip_timesteps and the steps of one of its windows (schedule length - skip)
     const float* win_audio = nullptr;      // a live job of a session: the audio of window c, where it is read (null: job.audio + c * n_audio)
+    const float* resume = nullptr;         // a session's job that takes a slot again on window c > 0: the parked [S][J] tail, for this round only
 };
 
 // The lane's device buffers for the rounds of a queue, on first use
@@ -3389,8 +3390,10 @@ extern "C" int dsg_sample_clip_queue(dsg_handle** hs, int n, const dsg_clip_job*
 // ---------------------------------------------------------------------------------------------------------
 // Queue session (dsg_queue_*): the clip queue as an object that lives between rounds.  Jobs are submitted while it runs and a job's rows
 // are in the caller's memory after the round that made them final.  What it adds to QueueRound:
-//   slots      first come, first served: at the start of a round the free slots, lowest first, take the pending jobs, oldest ticket first
-//              (dsg_queue_place is the same rule on the host); a job stands on the window behind those it has done;
+//   slots      by priority, then first come, first served: at the start of a round the free slots, lowest first, take the waiting jobs,
+//              highest priority and oldest ticket first, and a running job of a strictly lower priority is parked for one still waiting
+//              (queue_place_round; dsg_queue_place_prio is the same code on the host, dsg_queue_place the rule with equal priorities); a job
+//              stands on the window behind those it has done, in whichever slot it is;
 //   inputs     a job's host tensors are copied into session-owned device memory at submit; the round's per-slot conditioning is gathered on
 //              the device (cond_gathered: k_clipq_gather, one launch per lane);
 //   edits      every lane starts every round through the edit table (k_clipq_x_in): a job with its own skip or an init motion may arrive in
@@ -3416,12 +3419,21 @@ struct QJob {
     float scale0 = 1.f;
     std::vector<Win> wins;            // the windows given so far
     bool has_window() const { return !live || w.c < (int)wins.size(); }      // something to run in the next round
+    // Priorities, park and resume.  Between two rounds the only device state a running job owns is the [S][J] tail its last window handed
+    // off; everything else a round needs is rebuilt from the job.  A job that leaves its slot at a window boundary (state DSG_JOB_PARKED)
+    // keeps that tail in `park`, a staging block of its own, and takes any slot of any lane later (SlotWork::resume, GQ_RESUME)
+    int priority = 0, parks = 0;
+    bool held = false;                // dsg_queue_park: not placed, and parked when a round finds it in a slot, until dsg_queue_resume
+    float* park = nullptr;            // [S][J], written on the stream of lane park_lane; one of `blocks`
+    int park_lane = 0;
+    bool waiting() const { return (state == DSG_JOB_PENDING || state == DSG_JOB_PARKED) && !held && has_window(); }
 };
 struct dsg_queue {
     QueueRound rd;                    // the lanes, B, guided, args, root_shift, keep_last_tail; rd.mask: the session's device copy of mask_local
     std::vector<QJob> jobs;           // index = ticket
     std::vector<int64_t> slot_job;    // [n * B] -> ticket, -1: free
-    size_t next_pending = 0;          // no ticket below it is pending
+    size_t next_pending = 0;          // no ticket below it is pending or parked
+    std::vector<hipEvent_t> ev_park;  // per lane: recorded behind the lane's latest park copy, for a job that resumes on another lane
     int64_t rounds_total = 0;
     std::multimap<size_t, void*> free_blocks;      // recycled staging, by capacity
     std::vector<void*> all_blocks;                 // every staging block ever allocated: released at close
@@ -3487,6 +3499,116 @@ extern "C" int dsg_queue_place(const int32_t* K, const int32_t* arrive_round, in
     return 0;
 }
 
+// The placement of one round, written once under dsg_queue_run and dsg_queue_place_prio.  wait: the jobs that may take a slot, in ticket
+// order; slots: who holds each slot when the round starts.  (1) the waiting jobs are ordered by priority descending, ticket ascending;
+// (2) the free slots, lowest first, take them in that order; (3) every waiting job still unplaced looks among the running jobs not placed
+// in this round for the one of the lowest priority -- ties: first a job without a window to run, then the highest ticket -- and takes its
+// slot if that priority is strictly lower, else the placement ends (the jobs behind it in the order have no higher priority).  moves: in
+// the order made; parked >= 0: the job that leaves the slot.  With equal priorities (3) never moves anything and (1) + (2) is first come,
+// first served.
+struct PlaceWait { int64_t t; int32_t prio; };
+struct PlaceSlot { int64_t t = -1; int32_t prio = 0; bool idle = false, fresh = false; };
+struct PlaceMove { int64_t t; int slot; int64_t parked; };
+static void queue_place_round(std::vector<PlaceWait>& wait, std::vector<PlaceSlot>& slots, std::vector<PlaceMove>& moves) {
+    moves.clear();
+    std::stable_sort(wait.begin(), wait.end(), [](const PlaceWait& a, const PlaceWait& b) { return a.prio > b.prio; });
+    const int n_slots = (int)slots.size();
+    size_t w = 0;
+    for (int s = 0; s < n_slots && w < wait.size(); ++s) {
+        if (slots[s].t >= 0) continue;
+        moves.push_back(PlaceMove{wait[w].t, s, -1});
+        slots[s] = PlaceSlot{wait[w].t, wait[w].prio, false, true};
+        ++w;
+    }
+    for (; w < wait.size(); ++w) {
+        int v = -1;
+        for (int s = 0; s < n_slots; ++s) {
+            const PlaceSlot& c = slots[s];
+            if (c.t < 0 || c.fresh) continue;
+            if (v < 0) { v = s; continue; }
+            const PlaceSlot& b = slots[v];
+            if (c.prio != b.prio ? c.prio < b.prio : c.idle != b.idle ? c.idle : c.t > b.t) v = s;
+        }
+        if (v < 0 || slots[v].prio >= wait[w].prio) break;
+        moves.push_back(PlaceMove{wait[w].t, v, slots[v].t});
+        slots[v] = PlaceSlot{wait[w].t, wait[w].prio, false, true};
+    }
+}
+
+// The session's rounds on the host: nothing changes between two events -- an arrival, a job's last window -- so the rounds in between are
+// stepped over.  done_round: the round of a job's last window; n_rounds: one past the last of them
+extern "C" int dsg_queue_place_prio(const int32_t* K, const int32_t* arrive_round, const int32_t* priority, int n_jobs, int n_slots,
+                                    int32_t* first_round, int32_t* done_round, int32_t* n_parks, int32_t* n_rounds) {
+    if (!K || !first_round || !done_round || !n_parks || !n_rounds) return fail(DSG_E_INVALID, "dsg_queue_place_prio: null argument");
+    if (n_jobs < 1) return fail(DSG_E_INVALID, "dsg_queue_place_prio: n_jobs < 1");
+    if (n_slots < 1) return fail(DSG_E_INVALID, "dsg_queue_place_prio: n_slots < 1");
+    for (int j = 0; j < n_jobs; ++j) {
+        if (K[j] < 1) return fail(DSG_E_INVALID, "dsg_queue_place_prio: job " + std::to_string(j) + " has K < 1");
+        if (arrive_round && (arrive_round[j] < 0 || (j > 0 && arrive_round[j] < arrive_round[j - 1])))
+            return fail(DSG_E_INVALID, "dsg_queue_place_prio: arrive_round must be non-negative and non-decreasing (job " + std::to_string(j) + ")");
+    }
+    std::vector<int32_t> c(n_jobs, 0);      // windows done
+    std::vector<int> at(n_jobs, -1);        // the slot a job runs in, -1: none
+    std::vector<PlaceSlot> slots(n_slots);
+    std::vector<PlaceWait> wait;
+    std::vector<PlaceMove> moves;
+    int arrived = 0, left = n_jobs;
+    int64_t r = 0;
+    for (int j = 0; j < n_jobs; ++j) { first_round[j] = -1; done_round[j] = -1; n_parks[j] = 0; }
+    while (left > 0) {
+        while (arrived < n_jobs && (arrive_round ? arrive_round[arrived] : 0) <= r) ++arrived;
+        wait.clear();
+        for (int j = 0; j < arrived; ++j)
+            if (at[j] < 0 && c[j] < K[j]) wait.push_back(PlaceWait{j, priority ? priority[j] : 0});
+        bool running = false;
+        for (PlaceSlot& s : slots) { s.fresh = false; running = running || s.t >= 0; }
+        if (!running && wait.empty()) { r = arrive_round[arrived]; continue; }      // every slot idle: on to the next arrival
+        queue_place_round(wait, slots, moves);
+        for (const PlaceMove& m : moves) {
+            if (m.parked >= 0) { at[m.parked] = -1; ++n_parks[m.parked]; }
+            at[m.t] = m.slot;
+            if (c[m.t] == 0) first_round[m.t] = (int32_t)r;
+        }
+        int64_t dr = arrived < n_jobs ? (int64_t)arrive_round[arrived] - r : 0x7fffffff;
+        for (const PlaceSlot& s : slots) if (s.t >= 0) dr = std::min<int64_t>(dr, K[s.t] - c[s.t]);
+        r += dr;
+        if (r > 0x7fffffff) return fail(DSG_E_INVALID, "dsg_queue_place_prio: more than 2^31 - 1 rounds");
+        for (PlaceSlot& s : slots) {
+            if (s.t < 0) continue;
+            c[s.t] += (int32_t)dr;
+            if (c[s.t] < K[s.t]) continue;
+            done_round[s.t] = (int32_t)(r - 1); at[s.t] = -1; --left;
+            s = PlaceSlot{};
+        }
+    }
+    *n_rounds = (int32_t)r;
+    return 0;
+}
+
+// A running job leaves its slot at a window boundary: the [S][J] tail its last window handed off -- clip_tail[(c - 1) & 1] of its position
+// -- goes into a staging block of the job on the lane's stream, in front of the round's gather on that lane: whoever takes the slot
+// overwrites c_seed and the tail only behind it in stream order.  The lane's park event is recorded behind the copy.  (c >= 1: a job is
+// placed only with a window to run, so every job found in a slot when a round starts has handed a window off.)
+static int queue_park_job(dsg_queue* q, int64_t t) {
+    QJob& jb = q->jobs[t];
+    QueueRound& rd = q->rd;
+    const int n = (int)rd.hs.size(), lane = jb.slot % n, pos = jb.slot / n;
+    dsg_handle* h = rd.hs[lane];
+    const size_t n_tail = (size_t)h->S * h->J;
+    if (!jb.park) {      // a recycled block may still be read by a round in flight (as dsg_queue_submit: the lanes are drained first)
+        for (dsg_handle* hh : rd.hs) HIPCHK(hipStreamSynchronize(hh->stream));
+        void* p = nullptr;
+        CHK(queue_take(q, n_tail * sizeof(float), jb, &p));
+        jb.park = (float*)p;
+    }
+    HIPCHK(hipMemcpyAsync(jb.park, h->clip_tail[(jb.w.c - 1) & 1] + pos * n_tail, n_tail * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipEventRecord(q->ev_park[lane], h->stream));
+    q->slot_job[jb.slot] = -1;
+    jb.park_lane = lane; jb.slot = -1; jb.state = DSG_JOB_PARKED; ++jb.parks;
+    q->next_pending = std::min(q->next_pending, (size_t)t);
+    return 0;
+}
+
 // the round's conditioning of a lane, gathered on the device from where the session keeps its jobs' tensors: the table, one launch
 static int cond_gathered(dsg_handle* h, int B, const SlotWork* const* lane) {
     dsg_handle::Queue& q = h->cq;
@@ -3494,13 +3616,15 @@ static int cond_gathered(dsg_handle* h, int B, const SlotWork* const* lane) {
     q.gather_host.resize(B);
     for (int b = 0; b < B; ++b) {
         const SlotWork* w = lane[b];
-        q.gather_host[b] = w ? GatherSlot{w->job.style, w->win_audio ? w->win_audio : w->job.audio + w->c * n_audio, w->job.seed0, w->job.seed_last, GQ_LIVE | (w->c == 0 ? GQ_FIRST : 0), 0}
-                             : GatherSlot{nullptr, nullptr, nullptr, nullptr, 0, 0};
+        q.gather_host[b] = w ? GatherSlot{w->job.style, w->win_audio ? w->win_audio : w->job.audio + w->c * n_audio, w->job.seed0, w->job.seed_last,
+                                          GQ_LIVE | (w->c == 0 ? GQ_FIRST : 0) | (w->resume ? GQ_RESUME : 0), w->c, w->resume}
+                             : GatherSlot{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
     }
     HIPCHK(hipMemcpyAsync(q.gather, q.gather_host.data(), (size_t)B * sizeof(GatherSlot), hipMemcpyHostToDevice, h->stream));
     GatherQArgs a;
     a.slots = q.gather; a.q_style = q.style; a.q_audio = q.audio; a.c_seed = h->c_seed; a.c_seed_last = h->c_seed_last;
-    a.B = B; a.sdi = h->cfg.style_dim_in; a.n_audio = h->Ta * h->As; a.n_seed = h->J * h->S; a.variant5 = h->cfg.variant == 5 ? 1 : 0;
+    a.tail0 = h->clip_tail[0]; a.tail1 = h->clip_tail[1];
+    a.B = B; a.sdi = h->cfg.style_dim_in; a.n_audio = h->Ta * h->As; a.n_seed = h->J * h->S; a.variant5 = h->cfg.variant == 5 ? 1 : 0; a.S = h->S;
     const size_t n = (size_t)B * ((a.sdi + 3) / 4 + (a.n_audio + 3) / 4 + (size_t)(a.variant5 ? 2 : 1) * ((a.n_seed + 3) / 4));
     hipLaunchKernelGGL(k_clipq_gather, dim3((int)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
@@ -3528,6 +3652,17 @@ extern "C" int dsg_queue_open(dsg_handle** hs, int n, int B, const uint8_t* mask
     q->rd.cond = cond_gathered;
     q->rd.lane_init.assign(n, 1);      // (lane_inp stays empty: per round)
     q->slot_job.assign((size_t)n * B, -1);
+    for (int i = 0; i < n; ++i) {
+        hipEvent_t ev = nullptr;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            for (hipEvent_t e : q->ev_park) (void)hipEventDestroy(e);
+            if (mask_d) (void)hipFree(mask_d);
+            delete q;
+            return fail(DSG_E_RUNTIME, "dsg_queue_open: hipEventCreate failed");
+        }
+        q->ev_park.push_back(ev);
+    }
     for (int i = 0; i < n; ++i) hs[i]->owner = q;
     *out = q;
     return 0;
@@ -3610,14 +3745,16 @@ extern "C" int dsg_queue_submit_live(dsg_queue* q, const dsg_clip_job* job, int 
 // every row of the clip is written and delivered already.  With it the closing S rows are the slot's tail -- [S][J], the values handoff_row
 // stored for f >= keep after the shift, which are the values the last window would have written to the clip had it known it was the last;
 // window K - 1 wrote clip_tail[(K - 1) & 1] -- copied on the lane's stream into the clip and on to a host `out`.  The lane is drained: the
-// call has no stream of the caller's to order a device `out` before
+// call has no stream of the caller's to order a device `out` before.  A PARKED job holds no slot: its tail is the parked block -- the same
+// values, copied when it left its slot -- read on the stream of the lane that wrote it
 static int queue_finish_late(dsg_queue* q, QJob& jb) {
     const QueueRound& rd = q->rd;
     const int n = (int)rd.hs.size(), J = rd.hs[0]->J, S = rd.hs[0]->S, keep = rd.hs[0]->T - S, K = jb.w.job.K;
-    dsg_handle* h = rd.hs[jb.slot % n];
+    const bool parked = jb.state == DSG_JOB_PARKED;
+    dsg_handle* h = rd.hs[parked ? jb.park_lane : jb.slot % n];
     HIPCHK(hipSetDevice(h->cfg.device));
     if (rd.keep_last_tail) {
-        const float* tail = h->clip_tail[(K - 1) & 1] + (size_t)(jb.slot / n) * S * J;
+        const float* tail = parked ? jb.park : h->clip_tail[(K - 1) & 1] + (size_t)(jb.slot / n) * S * J;
         HIPCHK(hipMemcpyAsync(jb.w.clip + ((size_t)K * keep - S) * J, tail, (size_t)S * J * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     }
     jb.rows_ready = jb.w.ed.n_out;
@@ -3629,7 +3766,8 @@ static int queue_finish_late(dsg_queue* q, QJob& jb) {
     HIPCHK(hipStreamSynchronize(h->stream));
     jb.state = DSG_JOB_DONE;
     queue_give(q, jb);
-    q->slot_job[jb.slot] = -1;
+    jb.park = nullptr;
+    if (!parked) q->slot_job[jb.slot] = -1;
     return 0;
 }
 extern "C" int dsg_queue_finish(dsg_queue* q, int64_t ticket) {
@@ -3647,7 +3785,7 @@ extern "C" int dsg_queue_finish(dsg_queue* q, int64_t ticket) {
     }
     jb.w.job.K = K;
     jb.w.ed.n_out = K * keep - (q->rd.keep_last_tail ? 0 : S);
-    if (jb.state == DSG_JOB_RUNNING && jb.w.c >= K) return queue_finish_late(q, jb);
+    if ((jb.state == DSG_JOB_RUNNING || jb.state == DSG_JOB_PARKED) && jb.w.c >= K) return queue_finish_late(q, jb);
     return 0;      // windows still to run: the last of them runs with HQ_LAST and the job is done after that round
 }
 extern "C" int dsg_queue_append(dsg_queue* q, int64_t ticket, const dsg_queue_window* wins, int n, void* stream) {
@@ -3706,20 +3844,36 @@ extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void
     HIPCHK(hipSetDevice(hs[0]->cfg.device));
     CHK(rd.begin(stream));
     std::vector<const SlotWork*> slots(n_slots);
+    std::vector<PlaceWait> wait;
+    std::vector<PlaceSlot> held_by(n_slots);
+    std::vector<PlaceMove> moves;
     int done = 0;
     while (max_rounds <= 0 || done < max_rounds) {
-        // placement: the free slots, lowest first, take the pending jobs, oldest ticket first
-        // (a pending live job without a window yet cannot be placed: the tickets behind it pass it)
-        size_t p = q->next_pending;
+        // a running job the caller holds (dsg_queue_park) leaves its slot
+        for (int s = 0; s < n_slots; ++s)
+            if (q->slot_job[s] >= 0 && q->jobs[q->slot_job[s]].held) CHK(queue_park_job(q, q->slot_job[s]));
+        // placement (queue_place_round): the waiting jobs -- pending or parked, not held, with a window to run -- by priority, then ticket;
+        // free slots first, then the slots of running jobs of a strictly lower priority, which are parked.  (A live job without a window
+        // cannot be placed: the tickets behind it pass it.)  With equal priorities: the free slots, lowest first, take the oldest tickets
+        while (q->next_pending < q->jobs.size() && q->jobs[q->next_pending].state != DSG_JOB_PENDING && q->jobs[q->next_pending].state != DSG_JOB_PARKED)
+            ++q->next_pending;
+        wait.clear();
+        for (size_t t = q->next_pending; t < q->jobs.size(); ++t)
+            if (q->jobs[t].waiting()) wait.push_back(PlaceWait{(int64_t)t, q->jobs[t].priority});
         for (int s = 0; s < n_slots; ++s) {
-            if (q->slot_job[s] >= 0) continue;
-            while (q->next_pending < q->jobs.size() && q->jobs[q->next_pending].state != DSG_JOB_PENDING) ++q->next_pending;
-            p = std::max(p, q->next_pending);
-            while (p < q->jobs.size() && (q->jobs[p].state != DSG_JOB_PENDING || !q->jobs[p].has_window())) ++p;
-            if (p >= q->jobs.size()) break;
-            QJob& jb = q->jobs[p];
-            jb.state = DSG_JOB_RUNNING; jb.slot = s; jb.first_round = (int)q->rounds_total;
-            q->slot_job[s] = (int64_t)p++;
+            const int64_t t = q->slot_job[s];
+            held_by[s] = t < 0 ? PlaceSlot{} : PlaceSlot{t, q->jobs[t].priority, !q->jobs[t].has_window(), false};
+        }
+        queue_place_round(wait, held_by, moves);
+        for (const PlaceMove& m : moves) {
+            if (m.parked >= 0) CHK(queue_park_job(q, m.parked));
+            QJob& jb = q->jobs[m.t];
+            if (jb.state == DSG_JOB_PARKED) {      // its tail goes into the new slot with the round's gather, behind the copy that parked it
+                jb.w.resume = jb.park;
+                if (m.slot % n != jb.park_lane) HIPCHK(hipStreamWaitEvent(hs[m.slot % n]->stream, q->ev_park[jb.park_lane], 0));
+            } else jb.first_round = (int)q->rounds_total;
+            jb.state = DSG_JOB_RUNNING; jb.slot = m.slot;
+            q->slot_job[m.slot] = m.t;
         }
         // a running live job without a window to run sits the round out: a dead slot, whose c_seed rows, tail and state stay
         bool alive = false;
@@ -3745,6 +3899,7 @@ extern "C" int dsg_queue_run(dsg_queue* q, int max_rounds, int* rounds_run, void
             if (!slots[s]) continue;
             QJob& jb = q->jobs[t];
             ++jb.w.c;
+            jb.w.resume = nullptr;      // (its tail is the slot's again)
             jb.rows_ready = queue_rows_ready(q, jb);
             if (jb.host_out && jb.rows_ready > jb.rows_copied) {
                 const size_t at = (size_t)jb.rows_copied * J, cnt = (size_t)(jb.rows_ready - jb.rows_copied) * J;
@@ -3775,12 +3930,14 @@ extern "C" int dsg_queue_job(dsg_queue* q, int64_t ticket, dsg_queue_job_info* i
     memset(info, 0, sizeof *info);
     info->state = jb.state; info->windows_done = jb.w.c; info->rows_ready = jb.rows_ready; info->slot = jb.slot; info->first_round = jb.first_round;
     if (jb.live) { info->windows_given = (int32_t)jb.wins.size(); info->live = DSG_JOB_LIVE | (jb.finished ? DSG_JOB_FINISHED : 0); }
+    if (jb.held && jb.state != DSG_JOB_DONE && jb.state != DSG_JOB_CANCELLED) info->live |= DSG_JOB_HELD;
+    info->reserved[0] = jb.parks;
     return 0;
 }
 extern "C" int dsg_queue_info(dsg_queue* q, int64_t* rounds_total, int* n_pending, int* n_running) {
     if (!q) return fail(DSG_E_INVALID, "dsg_queue_info: null queue");
     int pend = 0, run = 0;
-    for (size_t t = q->next_pending; t < q->jobs.size(); ++t) pend += q->jobs[t].state == DSG_JOB_PENDING;
+    for (size_t t = q->next_pending; t < q->jobs.size(); ++t) pend += q->jobs[t].state == DSG_JOB_PENDING || q->jobs[t].state == DSG_JOB_PARKED;
     for (int64_t t : q->slot_job) run += t >= 0;
     if (rounds_total) *rounds_total = q->rounds_total;
     if (n_pending) *n_pending = pend;
@@ -3793,8 +3950,34 @@ extern "C" int dsg_queue_cancel(dsg_queue* q, int64_t ticket) {
     QJob& jb = q->jobs[ticket];
     if (jb.state == DSG_JOB_DONE || jb.state == DSG_JOB_CANCELLED) return 0;      // nothing left to cancel
     if (jb.state == DSG_JOB_RUNNING) q->slot_job[jb.slot] = -1;                    // dead from the next round on; the rows written so far stay
-    jb.state = DSG_JOB_CANCELLED;
-    queue_give(q, jb);      // (dsg_queue_submit drains the lanes before it writes over a recycled block)
+    jb.state = DSG_JOB_CANCELLED;      // (a parked job holds no slot)
+    queue_give(q, jb);      // (dsg_queue_submit drains the lanes before it writes over a recycled block, a parked tail included)
+    jb.park = nullptr;
+    return 0;
+}
+// dsg_queue_set_priority / _park / _resume: the job's word for the next placement; nothing happens on the device before dsg_queue_run
+static int queue_ticket(dsg_queue* q, int64_t ticket, const char* who, QJob** jb) {
+    if (!q) return fail(DSG_E_INVALID, std::string(who) + ": null queue");
+    if (ticket < 0 || ticket >= (int64_t)q->jobs.size()) return fail(DSG_E_INVALID, std::string(who) + ": no such ticket: " + std::to_string(ticket));
+    *jb = &q->jobs[ticket];
+    return 0;
+}
+extern "C" int dsg_queue_set_priority(dsg_queue* q, int64_t ticket, int32_t priority) {
+    QJob* jb = nullptr;
+    CHK(queue_ticket(q, ticket, "dsg_queue_set_priority", &jb));
+    if (jb->state != DSG_JOB_DONE && jb->state != DSG_JOB_CANCELLED) jb->priority = priority;
+    return 0;
+}
+extern "C" int dsg_queue_park(dsg_queue* q, int64_t ticket) {
+    QJob* jb = nullptr;
+    CHK(queue_ticket(q, ticket, "dsg_queue_park", &jb));
+    if (jb->state != DSG_JOB_DONE && jb->state != DSG_JOB_CANCELLED) jb->held = true;      // (a parked or held job: nothing changes)
+    return 0;
+}
+extern "C" int dsg_queue_resume(dsg_queue* q, int64_t ticket) {
+    QJob* jb = nullptr;
+    CHK(queue_ticket(q, ticket, "dsg_queue_resume", &jb));
+    jb->held = false;
     return 0;
 }
 extern "C" int dsg_queue_close(dsg_queue* q) {
@@ -3805,6 +3988,7 @@ extern "C" int dsg_queue_close(dsg_queue* q) {
         h->owner = nullptr;
     }
     q->rd.leave();
+    for (hipEvent_t e : q->ev_park) (void)hipEventDestroy(e);
     for (void* p : q->all_blocks) (void)hipFree(p);
     if (q->rd.mask) (void)hipFree((void*)q->rd.mask);
     delete q;

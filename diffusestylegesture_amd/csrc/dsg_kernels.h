@@ -1970,20 +1970,37 @@ __global__ void k_clipq_x_in(const ClipXInQArgs a) {
 // past its first window leaves c_seed alone (the hand-off wrote it).  One thread per 16-byte quad; a caller's device tensor may sit on any
 // 4-byte boundary and sdi / n_seed are no multiples of 4 in the product models, so source and destination are each accessed as 16 bytes
 // where their address allows and as scalars elsewhere (clip_inp_load4 / handoff_store4).  A pure copy: no bits change.
+// RESUME (GQ_RESUME, never with GQ_FIRST): the slot takes a job that was parked at a window boundary (dsg_queue_park, or pre-empted by a
+// higher priority) and stands on window c > 0.  `resume` is the [S][J] block its last hand-off left -- the parked copy of
+// clip_tail[(c - 1) & 1] of the slot it ran in -- and the quads that would carry seed0 on a first window put it back as both images
+// handoff_row writes: clip_tail[(c - 1) & 1][b][s][j] = resume[s][j] and, transposed, c_seed[b][j][s] = resume[s][j], so window c shifts,
+// blends and seeds exactly as it would have in the old slot.  Variant 5: y['seed_last'] is per job and stays in the slot's rows of
+// c_seed_last, so it is gathered again for the new slot.  Slots without the flag take the path they always took.
 struct GatherSlot {
     const float* style; const float* audio;      // [sdi], [n_audio] of the window the slot stands on
     const float* seed0; const float* seed_last;  // [n_seed] each; read on the first window only; seed0 null: zeros
-    int flags, pad_;                             // GQ_LIVE | GQ_FIRST
+    int flags, c;                                // GQ_LIVE | GQ_FIRST | GQ_RESUME; c: the window the slot stands on (read with GQ_RESUME)
+    const float* resume;                         // [S][J], read with GQ_RESUME
 };
-enum { GQ_LIVE = 1, GQ_FIRST = 2 };
+enum { GQ_LIVE = 1, GQ_FIRST = 2, GQ_RESUME = 4 };
 struct GatherQArgs {
     const GatherSlot* slots; float* q_style; float* q_audio; float* c_seed; float* c_seed_last;
-    int B, sdi, n_audio, n_seed, variant5;
+    float* tail0; float* tail1;                  // clip_tail[0] / [1], written with GQ_RESUME
+    int B, sdi, n_audio, n_seed, variant5, S;    // n_seed = J * S
 };
 __device__ __forceinline__ void gather_quad(float* dst, const float* src, int at, int n) {      // quad `at / 4` of a row of n floats
     const int nv = n - at < 4 ? n - at : 4;
     const f32x4 v = src ? clip_inp_load4(src + at, nv) : (f32x4){0.f, 0.f, 0.f, 0.f};
     handoff_store4(dst + at, v, nv);
+}
+// quad `at / 4` of a parked [S][J] block: into the slot's tail as it is, into the slot's c_seed [J][S] transposed
+__device__ __forceinline__ void resume_quad(float* tail, float* c_seed, const float* src, int at, int n, int S) {
+    const int nv = n - at < 4 ? n - at : 4, J = n / S;
+    const f32x4 v = clip_inp_load4(src + at, nv);
+    handoff_store4(tail + at, v, nv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (e < nv) { const int sf = (at + e) / J, j = (at + e) % J; c_seed[(size_t)j * S + sf] = v[e]; }
 }
 __global__ void k_clipq_gather(const GatherQArgs a) {
     const int qs = (a.sdi + 3) / 4, qa = (a.n_audio + 3) / 4, qd = (a.n_seed + 3) / 4;
@@ -1997,9 +2014,10 @@ __global__ void k_clipq_gather(const GatherQArgs a) {
         k -= qs;
         if (k < qa) { gather_quad(a.q_audio + (size_t)b * a.n_audio, s.audio, 4 * k, a.n_audio); continue; }
         k -= qa;
-        if (!(s.flags & GQ_FIRST)) continue;
-        if (k < qd) { gather_quad(a.c_seed + (size_t)b * a.n_seed, s.seed0, 4 * k, a.n_seed); continue; }
-        gather_quad(a.c_seed_last + (size_t)b * a.n_seed, s.seed_last, 4 * (k - qd), a.n_seed);
+        if (!(s.flags & (GQ_FIRST | GQ_RESUME))) continue;
+        if (k >= qd) { gather_quad(a.c_seed_last + (size_t)b * a.n_seed, s.seed_last, 4 * (k - qd), a.n_seed); continue; }
+        if (s.flags & GQ_FIRST) { gather_quad(a.c_seed + (size_t)b * a.n_seed, s.seed0, 4 * k, a.n_seed); continue; }
+        resume_quad(((s.c - 1) & 1 ? a.tail1 : a.tail0) + (size_t)b * a.n_seed, a.c_seed + (size_t)b * a.n_seed, s.resume, 4 * k, a.n_seed, a.S);
     }
 }
 // Self-check of the fence-free hand-off (dsg_hip.cpp: uc_selfcheck): `buf` is uncached device memory; the two kernels run as

@@ -827,11 +827,22 @@ class DSGDiffusion:
 _INPAINT_KEYS = ("inpainting_mask", "inpainted_motion")
 
 
+class _JobInfo(dict):
+    """what `ClipQueue.job` returns: a dict in which the words of parking read as their defaults while they are not stored"""
+    DEFAULTS = {"parks": 0, "held": False, "priority": 0}
+
+    def __missing__(self, key):
+        return self.DEFAULTS[key]
+
+
 class ClipQueue:
     """A queue session (`DSGDiffusion.open_clip_queue`; dsg_queue_* of include/dsg.h).  `submit` a clip dict at any time, `run` rounds,
     read `rows(ticket)` as windows finish, `result(ticket)` when the clip is done.  Host tensors of a clip are copied by `submit`; device
     tensors must stay valid until the clip is done or cancelled (the session keeps a reference).  Not thread safe: submit and run from
-    one thread.  Placement is first come, first served (`lib.queue_place`)."""
+    one thread.  Placement is by priority, then first come, first served: every round the waiting clips -- pending or parked, not held --
+    take the free slots, highest `priority` first, oldest ticket first, and then the slots of running clips of a strictly lower priority,
+    which are parked at that window boundary and continue later in any slot (`lib.queue_place_prio`; with equal priorities
+    `lib.queue_place`).  `park` / `resume` pause a clip and let it go on; a clip comes out bit for bit the same however often it was parked."""
 
     def __init__(self, diffusion, lanes, B, *, root_shift, keep_last_tail, ddim, eta, skip_timesteps, clip_denoised, guided, mask_local):
         self._handle = None
@@ -849,6 +860,7 @@ class ClipQueue:
         self._advance = 0
         self._outs, self._keep = [], {}
         self._live = {}                                  # ticket -> [windows given, steps per window] of a live job
+        self._prio = []                                  # per ticket: its priority (the library reports every other word of a job)
         hs = (C.c_void_p * len(self.lanes))(*[m.handle for m in self.lanes])
         q = C.c_void_p()
         self.lib.check(self.lib.cdll.dsg_queue_open(hs, len(self.lanes), self.B, mbuf.p, int(bool(guided)), C.byref(a), int(bool(root_shift)),
@@ -872,13 +884,14 @@ class ClipQueue:
             raise L.DSGError("the clip queue is closed")
         return self._handle
 
-    def submit(self, clip, out=None) -> int:
+    def submit(self, clip, out=None, priority=0) -> int:
         """One clip dict as `sample_clip_queue` takes it, "skip_timesteps" and the edit keys included.  Returns its ticket (0, 1, ...).
         `out`: the caller's own C-contiguous float32 numpy array [n_out, J] to receive the clip (a playback buffer); rows past
-        `rows_ready` are never touched.  Default: an array of the session's."""
-        return self._submit(clip, out, None)
+        `rows_ready` are never touched.  Default: an array of the session's.  `priority` (or a "priority" key of the dict): higher runs
+        first and takes the slot of a running clip of a lower one; default 0."""
+        return self._submit(clip, out, None, priority)
 
-    def submit_live(self, clip, capacity, out=None) -> int:
+    def submit_live(self, clip, capacity, out=None, priority=0) -> int:
         """A live clip (dsg_queue_submit_live): its windows arrive while it runs.  `clip` as for `submit`, without edits; "feats" are the
         windows known now and may be empty.  `capacity`: the most windows it may ever get -- `out` (the caller's, or the session's) is
         [n_out(capacity), J].  Feed it with `append`, end it with `finish` (or `append(..., last=True)`); `rows` / `result` as for every
@@ -886,9 +899,9 @@ class ClipQueue:
         self._q()
         if any(clip.get(k) is not None for k in ("inpainting_mask", "inpainted_motion", "init_motion")):
             raise ValueError(f"ClipQueue.submit_live: clip {len(self._outs)}: a live clip takes no edits (their coordinates depend on the final length)")
-        return self._submit(clip, out, capacity)
+        return self._submit(clip, out, capacity, priority)
 
-    def _submit(self, clip, out, capacity):
+    def _submit(self, clip, out, capacity, priority=0):
         """`submit` (`capacity` None: dsg_queue_submit) and `submit_live` (dsg_queue_submit_live)"""
         live = capacity is not None
         who = "ClipQueue.submit_live" if live else "ClipQueue.submit"
@@ -918,6 +931,11 @@ class ClipQueue:
             self.lib.check(self.lib.cdll.dsg_queue_submit(q, C.byref(job), C.byref(edit) if has_edit else None, skip, C.byref(ticket), stream))
         assert ticket.value == i
         self._outs.append(out)
+        self._prio.append(0)
+        prio = clip.get("priority")
+        prio = int(priority) if prio is None else int(prio)
+        if prio:
+            self.set_priority(i, prio)
         dev = [b for b in bufs if b.obj is not None and L.is_torch(b.obj) and b.obj.is_cuda]
         if dev:
             self._keep[i] = dev                          # device tensors are read where they are, until the clip is done or cancelled
@@ -969,6 +987,21 @@ class ClipQueue:
         window -- at once when that has run already."""
         self.lib.check(self.lib.cdll.dsg_queue_finish(self._q(), int(ticket)))
 
+    def set_priority(self, ticket, priority):
+        """dsg_queue_set_priority: read at the next placement; a clip that is done or cancelled keeps what it had."""
+        self.lib.check(self.lib.cdll.dsg_queue_set_priority(self._q(), int(ticket), int(priority)))
+        if self.job(ticket)["state"] not in (L.JOB_DONE, L.JOB_CANCELLED):
+            self._prio[int(ticket)] = int(priority)
+
+    def park(self, ticket):
+        """dsg_queue_park: the clip waits -- a pending one is not placed, a running one leaves its slot at the start of the next round --
+        until `resume`.  Its rows so far stay; it continues bit for bit where it stopped."""
+        self.lib.check(self.lib.cdll.dsg_queue_park(self._q(), int(ticket)))
+
+    def resume(self, ticket):
+        """dsg_queue_resume: the clip competes for a slot again, like any waiting clip."""
+        self.lib.check(self.lib.cdll.dsg_queue_resume(self._q(), int(ticket)))
+
     def run(self, max_rounds=1) -> int:
         """Up to `max_rounds` rounds (0: until nothing has a window to run and nothing pending can be placed); returns the rounds run."""
         n = C.c_int(0)
@@ -981,10 +1014,14 @@ class ClipQueue:
 
     def job(self, ticket) -> dict:
         """{"state", "windows_done", "rows_ready", "slot", "first_round"} of a ticket (state: lib.JOB_*); a live clip adds "windows_given",
-        "live" (True) and "finished"."""
+        "live" (True) and "finished".  j["parks"] (how often the clip left a slot before its end), j["held"] and j["priority"] read 0 /
+        False / 0 for a clip that was never parked, held or given a priority, and are stored in the dict only once they differ: the dict
+        of such a clip compares equal to what it always was."""
         info = L.dsg_queue_job_info()
         self.lib.check(self.lib.cdll.dsg_queue_job(self._q(), int(ticket), C.byref(info)))
-        d = {k: int(getattr(info, k)) for k in ("state", "windows_done", "rows_ready", "slot", "first_round")}
+        d = _JobInfo({k: int(getattr(info, k)) for k in ("state", "windows_done", "rows_ready", "slot", "first_round")})
+        more = {"parks": int(info.reserved[2]), "held": bool(info.reserved[1] & L.JOB_HELD), "priority": self._prio[int(ticket)]}
+        d.update({k: v for k, v in more.items() if v != _JobInfo.DEFAULTS[k]})
         if info.reserved[1] & L.JOB_LIVE:
             d.update(windows_given=int(info.reserved[0]), live=True, finished=bool(info.reserved[1] & L.JOB_FINISHED))
         return d

@@ -55,6 +55,8 @@ class dsg_queue_job_info(C.Structure):
 
 JOB_PENDING, JOB_RUNNING, JOB_DONE, JOB_CANCELLED = 0, 1, 2, 3          # DSG_JOB_* of include/dsg.h
 JOB_LIVE, JOB_FINISHED = 1, 2          # bits of dsg_queue_job_info.live (reserved[1] here; reserved[0]: windows_given)
+JOB_PARKED = 4                         # DSG_JOB_PARKED: a job that left its slot at a window boundary (reserved[2] here: parks)
+JOB_HELD = 4                           # DSG_JOB_HELD, a bit of .live: the caller asked the job to wait (dsg_queue_park)
 
 
 class dsg_queue_window(C.Structure):
@@ -107,6 +109,10 @@ SYMBOLS = {
     "dsg_queue_submit_live": (_I, [_P, C.POINTER(dsg_clip_job), _I, _I, C.POINTER(_I64), _P]),
     "dsg_queue_append": (_I, [_P, _I64, C.POINTER(dsg_queue_window), _I, _P]),
     "dsg_queue_finish": (_I, [_P, _I64]),
+    "dsg_queue_set_priority": (_I, [_P, _I64, C.c_int32]),
+    "dsg_queue_park": (_I, [_P, _I64]),
+    "dsg_queue_resume": (_I, [_P, _I64]),
+    "dsg_queue_place_prio": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, C.POINTER(C.c_int32)]),
     "dsg_set_kernel_set": (_I, [_P, _I]),
     "dsg_get_kernel_set": (_I, [_P, C.POINTER(_I)]),
     "dsg_recommend_kernel_set": (_I, [_P, _I, _I, C.POINTER(_I)]),
@@ -205,6 +211,24 @@ def queue_place(K, n_slots: int, arrive_round=None, library: "DSGLibrary | None"
     lib.check(lib.cdll.dsg_queue_place(k.ctypes.data, None if arr is None else arr.ctypes.data, len(k), int(n_slots), slot.ctypes.data,
                                        first.ctypes.data, C.byref(n_rounds)))
     return slot.tolist(), first.tolist(), int(n_rounds.value)
+
+
+def queue_place_prio(K, n_slots: int, arrive_round=None, priority=None, library: "DSGLibrary | None" = None):
+    """dsg_queue_place_prio: the rounds of a queue session with priorities (host only) -- every round the waiting jobs, by priority
+    descending then ticket ascending, take the free slots and then the slots of running jobs of a strictly lower priority, which are
+    parked.  Returns (first_round[j], done_round[j], n_parks[j], n_rounds); done_round: the round of a job's last window."""
+    lib = library or default_library()
+    k = np.ascontiguousarray(K, dtype=np.int32)
+    opt = {}
+    for name, v in (("arrive_round", arrive_round), ("priority", priority)):
+        opt[name] = None if v is None else np.ascontiguousarray(v, dtype=np.int32)
+        if opt[name] is not None and opt[name].shape != k.shape:
+            raise ValueError(f"queue_place_prio: {name} has {opt[name].size} entries for {k.size} jobs")
+    arr, pri = opt["arrive_round"], opt["priority"]
+    first, done, parks, n_rounds = np.zeros(len(k), np.int32), np.zeros(len(k), np.int32), np.zeros(len(k), np.int32), C.c_int32(0)
+    lib.check(lib.cdll.dsg_queue_place_prio(k.ctypes.data, None if arr is None else arr.ctypes.data, None if pri is None else pri.ctypes.data,
+                                            len(k), int(n_slots), first.ctypes.data, done.ctypes.data, parks.ctypes.data, C.byref(n_rounds)))
+    return first.tolist(), done.tolist(), parks.tolist(), int(n_rounds.value)
 
 
 _default = None

@@ -645,9 +645,10 @@ class _ClipQueueSession:
     def __exit__(self, *exc):
         self.close()
 
-    def submit(self, clip) -> int:
-        """One clip dict of `generate_clip_queue` (`generate_clip_queue_dsgplus` for a DSG+ session); "clip_id" defaults to the ticket."""
-        t = self.queue.submit(_queue_job(self.cfg, clip, self._n, self.dsgplus))
+    def submit(self, clip, priority=0) -> int:
+        """One clip dict of `generate_clip_queue` (`generate_clip_queue_dsgplus` for a DSG+ session); "clip_id" defaults to the ticket.
+        `priority` (or a "priority" key of the dict) as `ClipQueue.submit`: higher runs first, default 0."""
+        t = self.queue.submit(_queue_job(self.cfg, clip, self._n, self.dsgplus), priority=clip.get("priority", priority))
         self._n += 1
         if self.dsgplus:
             self._real[t] = int(clip["real_n_frames"])
@@ -669,13 +670,14 @@ class _ClipQueueSession:
         self._live[ticket][2] = feats[-1]
         return audio
 
-    def submit_live(self, clip, capacity) -> int:
+    def submit_live(self, clip, capacity, priority=0) -> int:
         """A live clip (`ClipQueue.submit_live`): the clip dict of `submit` without edits and without "real_n_frames"; "feats" are the
-        windows known now and may be empty; `capacity`: the most windows it may ever get.  Feed it with `append`, end it with `finish`."""
+        windows known now and may be empty; `capacity`: the most windows it may ever get.  Feed it with `append`, end it with `finish`.
+        `priority` as for `submit`."""
         ticket = self._n                                 # (tickets count submissions)
         self._live[ticket] = [clip["seed_pose"], clip.get("seed_last"), None] if self.dsgplus else None
         job = _queue_job(self.cfg, dict(clip, feats=self._window_audio(ticket, clip.get("feats") or [])), ticket, self.dsgplus, live=True)
-        t = self.queue.submit_live(job, capacity)
+        t = self.queue.submit_live(job, capacity, priority=clip.get("priority", priority))
         assert t == ticket
         self._n += 1
         return t
@@ -698,6 +700,16 @@ class _ClipQueueSession:
         if not self.dsgplus:
             return q
         return np.ascontiguousarray(q[: self._real.get(int(ticket)), : self.cfg.njoints // self.feature_division], dtype=np.float32)
+
+    def set_priority(self, ticket, priority):
+        self.queue.set_priority(ticket, priority)
+
+    def park(self, ticket):
+        """`ClipQueue.park`: the clip waits -- a running one leaves its slot at the next round -- until `resume`"""
+        self.queue.park(ticket)
+
+    def resume(self, ticket):
+        self.queue.resume(ticket)
 
     def run(self, max_rounds=1) -> int:
         return self.queue.run(max_rounds)
@@ -729,8 +741,8 @@ class _ClipQueueSession:
 def open_clip_queue(lanes, diffusion, seed=123456, smoothing=True, skip_timesteps=0, ddim=False, eta=0.0, kernel_set="recommended", *, B=None,
                     guided=False):
     """`generate_clip_queue` as a session: submit ZEGGS clip dicts while it runs, collect rows per window (`DSGDiffusion.open_clip_queue`).
-    Returns a context manager with submit / run / job / rows / result / cancel / close, and submit_live / append / finish for a clip whose
-    windows arrive while it runs.  `guided` is fixed at open (a lane wrapped in
+    Returns a context manager with submit / run / job / rows / result / cancel / close, submit_live / append / finish for a clip whose
+    windows arrive while it runs, and set_priority / park / resume (`submit(clip, priority=)`: higher runs first and pre-empts).  `guided` is fixed at open (a lane wrapped in
     ClassifierFreeSampleModel turns it on); B defaults to the lanes' max_batch (halved with guidance).  Clip i is bit for bit
     `generate_clip(lane of batch 1, ..., windows="library", stream_id=clip_id)` whenever it was submitted."""
     return _ClipQueueSession(lanes, diffusion, False, seed, skip_timesteps, ddim, eta, kernel_set, B, guided, smoothing, 1)

@@ -431,7 +431,8 @@ int dsg_clip_queue_plan_steps(const int32_t* K, const int32_t* n_run /* NULL: al
  * read where they are, behind whatever `stream` has enqueued, and must stay valid until the job is DONE or CANCELLED.  `out` stays the
  * caller's until then, host or device.  Staging blocks are recycled inside the session and released at close.  An allocation that fails:
  * DSG_E_RUNTIME, and the session is as it was.
- * PLACEMENT: at the start of every round the free slots take the pending jobs -- lowest free slot first, oldest ticket first.  Global slot s is
+ * PLACEMENT (with equal priorities; "Priorities, park and resume" below states the whole rule): at the start of every round the free slots take
+ * the pending jobs -- lowest free slot first, oldest ticket first.  Global slot s is
  * lane s % n_lanes, position s / n_lanes, as in the one-shot call.  First come, first served is deliberate: predictable latency is what a
  * session is for.  A caller who holds the whole corpus submits it longest first, which reproduces the one-shot plan, or keeps using the
  * one-shot call.  dsg_queue_place is this rule on the host (no device): arrive_round[j] = the session round before which job j is submitted,
@@ -462,8 +463,8 @@ typedef struct dsg_queue_job_info {
     int32_t slot;          /* global slot, -1 while pending                               */
     int32_t first_round;   /* session round of its window 0, -1 while pending             */
     int32_t windows_given; /* a live job: the windows given so far; 0 for a closed job    */
-    int32_t live;          /* DSG_JOB_LIVE | DSG_JOB_FINISHED; 0 for a closed job         */
-    int32_t reserved[1];
+    int32_t live;          /* DSG_JOB_LIVE | DSG_JOB_FINISHED | DSG_JOB_HELD; 0 for a closed job nobody holds */
+    int32_t reserved[1];   /* [0]: parks -- how often the job has been parked (priorities, below); 0 for a job never parked */
 } dsg_queue_job_info;
 enum { DSG_JOB_LIVE = 1, DSG_JOB_FINISHED = 2 };      /* dsg_queue_job_info.live */
 int dsg_queue_open(dsg_handle** lanes, int n_lanes, int B, const uint8_t* mask_local, int guided,
@@ -527,6 +528,56 @@ int dsg_queue_submit_live(dsg_queue* q, const dsg_clip_job* job, int n_given, in
                           int64_t* ticket, void* stream);
 int dsg_queue_append(dsg_queue* q, int64_t ticket, const dsg_queue_window* wins, int n, void* stream);
 int dsg_queue_finish(dsg_queue* q, int64_t ticket);
+/* Priorities, park and resume at window boundaries.  Placement above is first come, first served and a placed job keeps its slot until it
+ * ends: a live speaker submitted while every slot holds a long batch clip waits for a clip to end, an idle live job keeps its slot as dead
+ * rows, and a generation cannot be paused without cancelling it.  Between two rounds the only device state a running job owns is one [S][J]
+ * fp32 block -- the tail its last window handed off -- and everything else a round needs (noise key and draw offsets, edits, skip,
+ * conditioning, `out`) travels with the job.  So a job may leave its slot at a window boundary and continue later in any slot of any lane.
+ * The promise stands: a job comes out bit for bit as dsg_sample_clip produces it alone -- B = 1, its (seed, stream_id), its skip and edits,
+ * the same draw_base, root_shift / keep_last_tail and named kernel set -- however often it was parked and whichever slots and lanes it ran
+ * in; for a live job with the provisos stated above.  Reference counterpart: none.
+ * STATES: DSG_JOB_PARKED -- the job has run at least one window, holds no slot (slot == -1) and its hand-off state lives in session staging.
+ * DSG_JOB_HELD (a bit of dsg_queue_job_info.live, for closed jobs too) -- the caller asked it to wait: a held PENDING job stays PENDING and
+ * is not placed; a held RUNNING job is parked when dsg_queue_run next starts a round (or finds that none can start).  dsg_queue_job_info.
+ * reserved[0] is `parks`, how often the job has been parked: 0 for every job never parked.  first_round stays the round of window 0;
+ * windows_done, rows_ready and the rows already copied to a host `out` are untouched by parking.
+ * dsg_queue_set_priority: default 0; higher runs first; read at the next placement.  dsg_queue_park: sets HELD.  dsg_queue_resume: clears it;
+ * the job then competes for a slot like any waiting job.  All three: an unknown ticket -> DSG_E_INVALID with the ticket in dsg_last_error; a
+ * DONE or CANCELLED job -> no-op, 0; park on a parked or held job, resume on a job that is not held -> no-op.  None of them touches the
+ * device.
+ * PLACEMENT, at the start of every round (this replaces the rule stated at dsg_queue_run; dsg_queue_place_prio is the same code on the host):
+ *  1. the WAITING jobs are the PENDING and PARKED jobs that are not HELD and have a window to run (a live job without one cannot be placed),
+ *     ordered by priority descending, then ticket ascending;
+ *  2. the free slots, lowest first, take them in that order;
+ *  3. then every waiting job W still unplaced, in order, looks among the running jobs NOT placed in this round for the victim V: the lowest
+ *     priority; ties go first to a job without a window to run this round (an idle live job), then to the highest ticket.  If
+ *     priority(V) < priority(W) strictly, V is parked and W takes its slot; otherwise the placement ends.
+ * With all priorities equal and no HELD bit this is the rule above: the same slots, the same first_round, the same launches -- no copy and
+ * no kernel is added to such a session -- and dsg_queue_place_prio(K, arrive, NULL, ...) gives dsg_queue_place's first_round.  There is
+ * no ageing: a low priority starves for as long as higher ones keep the slots; that policy is the caller's.
+ * dsg_queue_place_prio: host only.  K, arrive_round as dsg_queue_place; priority NULL: all 0.  first_round[j]: the round of window 0;
+ * done_round[j]: the round of its last window; n_parks[j]: how often it is pre-empted; *n_rounds: one past the last done_round.  DSG_E_INVALID
+ * as dsg_queue_place, and for a null output.
+ * OTHER CALLS: dsg_queue_run returns early when nothing can run: held jobs alone, parked or pending, run no round.  dsg_queue_info:
+ * n_pending counts PENDING + PARKED.  dsg_queue_cancel on a parked job releases its staging; dsg_queue_close abandons parked jobs as it does
+ * running ones.  dsg_queue_finish on a parked live job whose given windows have all run: DONE before the call returns, as for a running
+ * one; with keep_last_tail the closing S rows come from the parked block instead of the slot's tail.  A parked live job with windows left
+ * waits for a slot like every parked job.
+ * On the device.  Park: job V stands on window c in lane l, position p; clip_tail[(c - 1) & 1] + p * S * J of lane l is copied into a
+ * staging block of the job (S * J * 4 bytes) on lane l's stream, in front of that lane's gather for the round -- whoever takes the slot
+ * overwrites y['seed'] and the tail only behind it in stream order.  Resume into lane l', position p': k_clipq_gather, in the launch that
+ * gathers the slot's style and audio, writes both images the hand-off would have left -- clip_tail[(c - 1) & 1][p'][s][j] and, transposed,
+ * y['seed'][p'][j][s]; variant 5 gathers the job's y['seed_last'] again.  When l' != l, lane l''s stream waits on an event recorded behind
+ * the park copy.  Slots that do not resume take the path they took before.
+ * Added without a version step: dsg_version() stays 330; dsg_clip_job, dsg_clip_edit, dsg_queue_window and dsg_queue_job_info keep their
+ * sizes and layouts. */
+enum { DSG_JOB_PARKED = 4 };      /* dsg_queue_job_info.state */
+enum { DSG_JOB_HELD = 4 };        /* bit of dsg_queue_job_info.live, beside DSG_JOB_LIVE | DSG_JOB_FINISHED */
+int dsg_queue_set_priority(dsg_queue* q, int64_t ticket, int32_t priority);
+int dsg_queue_park(dsg_queue* q, int64_t ticket);
+int dsg_queue_resume(dsg_queue* q, int64_t ticket);
+int dsg_queue_place_prio(const int32_t* K, const int32_t* arrive_round /* NULL: all 0 */, const int32_t* priority /* NULL: all 0 */,
+                         int n_jobs, int n_slots, int32_t* first_round, int32_t* done_round, int32_t* n_parks, int32_t* n_rounds);
 /* Per-element noise streams ("keyed noise") for dsg_sample / _multi / dsg_sample_clip / _multi.  seeds, stream_ids: HOST uint64[B], copied by
  * the call.  While set, element b of the batch draws from its own pair (seed_b, sid_b): draw d at frame f, feature j is
  *   philox4x32_10(ctr = ((f * Jq + j) >> 2, d, sid_b lo, sid_b hi), key = (seed_b lo, seed_b hi)) + Box-Muller,   Jq = J rounded up to 4,
